@@ -1,6 +1,6 @@
 """Benchmark: FD EMRI waveforms/s on MI355X (BASELINE.json metric, config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -33,6 +33,10 @@ the committed profile, per SPA evaluation, times this run's evaluations) / launc
 78.6 TFLOP/s. traffic: HBM bytes per launch from the same PMC pass. SURVEY.md section 8d's
 scatter-formulation bytes (32 B per SPA contribution) are reported as scatter_equiv_gbs, a
 secondary figure: the kernel never issues that traffic.
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR then
+writes what the last timed step computed (see dump_outputs). The three legs below are timed
+only with --full (fields few_gen, cpu_baseline, cpu_reference are null without it).
 
 few_gen: the drivers' whole GenerateEMRIWaveform call on the same source, one at a time (host
 upstream + device pipeline; rank 0 at N = 1), next to the batched device rate.
@@ -401,6 +405,32 @@ def cpu_reference(w, seconds=5.0):
                       f"{dt:.1f} s on {threads} threads, extrapolated by contribution count"}
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each (name, array) as DIR/<name>.npy in float64 (a complex array as
+    its (..., 2) real/imaginary view), what a caller of the timed path holds after the last
+    timed step. The inputs are fixed by the arguments (seeded draws), so two builds run with the
+    same arguments can be compared file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays:
+        a = np.ascontiguousarray(a)
+        if np.iscomplexobj(a):
+            a = a.astype(np.complex128).view(np.float64).reshape(a.shape + (2,))
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
+
+
+DUMP_BYTES = 48 << 20   # budget of one --dump-outputs directory (the limit is 64 MB)
+DUMP_SEED = 2601996
+
+
+def sample_bins(n, n_arrays):
+    """Sorted bin indices shared by the n_arrays complex128 outputs of length n that
+    --dump-outputs writes: every bin when they fit DUMP_BYTES, else a fixed seeded draw."""
+    cap = DUMP_BYTES // (16 * max(1, n_arrays))
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -412,8 +442,18 @@ def main():
     ap.add_argument("--sources", default="walkers", choices=["walkers", "same"],
                     help="the B waveforms of a step: distinct sources from emri_pe.py's walker "
                          "start around config 2's (default), or B copies of config 2's source")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float64): h+/hx of its B waveforms (hp_<j>, hc_<j>) at "
+                         "the bins of sample_bins.npy, a fixed seeded sample of f >= 0; "
+                         "--likelihood: logL.npy; --scan: summary.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also time what is not part of the headline figure: few_gen (the "
+                         "drivers' whole call), cpu_baseline (the host twin) and cpu_reference "
+                         "(the oracle); --likelihood / --scan: their cpu_baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without its host legs (few_gen, cpu_baseline, cpu_reference)")
     ap.add_argument("--pipeline", default="overlap", choices=["overlap", "serial"],
                     help="overlap: prepare(i+1) on a second stream beside sum(i), fused h+/hx; "
                          "serial: one stream, efd_modesum + efd_polarizations")
@@ -456,6 +496,8 @@ def main():
     ap.add_argument("--api-steps", type=int, default=2,
                     help="--likelihood: half-steps timed with the host upstream in the loop")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world_size(args.gpus)
 
     import torch
@@ -579,6 +621,19 @@ def main():
         for x in sl["wf"]:
             if not x["eng"].status(s_sum.cuda_stream):
                 raise RuntimeError(f"efd_modesum reported a device error: {_lib.last_error(lib)}")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's slot: h+/hx of its B waveforms (complex128 over f >= 0), and in
+        # the serial pipeline the two-sided S they were split from
+        wf = slots[(args.steps - 1) % len(slots)]["wf"]
+        sel = sample_bins(nf - k0, 2 * len(wf))
+        sel_d = torch.as_tensor(sel, device=dev)
+        out = [("sample_bins", sel)]
+        for j, x in enumerate(wf):
+            for name, buf in (("hp", x["fhp"]), ("hc", x["fhc"])):
+                out.append((f"{name}_{j}", buf.index_select(0, sel_d).cpu().numpy()))
+            if x["fS"] is not None:
+                out.append((f"S_{j}", x["fS"][k0:].index_select(0, sel_d).cpu().numpy()))
+        dump_outputs(args.dump_outputs, out)
     # per-launch k_modesum duration, live over the timed region (HIP events on the sum stream;
     # with the overlap pipeline the next waveform's preparation kernels share the GPU with it)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
@@ -616,7 +671,7 @@ def main():
         scatter_gbs = b_alg / (kern_ms * 1e-3) / 1e9
         roof = fp64_roofline(B, n_eval, kern_ms, args.caustic, args.sources)
         cpu = cpu_ref = api = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 api = few_gen_timing(w, caustic=args.caustic)
             except Exception as exc:  # not part of the metric: never kill the GPU measurement
@@ -739,7 +794,9 @@ def bench_scan(args):
         times.append(float(res.seconds.max()))
     sweep = float(np.median(times))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("summary", np.asarray(res.summary))])
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the host twin over the same 100 points (inputs from the same stand-in upstream,
         # prepared beforehand; the upstream's own cost is reported beside it)
         try:
@@ -862,8 +919,10 @@ def bench_likelihood(args):
         tt = torch.tensor([elapsed, api], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, api = float(tt[0]), float(tt[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("logL", np.asarray(ll))])
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the host twin on the same walkers (all of the start's for config 4, the first
         # half-step's 64 for config 5) against the device logL of the same rows
         try:

@@ -11,7 +11,7 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_batch_prepare.py tests/test
 tail -2 $O/like_tests.log
 timeout -k 10 500 python tools/configs.py --reps 5 > $O/configs.jsonl 2> $O/configs.err || { tail -20 $O/configs.err; exit 2; }
 for c in config4 config5; do
-  timeout -k 10 300 python bench.py --likelihood $c --steps 40 --warmup 4 --api-steps 4 > $O/like_$c.json 2> $O/like_$c.err || { tail -20 $O/like_$c.err; exit 3; }
+  timeout -k 10 300 python bench.py --full --likelihood $c --steps 40 --warmup 4 --api-steps 4 > $O/like_$c.json 2> $O/like_$c.err || { tail -20 $O/like_$c.err; exit 3; }
   cat $O/like_$c.json
 done
 for c in 4 5; do

@@ -8,7 +8,7 @@ TAG=$1; shift
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 400 python bench.py "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 2; }
+timeout -k 10 400 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 2; }
 cat $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --no-cpu-baseline --steps 50 --warmup 5 $*"
