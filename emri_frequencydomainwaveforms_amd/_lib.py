@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "efd_hann_loglike",
     "efd_hann_loglike_local",
     "efd_hann_loglike_local_partials",
+    "efd_cosw_polarizations",
+    "efd_cosw_loglike",
     "efd_loglike",
     "efd_inner_product",
     "efd_modesum_cpu",
@@ -257,6 +259,11 @@ def load(path=None):
                                            vp, vp, vp]
     lib.efd_hann_loglike_local_partials.restype = ctypes.c_int
     lib.efd_hann_loglike_local_partials.argtypes = [i64]
+    lib.efd_cosw_polarizations.restype = ctypes.c_int
+    lib.efd_cosw_polarizations.argtypes = [vp, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp]
+    lib.efd_cosw_loglike.restype = ctypes.c_int
+    lib.efd_cosw_loglike.argtypes = [vp, i64, vp, vp, i64, i32, i64, i64, vp, i32, vp, vp, vp, vp,
+                                     vp]
     lib.efd_loglike.restype = ctypes.c_int
     lib.efd_loglike.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
     lib.efd_inner_product.restype = ctypes.c_int

@@ -5196,6 +5196,202 @@ __global__ __launch_bounds__(256) void k_hann_loglike_partial(
     }
 }
 
+// ---- Cosine-sum windows (efd_cosw_*; fdutils.CosineWindowConvolution): scipy's symmetric
+// w[n] = sum_j (-1)^j a_j cos(2 pi j n / (nf - 1)), j <= J <= 3 (hamming, blackman, nuttall,
+// blackmanharris). The Hann expansion at the shifts +-j (1 + e), e = 1 / (nf - 1), with the same
+// correction C (the transforms above, unchanged):
+//   S_w[k] = a_0 S[k] + sum_j b_j (S[k+j] + S[k-j]) + sum_j b_j j e (C[k+j] - C[k-j]),
+//   b_j = (-1)^j a_j / 2, indices mod nf.
+// A bin's 2J+1 S and 2J Y neighbours overlap its neighbours' (26 loads a bin pair at J = 3
+// against the Hann kernels' 10), so a workgroup stages its tile's bins and their mirrors, each
+// with a halo of J, in LDS once (S zeroed outside the row's support as hann_sw reads it; Y at
+// hann_sw's index) and every thread takes its neighbours from there.
+struct CoswCoef {
+    double a0;
+    double b[3];   // (-1)^j a_j / 2 for j = 1..3 (0 past J)
+    double g[3];   // b_j j / (nf - 1): times the row's scale, the weight of Y[k+j] - Y[k-j]
+};
+constexpr int COSW_TILE = 256;
+template <int J>
+struct CoswTile {
+    // side 0: bins kb - J + e; side 1: the mirrors, bins nf - kb - COSW_TILE - J + e
+    double2 s[2][COSW_TILE + 2 * J];
+    float2 y[2][COSW_TILE + 2 * J];
+};
+// kb: the tile's first bin. A tile's last bins may lie past nf - 1 (and their mirrors below 0):
+// such places hold 0 and no thread with a bin reads them. nf >= 2J + 1, so one wrap each way
+// brings every neighbour of a bin in [0, nf) back into the grid.
+// A thread fetches place threadIdx.x of both sides, and the first 2J lanes of waves 0 and 1 the
+// halo place COSW_TILE + lane of side 0 and 1: straight-line loads into registers (cosw_fetch),
+// all in flight together, then the LDS stores (cosw_put).
+struct CoswRegs {
+    double2 s[3];
+    float2 y[3];
+};
+__device__ __forceinline__ void cosw_fetch_one(const double2* __restrict__ S,
+                                               const float2* __restrict__ Y, int64_t nf,
+                                               int64_t kk, int64_t first, int64_t len,
+                                               int64_t off, double2& sv, float2& yv) {
+    kk += kk < 0 ? nf : 0;
+    kk -= kk >= nf ? nf : 0;
+    sv = make_double2(0.0, 0.0);
+    yv = make_float2(0.f, 0.f);
+    if (kk >= 0 && kk < nf) {
+        int64_t q = kk - first;
+        q += q < 0 ? nf : 0;
+        if (q < len) sv = S[kk];
+        yv = Y[q + off];
+    }
+}
+template <int J>
+__device__ __forceinline__ void cosw_fetch(CoswRegs& r, const double2* __restrict__ S,
+                                           const float2* __restrict__ Y, int64_t nf, int64_t kb,
+                                           int64_t first, int64_t len, int64_t off) {
+    const int64_t base0 = kb - J, base1 = nf - kb - COSW_TILE - J;
+    const int x = threadIdx.x, hs = x >> 6, hl = x & 63;
+    cosw_fetch_one(S, Y, nf, base0 + x, first, len, off, r.s[0], r.y[0]);
+    cosw_fetch_one(S, Y, nf, base1 + x, first, len, off, r.s[1], r.y[1]);
+    if (hs < 2 && hl < 2 * J)
+        cosw_fetch_one(S, Y, nf, (hs == 0 ? base0 : base1) + COSW_TILE + hl, first, len, off,
+                       r.s[2], r.y[2]);
+}
+template <int J>
+__device__ __forceinline__ void cosw_put(CoswTile<J>& t, const CoswRegs& r) {
+    const int x = threadIdx.x, hs = x >> 6, hl = x & 63;
+    t.s[0][x] = r.s[0];
+    t.y[0][x] = r.y[0];
+    t.s[1][x] = r.s[1];
+    t.y[1][x] = r.y[1];
+    if (hs < 2 && hl < 2 * J) {
+        t.s[hs][COSW_TILE + hl] = r.s[2];
+        t.y[hs][COSW_TILE + hl] = r.y[2];
+    }
+}
+// S_w of the bin staged at place c (g: CoswCoef.g times the row's scale)
+template <int J>
+__device__ __forceinline__ double2 cosw_sw(const double2* s, const float2* y, int c,
+                                           const CoswCoef& cf, const double* g) {
+#pragma clang fp contract(off)
+    const double2 s0 = s[c];
+    double2 v = make_double2(cf.a0 * s0.x, cf.a0 * s0.y);
+#pragma unroll
+    for (int j = 1; j <= J; ++j) {
+        const double2 sp = s[c + j], sm = s[c - j];
+        const float2 yp = y[c + j], ym = y[c - j];
+        v.x = (v.x + cf.b[j - 1] * (sp.x + sm.x)) + g[j - 1] * ((double)yp.x - (double)ym.x);
+        v.y = (v.y + cf.b[j - 1] * (sp.y + sm.y)) + g[j - 1] * ((double)yp.y - (double)ym.y);
+    }
+    return v;
+}
+// hann_pol's split for thread x of a staged tile: bin kb + x (a) and its mirror (b)
+template <int J>
+__device__ __forceinline__ void cosw_pol(const CoswTile<J>& t, int x, const CoswCoef& cf,
+                                         const double* g, double2& vp, double2& vc) {
+    const double2 a = cosw_sw<J>(t.s[0], t.y[0], x + J, cf, g);
+    const double2 b = cosw_sw<J>(t.s[1], t.y[1], COSW_TILE - 1 - x + J, cf, g);
+    vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
+    vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
+}
+template <int J>
+__global__ __launch_bounds__(COSW_TILE) void k_cosw_polarizations(
+    const double2* __restrict__ S, const float2* __restrict__ Y,
+    const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0, CoswCoef cf,
+    double2* __restrict__ hp, double2* __restrict__ hc) {
+    __shared__ CoswTile<J> t;
+    const int64_t ib = (int64_t)blockIdx.x * COSW_TILE;
+    const HannRow h = hann_row(info, 0);
+    CoswRegs r;
+    cosw_fetch<J>(r, S, Y, nf, k0 + ib, h.first, h.len, m - nf);
+    cosw_put<J>(t, r);
+    __syncthreads();
+    const int64_t i = ib + threadIdx.x;
+    if (k0 + i >= nf) return;
+    double g[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) g[j] = cf.g[j] * h.scale;   // a NaN scale: a NaN row
+    double2 vp, vc;
+    cosw_pol<J>(t, threadIdx.x, cf, g, vp, vc);
+    hp[i] = vp;
+    hc[i] = vc;
+}
+// k_hann_loglike_partial with the general stencil: the same workgroup-to-XCD mapping, row
+// groups, term order and reductions; a row's tile is staged by its workgroup alone and its
+// partial sums the same bins in the same order whatever RPT and the other rows are.
+template <int J, int RPT>
+__global__ __launch_bounds__(COSW_TILE) void k_cosw_loglike_partial(
+    const double2* __restrict__ S, int64_t stride, const float2* __restrict__ Y,
+    const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0, CoswCoef cf,
+    const double2* __restrict__ d, const double* __restrict__ w, int rows, int nchunk,
+    double* __restrict__ part) {
+#pragma clang fp contract(off)
+    __shared__ CoswTile<J> t[RPT];
+    const int ngr = rows / RPT;
+    const int j = (int)(blockIdx.x >> 3);
+    const int r0 = (j % ngr) * RPT, chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
+    double g[RPT][3];
+    int64_t first[RPT], len[RPT];
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) {
+        const HannRow h = hann_row(info, r0 + q);
+#pragma unroll
+        for (int jj = 0; jj < 3; ++jj) g[q][jj] = cf.g[jj] * h.scale;
+        first[q] = h.first;
+        len[q] = h.len;
+    }
+    const int64_t nb = nf - k0;
+    double acc[RPT];
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) acc[q] = 0.0;
+    // (the tile loop is uniform over the workgroup: the barriers sit outside the bin's test)
+    for (int64_t ib = (int64_t)chunk * COSW_TILE; ib < nb; ib += (int64_t)nchunk * COSW_TILE) {
+        // the bin's d and w are asked for ahead of the staging, so that their latency runs
+        // beside the tile's and not after the barrier
+        const int64_t i = ib + threadIdx.x;
+        double2 d0 = make_double2(0.0, 0.0), d1 = d0;
+        double w0 = 0.0, w1 = 0.0;
+        if (i < nb) {
+            d0 = d[i];
+            d1 = d[nb + i];
+            w0 = w[i];
+            w1 = w[nb + i];
+        }
+        CoswRegs r[RPT];
+#pragma unroll
+        for (int q = 0; q < RPT; ++q)
+            cosw_fetch<J>(r[q], S + (int64_t)(r0 + q) * stride, Y + (int64_t)(r0 + q) * m, nf,
+                          k0 + ib, first[q], len[q], m - nf);
+#pragma unroll
+        for (int q = 0; q < RPT; ++q) cosw_put<J>(t[q], r[q]);
+        __syncthreads();
+        if (i < nb) {
+#pragma unroll
+            for (int q = 0; q < RPT; ++q) {
+                double2 vp, vc;
+                cosw_pol<J>(t[q], threadIdx.x, cf, g[q], vp, vc);
+                const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
+                const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
+                acc[q] = fma(x0, x0, fma(y0, y0, acc[q]));
+                acc[q] = fma(x1, x1, fma(y1, y1, acc[q]));
+            }
+        }
+        __syncthreads();
+    }
+    // a butterfly over each wave, then the 4 waves in turn (fixed order)
+    __shared__ double red[RPT][4];
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) {
+        double a = acc[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < RPT && chunk < nchunk) {
+        const int q = threadIdx.x;
+        part[(int64_t)(r0 + q) * nchunk + chunk] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
+    }
+}
+
 // (C) with the windowed logL fused in (efd_hann_loglike_local). Per bin the two channels' terms
 // of a bin k and of its mirror k' = nf-1-k combine into one term on each (with the same weight
 // w on both channels, p = d0 - w h+, q = d1 - w hx: |p|^2 + |q|^2 = (|p - iq|^2 + |p + iq|^2)/2,
@@ -6489,6 +6685,92 @@ int efd_hann_loglike(const double* S, int64_t stride, const float* Y, const uint
                        dim3((unsigned)(np * (rows / rpt))), dim3(threads), 0, st,
                        (const double2*)S, stride, (const float2*)Y, info, m, nf, k0,
                        (const double2*)d, w, (int)rows, np, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+// the stencil's weights from the window's coefficients a_0..a_J (host doubles)
+static bool cosw_coef(const double* a, int32_t nterm, int64_t nf, CoswCoef& cf) {
+    if (!a || nterm < 2 || nterm > 4 || nf < 2 * (int64_t)(nterm - 1) + 1) return false;
+    cf.a0 = a[0];
+    for (int j = 1; j <= 3; ++j) {
+        cf.b[j - 1] = j < nterm ? ((j & 1) ? -0.5 : 0.5) * a[j] : 0.0;
+        cf.g[j - 1] = cf.b[j - 1] * (double)j / (double)(nf - 1);
+    }
+    return true;
+}
+}  // extern "C"
+template <int J>
+static void cosw_launch_pol(int64_t blocks, hipStream_t st, const double* S, const float* Y,
+                            const uint64_t* info, int64_t m, int64_t nf, int64_t k0,
+                            const CoswCoef& cf, double* hp, double* hc) {
+    hipLaunchKernelGGL(k_cosw_polarizations<J>, dim3((unsigned)blocks), dim3(COSW_TILE), 0, st,
+                       (const double2*)S, (const float2*)Y, info, m, nf, k0, cf, (double2*)hp,
+                       (double2*)hc);
+}
+template <int J>
+static void cosw_launch_ll(int rpt, int np, hipStream_t st, const double* S, int64_t stride,
+                           const float* Y, const uint64_t* info, int64_t m, int32_t rows,
+                           int64_t nf, int64_t k0, const CoswCoef& cf, const double* d,
+                           const double* w, double* scratch) {
+    hipLaunchKernelGGL((rpt == 2 ? k_cosw_loglike_partial<J, 2> : k_cosw_loglike_partial<J, 1>),
+                       dim3((unsigned)(np * (rows / rpt))), dim3(COSW_TILE), 0, st,
+                       (const double2*)S, stride, (const float2*)Y, info, m, nf, k0, cf,
+                       (const double2*)d, w, (int)rows, np, scratch);
+}
+extern "C" {
+int efd_cosw_polarizations(const double* S, const float* Y, const uint64_t* info, int64_t m,
+                           int64_t nf, int64_t k0, const double* a, int32_t nterm, double* hp,
+                           double* hc, void* stream) {
+    CoswCoef cf;
+    if (!S || !Y || !info || !hp || !hc || !cosw_coef(a, nterm, nf, cf) || m < nf || k0 < 0 ||
+        k0 > nf)
+        return fail(EFD_ERR_ARG, "efd_cosw_polarizations: bad arguments (2 <= nterm <= 4, "
+                                 "nf >= 2 (nterm - 1) + 1)");
+    const int64_t cnt = nf - k0;
+    if (cnt == 0) return EFD_OK;
+    const int64_t blocks = (cnt + COSW_TILE - 1) / COSW_TILE;
+    hipStream_t st = (hipStream_t)stream;
+    switch (nterm - 1) {
+        case 1: cosw_launch_pol<1>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
+        case 2: cosw_launch_pol<2>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
+        default: cosw_launch_pol<3>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+int efd_cosw_loglike(const double* S, int64_t stride, const float* Y, const uint64_t* info,
+                     int64_t m, int32_t rows, int64_t nf, int64_t k0, const double* a,
+                     int32_t nterm, const double* d, const double* w, double* out,
+                     double* scratch, void* stream) {
+    CoswCoef cf;
+    if (!hann_rows_ok("efd_cosw_loglike", S, stride, nf, rows) || !Y || !info || !d || !w ||
+        !out || !scratch || !cosw_coef(a, nterm, nf, cf) || m < nf || k0 < 0 || k0 >= nf ||
+        rows > HANN_ROWS_MAX)
+        return fail(EFD_ERR_ARG, "efd_cosw_loglike: bad arguments (rows <= 16, 2 <= nterm <= 4, "
+                                 "nf >= 2 (nterm - 1) + 1)");
+    const int64_t nb = nf - k0;
+    // efd_hann_loglike's chunks and row grouping
+    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH,
+                                          ((nb + COSW_TILE - 1) / COSW_TILE + 7) / 8 * 8);
+    hipStream_t st = (hipStream_t)stream;
+    const int rpt = (rows % 2 == 0) ? 2 : 1;
+    switch (nterm - 1) {
+        case 1:
+            cosw_launch_ll<1>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
+                              scratch);
+            break;
+        case 2:
+            cosw_launch_ll<2>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
+                              scratch);
+            break;
+        default:
+            cosw_launch_ll<3>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
+                              scratch);
+            break;
+    }
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
     HIP_TRY(hipGetLastError());

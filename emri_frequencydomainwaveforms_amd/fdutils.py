@@ -437,6 +437,123 @@ class HannConvolution:
         return 0.5 * S - 0.25 * (Sp + Sm) - (0.25 * self.eps) * Cd
 
 
+# scipy.signal.windows' symmetric cosine-sum windows, w[n] = sum_j (-1)^j a_j cos(2 pi j n /
+# (N - 1)): the reference's mode-by-mode driver windows its FD templates with blackman, hann and
+# nuttall (check_mode_by_mode.py:269-272) and imports hamming and blackmanharris
+COSINE_WINDOWS = {
+    "hann": (0.5, 0.5),
+    "hamming": (0.54, 0.46),
+    "blackman": (0.42, 0.5, 0.08),
+    "nuttall": (0.3635819, 0.4891775, 0.1365995, 0.0106411),
+    "blackmanharris": (0.35875, 0.48829, 0.14128, 0.01168),
+}
+
+
+def cosine_window(window):
+    """(name, coefficients) when window is scipy.signal.windows.<name>(len(window)) (sym=True)
+    for a name in COSINE_WINDOWS, bit for bit (as HannConvolution.matches), else None. A few
+    samples reject the other candidates first, so at most one full-length window is built."""
+    import scipy.signal.windows as sw
+    w = np.asarray(window.cpu().numpy() if hasattr(window, "detach") else window)
+    if w.ndim != 1 or len(w) < 3 or not np.isrealobj(w):
+        return None
+    n = len(w)
+    at = np.unique(np.array([0, 1, n // 7, n // 3, n // 2, n - 2, n - 1]))
+    for name, a in COSINE_WINDOWS.items():
+        probe = sum((-1) ** j * aj * np.cos(2.0 * np.pi * j * at / (n - 1))
+                    for j, aj in enumerate(a))
+        if (np.all(np.abs(w[at] - probe) <= 1e-12)
+                and np.array_equal(w, getattr(sw, name)(n))):
+            return name, a
+    return None
+
+
+class CosineWindowConvolution(HannConvolution):
+    """HannConvolution's first-order form for a cosine-sum window of coefficients a_0..a_J
+    (J <= 3), at the shifts +-j (1 + e) of the trigonometric interpolant:
+      S_w[k] = a_0 S[k] + sum_{j=1..J} (-1)^j (a_j / 2) [S[k+j] + S[k-j]
+                                                        + j e (C[k+j] - C[k-j])] + O(e^2),
+    C = K (*) S as there: the lag kernel, the supports, the transform lengths and the
+    transforms are HannConvolution's own (C does not depend on the window), only the stencil
+    that reads S and Y is general (efd_cosw_polarizations, efd_cosw_loglike). The dropped term
+    scales with j^2 a_j per shift: within 10 q / N^2 of max|S|, q = sum_j a_j j^2 (Hann's
+    5 / N^2 at q = 1/2; measured 0.3-0.4 of it for blackman, nuttall and blackmanharris).
+    The local logL form (efd_hann_loglike_local) is the Hann stencil's alone: not offered."""
+
+    def __init__(self, n, device, coeffs):
+        import ctypes
+        a = tuple(float(x) for x in coeffs)
+        if not 2 <= len(a) <= 4:
+            raise ValueError("CosineWindowConvolution: 2 to 4 coefficients")
+        if int(n) < 2 * (len(a) - 1) + 1:
+            raise ValueError("CosineWindowConvolution: n >= 2 J + 1")
+        super().__init__(n, device)
+        self.coeffs = a
+        self._a = (ctypes.c_double * len(a))(*a)
+
+    @staticmethod
+    def q(coeffs):
+        """sum_j a_j j^2: the second-order term's weight (Hann: 1/2)."""
+        return sum(float(aj) * j * j for j, aj in enumerate(coeffs))
+
+    @classmethod
+    def applies(cls, n, coeffs=COSINE_WINDOWS["hann"]):
+        """Whether the first-order form is within TOL of max|S| at grid length n."""
+        return (int(n) >= 2 * (len(coeffs) - 1) + 1
+                and 10.0 * cls.q(coeffs) / float(n) ** 2 <= cls.TOL)
+
+    def polarizations_batch(self, S, outs, k0, lib, lanes=None, support=None):
+        """polarizations for every row of S ([B][n], contiguous): one transform pair over the
+        rows and one efd_cosw_polarizations per row into outs[i] = (hp, hc)."""
+        from . import _lib
+        torch = require_gpu()
+        S = self._rows(S)
+        Y, info, m = self.transform(S, lib, lanes, support)
+        st = torch.cuda.current_stream(S.device).cuda_stream
+        for i, (hp, hc) in enumerate(outs):
+            _lib.check(lib.efd_cosw_polarizations(
+                torch.view_as_real(S[i]).data_ptr(), torch.view_as_real(Y[i]).data_ptr(),
+                info[i].data_ptr(), m, self.n, k0, self._a, len(self.coeffs),
+                torch.view_as_real(hp).data_ptr(), torch.view_as_real(hc).data_ptr(), st),
+                "efd_cosw_polarizations", lib)
+        return outs
+
+    def loglike_batch(self, S, d, w, k0, out, scratch, lib, lanes=None, support=None):
+        """efd_cosw_loglike: HannConvolution.loglike_batch with this window's stencil."""
+        from . import _lib
+        torch = require_gpu()
+        S = self._rows(S)
+        rows = int(S.shape[0])
+        Y, info, m = self.transform(S, lib, lanes, support)
+        st = torch.cuda.current_stream(S.device).cuda_stream
+        _lib.check(lib.efd_cosw_loglike(
+            torch.view_as_real(S).data_ptr(), self.n, torch.view_as_real(Y).data_ptr(),
+            info.data_ptr(), m, rows, self.n, k0, self._a, len(self.coeffs),
+            torch.view_as_real(d).data_ptr(), w.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+            st), "efd_cosw_loglike", lib)
+        return out
+
+    def local_ok(self, d, w, k0):
+        return False
+
+    def local_emit(self, S, wl, kself, lib, lanes=None, support=None):
+        raise ValueError("the local logL form is the Hann window's only")
+
+    def loglike_local(self, S, local, out, scratch, lib, lanes=None, support=None):
+        raise ValueError("the local logL form is the Hann window's only")
+
+    def __call__(self, S):
+        torch = require_gpu()
+        C = self.correction(S)
+        out = self.coeffs[0] * S
+        for j in range(1, len(self.coeffs)):
+            b = (-1) ** j * 0.5 * self.coeffs[j]
+            out = out + b * (torch.roll(S, -j, dims=-1) + torch.roll(S, j, dims=-1))
+            out = out + (b * j * self.eps) * (torch.roll(C, -j, dims=-1)
+                                              - torch.roll(C, j, dims=-1))
+        return out
+
+
 def windowed_spectrum(S, mult):
     """The two-sided spectrum S = h+ - i hx (rows: one waveform each) convolved with the
     window: ifft(mult * fft(S)) along the last axis (rocFFT, batched over rows).
@@ -485,6 +602,18 @@ class get_fd_waveform_fromFD:
                       if window is not None and not window_in_fd
                       and HannConvolution.applies(len(window)) and HannConvolution.matches(window)
                       else None)
+        # scipy's other cosine-sum windows (hamming, blackman, nuttall, blackmanharris) take the
+        # same form with their own stencil where it is within TOL (CosineWindowConvolution);
+        # _conv is whichever of the two applies. The local logL form stays _hann's alone.
+        self._cosw = None
+        self.window_name = None if self._hann is None else "hann"
+        if self._hann is None and window is not None and not window_in_fd:
+            found = cosine_window(window)
+            if found is not None:
+                self.window_name = found[0]
+                if found[0] != "hann" and CosineWindowConvolution.applies(len(window), found[1]):
+                    self._cosw = CosineWindowConvolution(len(window), dev, found[1])
+        self._conv = self._hann if self._hann is not None else self._cosw
         # contiguous-suffix mask (f >= 0 of a sorted grid): the fused fill path applies
         pm = self.positive_frequency_mask
         k0 = int(torch.argmax(pm.to(torch.int8)).item()) if bool(pm.any()) else int(pm.numel())
@@ -572,7 +701,7 @@ class get_fd_waveform_fromFD:
 
     @property
     def can_fill_batch(self):
-        return self._hann is not None and self._windowed_s_path()
+        return self._conv is not None and self._windowed_s_path()
 
     def _spectra(self, params, **kwargs):
         """Every walker's two-sided spectrum in one [B][N] buffer; returns (rows,
@@ -580,7 +709,7 @@ class get_fd_waveform_fromFD:
         the rows' lane ranges or None)."""
         torch = require_gpu()
         if not self.can_fill_batch:
-            raise ValueError("the Hann-window spectrum path only")
+            raise ValueError("the cosine-sum windows' spectrum path only")
         gen = self.waveform_generator
         B = len(params)
         n = int(self.positive_frequency_mask.numel())
@@ -625,15 +754,16 @@ class get_fd_waveform_fromFD:
 
     def fill_batch(self, outs, params, **kwargs):
         """fill for a batch of walkers (rows of params, FEW's 14) into outs[i] (complex128
-        [2][num_bins] each): the walkers' spectra in one [B][N] buffer, then the Hann window
-        for all of them (one transform pair over the rows, HannConvolution.polarizations_batch).
+        [2][num_bins] each): the walkers' spectra in one [B][N] buffer, then the window (Hann,
+        or another of COSINE_WINDOWS) for all of them (one transform pair over the rows,
+        HannConvolution.polarizations_batch).
         Same values as B fill calls up to the batched transform's rounding (the correction term
         carries ~1e-6 of max|S|; it enters at <= 1e-12). The engine's device-side status is
         checked once, at the end."""
         if len(params) == 0:
             return outs
         S, cw, single, lanes = self._spectra(params, **kwargs)
-        self._hann.polarizations_batch(S, [(o[0], o[1]) for o in outs], self._suffix_k0,
+        self._conv.polarizations_batch(S, [(o[0], o[1]) for o in outs], self._suffix_k0,
                                        cw.engine.lib, lanes, self._lane_support(S, lanes))
         self._status(cw, single)
         return outs
@@ -644,7 +774,7 @@ class get_fd_waveform_fromFD:
         if lanes is None:
             return None
         self.waveform_generator.lanes_ready()
-        return self._hann.lane_support(self._lanes_host[:S.shape[0]].numpy(), S.shape[1])
+        return self._conv.lane_support(self._lanes_host[:S.shape[0]].numpy(), S.shape[1])
 
     def loglike_batch(self, out, params, d, w, scratch, local=None, **kwargs):
         """The windowed templates' log-likelihoods of a batch of walkers into out (float64
@@ -652,14 +782,16 @@ class get_fd_waveform_fromFD:
         fill_batch, then HannConvolution.loglike_batch (efd_hann_loglike: no template is
         written). The same logL as fill_batch + efd_loglike up to the reduction order.
         local: hann_local's data for d, w: the logL reduced inside the transforms' last pass
-        (HannConvolution.loglike_local) where the transform length allows it."""
+        (HannConvolution.loglike_local) where the transform length allows it (the Hann window
+        only: that form hard-codes its stencil)."""
         if len(params) == 0:
             return out
         S, cw, single, lanes = self._spectra(params, **kwargs)
         support = self._lane_support(S, lanes)
-        if local is None or not self._hann.loglike_local(S, local, out, scratch, cw.engine.lib,
-                                                         lanes, support):
-            self._hann.loglike_batch(S, d, w, self._suffix_k0, out, scratch, cw.engine.lib,
+        if (local is None or self._hann is None
+                or not self._hann.loglike_local(S, local, out, scratch, cw.engine.lib, lanes,
+                                                support)):
+            self._conv.loglike_batch(S, d, w, self._suffix_k0, out, scratch, cw.engine.lib,
                                      lanes, support)
         self._status(cw, single)
         return out
@@ -669,6 +801,9 @@ class get_fd_waveform_fromFD:
         they are those very tensors, unmodified since (the drivers inject data = gen(*truth),
         emri_pe.py:276), else None."""
         made = getattr(self, "_made", None)
+        # (it serves hann_local's emit, the Hann window's only)
+        if getattr(self, "_cosw", None) is not None:
+            return None
         if made is None or not isinstance(channels, (list, tuple)) or len(channels) != 2:
             return None
         params, kw, refs, version = made
@@ -712,8 +847,8 @@ class get_fd_waveform_fromFD:
         cw = gen.waveform_generator.create_waveform
         if self._suffix_k0 != cw.positive_start():
             raise ValueError("positive_frequency_mask does not match the generator's grid")
-        if self._hann is not None:
-            self._hann.polarizations(S.contiguous(), out[0], out[1], self._suffix_k0,
+        if self._conv is not None:
+            self._conv.polarizations(S.contiguous(), out[0], out[1], self._suffix_k0,
                                      cw.engine.lib)
             return out
         cw.polarizations(windowed_spectrum(S, self._mult), True, out=(out[0], out[1]))

@@ -26,6 +26,7 @@ them:
 import os
 
 MAX_THREADS = 16   # the GPU box's CPU share per GPU; more threads per walker batch stop paying
+_START_AFFINITY = frozenset(os.sched_getaffinity(0))   # before any pin()
 
 
 def local_rank_world(env=None):
@@ -59,8 +60,9 @@ def rank_cores(affinity=None, local_rank=None, local_world=None, allowed="auto")
     """This rank's disjoint share of `affinity` (default: the process's affinity set), split
     into `local_world` contiguous chunks of equal size (the remainder goes to the first ranks).
     With fewer cores than ranks every rank keeps one core (round-robin). An affinity set that is
-    a strict subset of `allowed` (default: allowed_cores(), the cgroup's cpuset) was bound per
-    rank by the launcher and is returned whole; EFD_HOST_SPLIT=0 / 1 forces no split / a split."""
+    a strict subset of `allowed` (default: allowed_cores(), the cgroup's cpuset, for the
+    affinity set the process started with; no bound for any other set) was bound per rank by
+    the launcher and is returned whole; EFD_HOST_SPLIT=0 / 1 forces no split / a split."""
     cores = sorted(os.sched_getaffinity(0) if affinity is None else affinity)
     lr, lw = local_rank_world()
     lr = lr if local_rank is None else int(local_rank)
@@ -71,7 +73,13 @@ def rank_cores(affinity=None, local_rank=None, local_world=None, allowed="auto")
     if lw <= 1 or not cores or mode == "0":
         return cores
     if mode != "1":
-        allowed = allowed_cores() if allowed == "auto" else allowed
+        if allowed == "auto":
+            # the cgroup's cpuset bounds the affinity set this process was started with only: a
+            # set passed in that is not that one (a node laid out for planning) is judged by
+            # itself, whatever cores the host this runs on happens to allow (after pin() the
+            # process's set is its share, which may equal such a set by chance)
+            own = affinity is None or set(cores) == _START_AFFINITY
+            allowed = allowed_cores() if own else None
         if allowed is not None and set(cores) < set(allowed):
             return cores   # narrowed below the cgroup's cores: bound per rank, not split again
     if len(cores) < lw:

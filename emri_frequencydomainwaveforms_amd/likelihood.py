@@ -224,10 +224,11 @@ class Likelihood:
                                               out=out[i:i + 1])
             P.wait()
         elif getattr(tm, "can_fill_batch", False) and not args:
-            # windowed templates (the drivers' Hann window): groups of WINDOW_GROUP walkers,
+            # windowed templates (the drivers' Hann window, or another of scipy's cosine-sum
+            # windows: fdutils.COSINE_WINDOWS): groups of WINDOW_GROUP walkers,
             # their spectra in one buffer and the window's transforms batched over them
-            # and the windowed templates' logL reduced in place (efd_hann_loglike, at most
-            # EFD_HANN_ROWS_MAX rows a call). The batch takes keyword waveform arguments only;
+            # and the windowed templates' logL reduced in place (efd_hann_loglike or
+            # efd_cosw_loglike, at most EFD_HANN_ROWS_MAX rows a call). The batch takes keyword waveform arguments only;
             # extra positional ones go to the per-walker fill below, which forwards them
             G = min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
                         or int(getattr(tm, "WINDOW_GROUP", 8))), _lib.EFD_HANN_ROWS_MAX)

@@ -47,10 +47,14 @@ class PESetup:
 
 
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
-          ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True):
+          ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
+          window=None):
     """window_flag: the templates and the injection convolved with a Hann window of the grid's
     length (emri_pe.py:259-263, -window_flag 1 in test.sh: scipy.signal.windows.hann(N), N the
     TD/FD length, odd_len); not with downsampling (emri_pe.py:330-331).
+    window: the same with another of scipy's symmetric cosine-sum windows, by name ("hann",
+    "hamming", "blackman", "nuttall", "blackmanharris": fdutils.COSINE_WINDOWS, the windows
+    check_mode_by_mode.py:269-272 uses and imports); window_flag=True alone means "hann".
     freeze_gc: collect, then move every object alive after the setup (torch's and scipy's
     modules, the likelihood, its grids) out of the cyclic collector's reach (gc.freeze), as a
     sampler process would once its setup is done: a full collection otherwise walks ~200 k
@@ -86,13 +90,17 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     pos = frequency >= 0.0
     info = {"p0": p0, "N_f": int(len(frequency))}
     like_subset = subset
+    window_name = window if window is not None else ("hann" if window_flag else None)
     window = None
-    if window_flag:
+    if window_name is not None:
+        from .fdutils import COSINE_WINDOWS
+        if window_name not in COSINE_WINDOWS:
+            raise ValueError(f"window: one of {sorted(COSINE_WINDOWS)}")
         if downsample:
             raise ValueError("Cannot run downsampling with windowing")   # emri_pe.py:331
-        from scipy.signal.windows import hann
-        window = hann(len(frequency))
-        info["window"] = "hann"
+        import scipy.signal.windows as windows
+        window = getattr(windows, window_name)(len(frequency))
+        info["window"] = window_name
     if downsample:
         fixed = frequency[pos]
         nz = np.abs(sig[0].cpu().numpy()) > 1e-50                    # emri_pe.py:245

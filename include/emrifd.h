@@ -370,6 +370,30 @@ int efd_hann_loglike_local(const double* S, int64_t stride, int64_t nf, int32_t 
 int efd_hann_loglike_local_partials(int64_t m);
 int efd_hann_polarizations(const double* S, const float* Y, const uint64_t* info, int64_t m,
                            int64_t nf, int64_t k0, double* hp, double* hc, void* stream);
+/*
+ * The same for scipy's other symmetric cosine-sum windows (the reference's mode-by-mode driver
+ * windows its FD templates with blackman, hann and nuttall, check_mode_by_mode.py:269-272, and
+ * imports hamming and blackmanharris):
+ *   w[n] = sum_{j=0..J} (-1)^j a_j cos(2 pi j n / (nf - 1)),   J = nterm - 1 in 1..3.
+ * The Hann expansion at the shifts +-j (1 + e), e = 1 / (nf - 1), with the same C (and so the
+ * same info, Y and m: efd_hann_extent, efd_hann_stage / efd_hann_convolve serve every window):
+ *   S_w[k] = a_0 S[k] + sum_{j=1..J} (-1)^j (a_j / 2) [ S[k+j] + S[k-j]
+ *                                                     + j e (C[k+j] - C[k-j]) ],  indices mod nf.
+ * a = (1/2, 1/2) is the Hann form above. The dropped second-order term is within 10 q / nf^2 of
+ * max|S|, q = sum_j a_j j^2 (Hann: 5 / nf^2). a: nterm host doubles a_0..a_J, 2 <= nterm <= 4;
+ * nf >= 2 (nterm - 1) + 1 (every neighbour wraps at most once), else EFD_ERR_ARG.
+ *   efd_cosw_polarizations: efd_hann_polarizations with this stencil (one row).
+ *   efd_cosw_loglike: efd_hann_loglike with this stencil (rows <= 16, the same scratch, term
+ *                    order and reductions; a row's value does not depend on the other rows of
+ *                    the call).
+ */
+int efd_cosw_polarizations(const double* S, const float* Y, const uint64_t* info, int64_t m,
+                           int64_t nf, int64_t k0, const double* a, int32_t nterm,
+                           double* hp, double* hc, void* stream);
+int efd_cosw_loglike(const double* S, int64_t stride, const float* Y, const uint64_t* info,
+                     int64_t m, int32_t rows, int64_t nf, int64_t k0, const double* a,
+                     int32_t nterm, const double* d, const double* w, double* out,
+                     double* scratch, void* stream);
 
 /*
  * Fused Gaussian log-likelihood over nchan channels of nbin bins each:
