@@ -18,6 +18,8 @@ EFD_CAUSTIC_SPA = 0
 EFD_CAUSTIC_UNIFORM = 1
 EFD_LOGLIKE_SCRATCH = 1024
 EFD_INNER_SCRATCH = 2048
+EFD_FISHER_MAX_PARAMS = 16
+EFD_FISHER_SCRATCH = 139264   # efd_fisher_gram's scratch doubles (1024 workgroups x 136 pairs)
 EFD_BATCH_MAX = 16
 EFD_HANN_ROWS_MAX = 16   # efd_hann_loglike's rows per call (include/emrifd.h)
 EFD_HANN_LOCAL_PARTIALS = 4096   # efd_hann_loglike_local's scratch doubles per row
@@ -64,12 +66,14 @@ EXPORTED_SYMBOLS = (
     "efd_cosw_loglike",
     "efd_loglike",
     "efd_inner_product",
+    "efd_fisher_gram",
     "efd_modesum_cpu",
     "efd_modesum_cpu_stats",
     "efd_spline_build_cpu",
     "efd_polarizations_cpu",
     "efd_loglike_cpu",
     "efd_inner_product_cpu",
+    "efd_fisher_gram_cpu",
     "efd_cpu_threads",
     "efd_cpu_last_error",
     "efd_host_trajectory",
@@ -268,6 +272,8 @@ def load(path=None):
     lib.efd_loglike.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
     lib.efd_inner_product.restype = ctypes.c_int
     lib.efd_inner_product.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
+    lib.efd_fisher_gram.restype = ctypes.c_int
+    lib.efd_fisher_gram.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp]
     if hasattr(lib, "efd_modesum_cpu"):   # the host twins (csrc/emrifd_cpu.cpp)
         lib.efd_modesum_cpu.restype = ctypes.c_int
         lib.efd_modesum_cpu.argtypes = [ctypes.POINTER(ModesumArgs), vp, sz, vp]
@@ -282,6 +288,8 @@ def load(path=None):
         lib.efd_loglike_cpu.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
         lib.efd_inner_product_cpu.restype = ctypes.c_int
         lib.efd_inner_product_cpu.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
+        lib.efd_fisher_gram_cpu.restype = ctypes.c_int
+        lib.efd_fisher_gram_cpu.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp]
         lib.efd_cpu_threads.restype = ctypes.c_int
         lib.efd_cpu_threads.argtypes = [ctypes.c_int]
         lib.efd_cpu_last_error.restype = ctypes.c_int

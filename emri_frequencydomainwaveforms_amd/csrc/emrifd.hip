@@ -5654,6 +5654,184 @@ __global__ void k_inner_final(const double2* __restrict__ part, int np, double s
     if (threadIdx.x == 0) out[0] = make_double2(scale * rre[0], scale * rim[0]);
 }
 
+// ---- weighted Gram matrix of stencil-combined rows (efd_fisher_gram) ----------------------
+// One pass over h and w. A workgroup of 4 waves stages FG_CHUNK elements at a time: thread t
+// forms D_i[e] = sum_s coef[i][s] h[i npoint + s][e] for its element (the stencil is applied per
+// element, before any product: the Gram matrix of the raw rows combined afterwards loses the
+// digits the differences cancel) and writes D_i and w to LDS, and D_i to dh. Then each wave
+// takes 4 x 4 tiles (i, j) of the upper triangle's tile grid, its lanes run over the chunk's
+// elements (lane l: l, l + 64, l + 128, l + 192; consecutive 16-byte LDS slots per read) and
+// keep the tile's 16 sums in registers across the workgroup's chunks.
+// What makes gram[i][j] a function of rows i, j, w and nelem alone (the subset promise):
+//   - chunk c goes to workgroup c mod gridDim.x, and gridDim.x is a function of nelem;
+//   - every pair sees the same element -> lane map, the same butterfly over the lanes and the
+//     same final order over the workgroups, whichever wave and tile hold it;
+//   - a term is fma(w, fma(ar, br, ai * bi), acc): symmetric in (a, b), so (j, i) of a
+//     reordered call rounds as (i, j) does; contraction is off, the fmas are the written ones.
+constexpr int FG_THREADS = 256;
+constexpr int FG_CHUNK = 256;
+constexpr int FG_MAXB = 1024;   // workgroups (4 per CU); EFD_FISHER_SCRATCH = FG_MAXB * 136
+
+struct fg_coef {
+    double c[EFD_FISHER_MAX_PARAMS * 4];
+};
+
+__host__ __device__ inline int fg_pair_index(int i, int j, int P) {   // i <= j, row-major upper
+    return i * P - (i * (i - 1)) / 2 + (j - i);
+}
+
+// TP: tile rows = ceil(nparam / 4); the upper triangle has TP (TP + 1) / 2 tiles, wave v takes
+// tiles v, v + 4, v + 8
+template <int NPOINT, int TP>
+__global__ __launch_bounds__(FG_THREADS) void k_fisher_partial(
+    const double2* __restrict__ h, int64_t row_stride, int nparam, fg_coef cf,
+    const double* __restrict__ w, int64_t nelem, double2* __restrict__ dh,
+    double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int NTILE = TP * (TP + 1) / 2;
+    constexpr int MAXT = (NTILE + 3) / 4;
+    __shared__ double2 D[4 * TP * FG_CHUNK];
+    __shared__ double wl[FG_CHUNK];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // rows nparam .. 4 TP - 1 pad the last tile row: zero, written once
+    for (int r = nparam; r < 4 * TP; ++r) D[r * FG_CHUNK + tid] = make_double2(0.0, 0.0);
+    int ti[MAXT], tj[MAXT];
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k) {
+        int t = wv + 4 * k, I = 0;
+        while (I < TP - 1 && t >= TP - I) {   // tile row I holds TP - I tiles (J = I .. TP-1)
+            t -= TP - I;
+            ++I;
+        }
+        ti[k] = I;
+        tj[k] = I + t;   // >= TP: this wave has no k-th tile
+    }
+    double acc[MAXT][16];
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k)
+#pragma unroll
+        for (int p = 0; p < 16; ++p) acc[k][p] = 0.0;
+
+    const int64_t nchunk = (nelem + FG_CHUNK - 1) / FG_CHUNK;
+    for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
+        const int64_t e = c * FG_CHUNK + tid;
+        const bool live = e < nelem;
+        wl[tid] = live ? (w ? w[e] : 1.0) : 0.0;
+        for (int i = 0; i < nparam; ++i) {
+            double dr = 0.0, di = 0.0;
+            if (live) {
+                const double2* r = h + row_stride * ((int64_t)i * NPOINT) + e;
+                double2 v[NPOINT];
+#pragma unroll
+                for (int s = 0; s < NPOINT; ++s) v[s] = r[row_stride * s];
+                const double c0 = cf.c[i * NPOINT];
+                dr = c0 * v[0].x;
+                di = c0 * v[0].y;
+#pragma unroll
+                for (int s = 1; s < NPOINT; ++s) {
+                    const double cs = cf.c[i * NPOINT + s];
+                    dr = fma(cs, v[s].x, dr);
+                    di = fma(cs, v[s].y, di);
+                }
+                if (dh) dh[(int64_t)i * nelem + e] = make_double2(dr, di);
+            }
+            D[i * FG_CHUNK + tid] = make_double2(dr, di);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MAXT; ++k) {
+            if (tj[k] >= TP) continue;
+            const double2* A = D + 4 * ti[k] * FG_CHUNK;
+            const double2* B = D + 4 * tj[k] * FG_CHUNK;
+#pragma unroll
+            for (int q = 0; q < FG_CHUNK / 64; ++q) {
+                const int x = lane + 64 * q;
+                const double ww = wl[x];
+                double2 a[4], b[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    a[r] = A[r * FG_CHUNK + x];
+                    b[r] = B[r * FG_CHUNK + x];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        acc[k][4 * r + s] = fma(ww, fma(a[r].x, b[s].x, a[r].y * b[s].y),
+                                                acc[k][4 * r + s]);
+            }
+        }
+        __syncthreads();
+    }
+    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
+    const int npair = nparam * (nparam + 1) / 2;
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k) {
+        if (tj[k] >= TP) continue;
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+            double v = acc[k][p];
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+            const int gi = 4 * ti[k] + (p >> 2), gj = 4 * tj[k] + (p & 3);
+            if (lane == 0 && gi <= gj && gj < nparam)
+                part[(int64_t)blockIdx.x * npair + fg_pair_index(gi, gj, nparam)] = v;
+        }
+    }
+}
+
+// one workgroup per pair: the workgroups' partials in a fixed order, mirrored into both halves
+__global__ void k_fisher_final(const double* __restrict__ part, int nb, int nparam,
+                               double* __restrict__ gram) {
+    __shared__ double red[256];
+    const int npair = nparam * (nparam + 1) / 2;
+    const int p = blockIdx.x;
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[(int64_t)b * npair + p];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        int i = 0, q = p;
+        while (q >= nparam - i) {
+            q -= nparam - i;
+            ++i;
+        }
+        const int j = i + q;
+        const double g = 4.0 * red[0];
+        gram[i * nparam + j] = g;
+        gram[j * nparam + i] = g;
+    }
+}
+
+template <int NPOINT>
+void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_stride, int nparam,
+               const fg_coef& cf, const double* w, int64_t nelem, double2* dh, double* part) {
+    switch (tp) {
+        case 1:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 1>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        case 2:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 2>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        case 3:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 3>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        default:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 4>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+    }
+}
+
 }  // namespace
 
 // ========================================================================================
@@ -6807,6 +6985,48 @@ int efd_inner_product(const double* a, const double* b, const double* w, int32_t
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_inner_final, dim3(1), dim3(256), 0, st, (const double2*)scratch, np,
                        4.0, (double2*)out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+static_assert(EFD_FISHER_SCRATCH == FG_MAXB * (EFD_FISHER_MAX_PARAMS * (EFD_FISHER_MAX_PARAMS + 1) / 2),
+              "EFD_FISHER_SCRATCH holds every workgroup's upper triangle");
+
+int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
+                    const double* coef, const double* w, int64_t nelem, double* dh, double* gram,
+                    double* scratch, void* stream) {
+    if (nparam < 1 || nparam > EFD_FISHER_MAX_PARAMS)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: nparam outside 1..16");
+    if (npoint != 1 && npoint != 2 && npoint != 4)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: npoint must be 1, 2 or 4");
+    if (!h || !coef || !gram || !scratch)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: NULL h, coef, gram or scratch");
+    if (nelem <= 0) return fail(EFD_ERR_ARG, "efd_fisher_gram: nelem <= 0");
+    if (row_stride < nelem) return fail(EFD_ERR_ARG, "efd_fisher_gram: row_stride < nelem");
+    fg_coef cf;
+    for (int i = 0; i < EFD_FISHER_MAX_PARAMS * 4; ++i)
+        cf.c[i] = i < nparam * npoint ? coef[i] : 0.0;
+    // the partition is a function of nelem alone
+    const int nb = (int)std::min<int64_t>(FG_MAXB, (nelem + FG_CHUNK - 1) / FG_CHUNK);
+    const int tp = (nparam + 3) / 4;
+    hipStream_t st = (hipStream_t)stream;
+    switch (npoint) {
+        case 1:
+            fg_launch<1>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+        case 2:
+            fg_launch<2>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+        default:
+            fg_launch<4>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fisher_final, dim3((unsigned)(nparam * (nparam + 1) / 2)), dim3(256), 0,
+                       st, scratch, nb, nparam, gram);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

@@ -925,4 +925,65 @@ int efd_inner_product_cpu(const double* a, const double* b, const double* w, int
     return EFD_OK;
 }
 
+// efd_fisher_gram's arithmetic: the stencil per element first (ascending s), then the symmetric
+// term w (ar br + ai bi) of every pair i <= j. Fixed chunks of 4096 elements, their partial
+// triangles added in chunk order: the result does not depend on the thread count.
+int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
+                        const double* coef, const double* w, int64_t nelem, double* dh,
+                        double* gram, double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (nparam < 1 || nparam > EFD_FISHER_MAX_PARAMS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_fisher_gram_cpu: nparam outside 1..16");
+    if (npoint != 1 && npoint != 2 && npoint != 4)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_fisher_gram_cpu: npoint must be 1, 2 or 4");
+    if (!h || !coef || !gram)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_fisher_gram_cpu: NULL h, coef or gram");
+    if (nelem <= 0) return efdcpu::fail(EFD_ERR_ARG, "efd_fisher_gram_cpu: nelem <= 0");
+    if (row_stride < nelem)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_fisher_gram_cpu: row_stride < nelem");
+    const int P = nparam;
+    const int npair = P * (P + 1) / 2;
+    const int64_t chunk = 4096;
+    const int64_t nchunk = (nelem + chunk - 1) / chunk;
+    std::vector<double> part((size_t)nchunk * npair, 0.0);
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+    for (int64_t c = 0; c < nchunk; ++c) {
+        double* acc = part.data() + (size_t)c * npair;
+        const int64_t e1 = std::min(nelem, (c + 1) * chunk);
+        double dr[EFD_FISHER_MAX_PARAMS], di[EFD_FISHER_MAX_PARAMS];
+        for (int64_t e = c * chunk; e < e1; ++e) {
+            for (int i = 0; i < P; ++i) {
+                const double* r = h + 2 * (row_stride * ((int64_t)i * npoint) + e);
+                const double* cf = coef + (size_t)i * npoint;
+                double xr = cf[0] * r[0], xi = cf[0] * r[1];
+                for (int s = 1; s < npoint; ++s) {
+                    xr = std::fma(cf[s], r[2 * row_stride * s], xr);
+                    xi = std::fma(cf[s], r[2 * row_stride * s + 1], xi);
+                }
+                dr[i] = xr;
+                di[i] = xi;
+                if (dh) {
+                    dh[2 * ((int64_t)i * nelem + e)] = xr;
+                    dh[2 * ((int64_t)i * nelem + e) + 1] = xi;
+                }
+            }
+            const double ww = w ? w[e] : 1.0;
+            int p = 0;
+            for (int i = 0; i < P; ++i)
+                for (int j = i; j < P; ++j, ++p) {
+                    const double q = di[i] * di[j];
+                    acc[p] = std::fma(ww, std::fma(dr[i], dr[j], q), acc[p]);
+                }
+        }
+    }
+    int p = 0;
+    for (int i = 0; i < P; ++i)
+        for (int j = i; j < P; ++j, ++p) {
+            double s = 0.0;
+            for (int64_t c = 0; c < nchunk; ++c) s += part[(size_t)c * npair + p];
+            gram[i * P + j] = gram[j * P + i] = 4.0 * s;
+        }
+    return EFD_OK;
+}
+
 }  // extern "C"

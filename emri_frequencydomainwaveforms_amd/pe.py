@@ -48,8 +48,12 @@ class PESetup:
 
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
-          window=None):
-    """window_flag: the templates and the injection convolved with a Hann window of the grid's
+          window=None, start_cov=None):
+    """start_cov: a 6 x 6 covariance of the sampled coordinates for the walker start (e.g.
+    fisher_covariance's, which belongs to this source), used in place of the shipped
+    walker_cov.npy (the reference's chain covariance of its own source) before the same
+    / (2.4 ndim) scaling; None keeps the shipped matrix.
+    window_flag: the templates and the injection convolved with a Hann window of the grid's
     length (emri_pe.py:259-263, -window_flag 1 in test.sh: scipy.signal.windows.hann(N), N the
     TD/FD length, odd_len); not with downsampling (emri_pe.py:330-331).
     window: the same with another of scipy's symmetric cosine-sum windows, by name ("hann",
@@ -64,6 +68,8 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     from .likelihood import Likelihood
     from .trajectory import EMRIInspiral, get_p_at_t
     from .waveform import GenerateEMRIWaveform
+    if start_cov is not None and np.shape(start_cov) != (6, 6):
+        raise ValueError(f"start_cov must be 6 x 6, got {np.shape(start_cov)}")
 
     a, x0, Phi_theta0 = 0.1, 1.0, 0.0           # a, x0 ignored for Schwarzschild (:598, :602)
     qK = phiK = qS = phiS = np.pi / 3
@@ -120,7 +126,10 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     data = gen(*injection, **kw)
     like.inject_signal(data_stream=data, noise_fn=[get_sensitivity, get_sensitivity],
                        noise_kwargs=[{}, {}])
-    cov = np.load(_COV, allow_pickle=False) / (2.4 * 6)
+    if start_cov is None:
+        cov = np.load(_COV, allow_pickle=False) / (2.4 * 6)
+    else:
+        cov = np.asarray(start_cov, dtype=np.float64) / (2.4 * 6)
     rng = np.random.default_rng(seed)
     start = rng.multivariate_normal(truth6, cov, size=nwalkers * ntemps)
     if freeze_gc:
@@ -130,6 +139,62 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     return PESetup(few=few, gen=gen, like=like, transform=tc, truth14=injection,
                    truth6=truth6, start=start, kwargs=kw, f_like=f_like,
                    half_step=max(1, nwalkers * ntemps // 2), info=info)
+
+
+class _SampledToWaveform:
+    """fisher()'s parameter_transforms for a PESetup: a sampled 6-vector to FEW's 14."""
+
+    def __init__(self, tc):
+        self.tc = tc
+
+    def transform_base_parameters(self, params):
+        return self.tc.both_transforms(np.asarray(params, dtype=np.float64)[None, :])[0]
+
+
+def fisher_covariance(s, eps, accuracy=True, waveform_model=None, return_derivs=False):
+    """Fisher matrix and covariance of a PESetup's source in its six sampled coordinates at
+    s.truth6, on the likelihood's grid and noise (s.f_like, the drivers' LISA_Alloc_Sh table):
+    (F, cov, info). eps: the six steps (or one float). The stencil points go through
+    s.transform.both_transforms to the generator's 14 parameters; waveform_model defaults to
+    s.gen, whose rows come from one batched call (diagnostic.fisher_rows).
+    info["stencil_agreement"] = max |F5 - F3| / sqrt(F5_ii F5_jj) with F3 the three-point matrix
+    from the +-eps rows already in the five-point buffer (a second Gram call, no new
+    waveforms): the step-size sanity number (accuracy=True only). info["derivs"] holds the
+    derivatives (device, [6][2][nbin]) with return_derivs."""
+    from . import diagnostic as dg
+    torch = dg.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model = s.gen if waveform_model is None else waveform_model
+    steps, points, npoint = dg._fisher_points(s.truth6, eps, None, _SampledToWaveform(s.transform),
+                                              accuracy)
+    rows, _ = dg.fisher_rows(model, points, s.kwargs, extra_rows=6 if return_derivs else 0)
+    rows = rows.to(torch.complex128)
+    nchan, nbin = int(rows.shape[1]), int(rows.shape[2])
+    # the likelihood's own grid and per-channel PSD; the bins it drops (f = 0, where its noise
+    # factor is NaN) carry no weight here either
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = torch.stack([dg.fisher_weights(nbin, f_arr=s.like.freqs,
+                                           PSD=np.asarray(p, dtype=np.float64))
+                         for p in s.like.psd])
+    w = torch.where(s.like._w > 0.0, w, torch.zeros_like(w)).contiguous()
+    red = dg._reducer(dev)
+    dh = (torch.empty((6, nchan, nbin), dtype=torch.complex128, device=dev)
+          if return_derivs else None)
+    gram = red.fisher_gram(rows, dg.stencil_coefficients(steps, accuracy), w, npoint, dh=dh)
+    info = {"steps": steps, "npoint": npoint, "weights": w}
+    if accuracy:
+        c3 = np.zeros((6, 4))
+        c3[:, 1:3] = dg.stencil_coefficients(steps, False)
+        both = torch.stack([gram, red.fisher_gram(rows, c3, w, 4)]).cpu().numpy()
+        F, F3 = both[0], both[1]
+        d = np.sqrt(np.diag(F))
+        info["fisher_three_point"] = F3
+        info["stencil_agreement"] = float(np.max(np.abs(F - F3) / np.outer(d, d)))
+    else:
+        F = gram.cpu().numpy()
+    if return_derivs:
+        info["derivs"] = dh
+    return F, dg.covariance(fish=F), info
 
 
 class MemoizedUpstream:

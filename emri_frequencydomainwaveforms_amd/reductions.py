@@ -1,12 +1,16 @@
-"""Device reductions of the likelihood side: thin wrappers of efd_loglike / efd_inner_product.
+"""Device reductions of the likelihood side: thin wrappers of efd_loglike / efd_inner_product /
+efd_fisher_gram.
 
-Both run in libemrifd.so (HIP, gfx950) as fixed-partition two-pass reductions, so results are
+All run in libemrifd.so (HIP, gfx950) as fixed-partition two-pass reductions, so results are
 bitwise reproducible. They read the channels in place: h, d complex128 [nchan][nbin], w float64
 [nchan][nbin] (all contiguous, on one device); the result stays on the device until the caller
-asks for it, so a batch of walkers costs one host synchronisation.
+asks for it, so a batch of walkers costs one host synchronisation. fisher_gram takes the rows of
+a Fisher matrix's stencil points and returns the whole [nparam][nparam] matrix from one pass.
 """
 
 import ctypes
+
+import numpy as _np
 
 from . import _lib
 from .summation import require_gpu
@@ -68,3 +72,52 @@ class Reducer:
                                               self._scr_ip.data_ptr(), self._stream()),
                    "efd_inner_product", self.lib)
         return out
+
+    def fisher_gram(self, rows, coef, w, npoint, dh=None):
+        """gram[i][j] = 4 sum_e w[e] Re(conj(D_i[e]) D_j[e]), D_i = sum_s coef[i][s] rows[i npoint
+        + s], as a float64 [nparam][nparam] device tensor (efd_fisher_gram: one pass, the stencil
+        applied per element before the products; lisatools fisher's reduction,
+        diagnostic.py:353-381).
+
+        rows: complex128 [nparam * npoint][...]: every row's trailing dimensions contiguous
+        (nelem elements), rows a fixed stride apart (a slice of a wider buffer is fine);
+        coef: host [nparam][npoint]; w: float64 with nelem elements on the device, or None
+        (w = 1); dh: None, or a contiguous complex128 [nparam][...] tensor that receives D.
+        """
+        torch = self.torch
+        if npoint not in (1, 2, 4):
+            raise ValueError("npoint must be 1, 2 or 4")
+        coef = _np.ascontiguousarray(coef, dtype=_np.float64)
+        if coef.ndim != 2 or coef.shape[1] != npoint:
+            raise ValueError(f"coef: expected [nparam][{npoint}], got {coef.shape}")
+        nparam = int(coef.shape[0])
+        if not 1 <= nparam <= _lib.EFD_FISHER_MAX_PARAMS:
+            raise ValueError(f"nparam must be in 1..{_lib.EFD_FISHER_MAX_PARAMS}")
+        if (rows.dtype != torch.complex128 or rows.device != self.device or rows.dim() < 2
+                or rows.shape[0] != nparam * npoint or not rows[0].is_contiguous()):
+            raise ValueError(f"rows: expected complex128 [{nparam * npoint}][...] on "
+                             f"{self.device} with contiguous rows")
+        nelem = int(rows[0].numel())
+        stride = int(rows.stride(0)) if rows.shape[0] > 1 else nelem
+        if nelem == 0 or stride < nelem:
+            raise ValueError("rows: empty or overlapping rows")
+        pw = None
+        if w is not None:
+            if w.numel() != nelem:
+                raise ValueError(f"w: expected {nelem} elements, got {w.numel()}")
+            pw = self._check(w, "w", torch.float64, tuple(w.shape))
+        pdh = None
+        if dh is not None:
+            if dh.numel() != nparam * nelem or dh.shape[0] != nparam:
+                raise ValueError(f"dh: expected [{nparam}][...] with {nelem} elements a row")
+            pdh = self._check(dh, "dh", torch.complex128, tuple(dh.shape))
+        scr = getattr(self, "_scr_fg", None)
+        if scr is None:
+            scr = self._scr_fg = torch.empty(_lib.EFD_FISHER_SCRATCH, dtype=torch.float64,
+                                             device=self.device)
+        gram = torch.empty((nparam, nparam), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.efd_fisher_gram(torch.view_as_real(rows).data_ptr(), stride, nparam,
+                                            npoint, coef.ctypes.data, pw, nelem, pdh,
+                                            gram.data_ptr(), scr.data_ptr(), self._stream()),
+                   "efd_fisher_gram", self.lib)
+        return gram

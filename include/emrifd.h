@@ -424,6 +424,33 @@ int efd_inner_product(const double* a, const double* b, const double* w, int32_t
                       int64_t nbin, double* out, double* scratch, void* stream);
 
 /*
+ * Weighted Gram matrix of stencil-combined rows in one pass: the reduction of lisatools' fisher
+ * (diagnostic.py:300-386: dh_dlambda's central differences :263-267, :294, then inner_product of
+ * every pair of derivatives :373-381).
+ *   D_i[e] = sum_s coef[i][s] * h[i npoint + s][e]      (ascending s, per element, in registers)
+ *   gram[i][j] = 4 * sum_e w[e] * Re(conj(D_i[e]) D_j[e])
+ * h: nparam * npoint complex rows of nelem elements (nelem = nchan * nbin flattened, as
+ * efd_inner_product's operands), row r at h + 2 r row_stride doubles, row_stride >= nelem, h
+ * 16-byte aligned; npoint in {1, 2, 4} (npoint = 1, coef = 1: the Gram matrix of the rows as
+ * given); coef: HOST doubles [nparam][npoint]; w: real [nelem] or NULL (w = 1); gram: doubles
+ * [nparam][nparam], full and exactly symmetric; dh: NULL, or complex [nparam][nelem]
+ * (contiguous rows) receiving D_i from the registers that feed the products; scratch:
+ * EFD_FISHER_SCRATCH device doubles. The stencil is applied before the products: the Gram
+ * matrix of the raw rows combined afterwards is the same algebra and loses the digits the
+ * differences cancel. Every element of h and w is read once. No atomics: a fixed partition that
+ * depends on nelem only and a fixed-order final reduction, so results are bitwise reproducible,
+ * and gram[i][j] is bitwise what the same two parameter blocks give in any other call over the
+ * same w and nelem (a subset of the parameters, another order). EFD_ERR_ARG before any launch:
+ * nparam outside 1..EFD_FISHER_MAX_PARAMS, npoint not 1, 2 or 4, NULL h, coef, gram or scratch,
+ * nelem <= 0, row_stride < nelem.
+ */
+#define EFD_FISHER_MAX_PARAMS 16
+#define EFD_FISHER_SCRATCH 139264
+int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
+                    const double* coef, const double* w, int64_t nelem, double* dh, double* gram,
+                    double* scratch, void* stream);
+
+/*
  * CPU twins: the same algorithm on HOST pointers, C++17 + OpenMP
  * (csrc/emrifd_cpu.cpp, linked into libemrifd.so). Signatures are those of the HIP entry points;
  * `stream`, `workspace` and `scratch` are accepted for parity and ignored (pass NULL / 0). The
@@ -445,6 +472,9 @@ int efd_loglike_cpu(const double* h, const double* d, const double* w, int32_t n
                     int64_t nbin, double* out, double* scratch, void* stream);
 int efd_inner_product_cpu(const double* a, const double* b, const double* w, int32_t nchan,
                           int64_t nbin, double* out, double* scratch, void* stream);
+int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
+                        const double* coef, const double* w, int64_t nelem, double* dh,
+                        double* gram, double* scratch, void* stream);
 /* OpenMP threads of the twins (n <= 0: all available); returns the previous setting. */
 int efd_cpu_threads(int n);
 /* Last error message of the calling thread's CPU-twin call. */
