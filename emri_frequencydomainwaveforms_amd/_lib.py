@@ -23,6 +23,7 @@ EFD_FISHER_SCRATCH = 139264   # efd_fisher_gram's scratch doubles (1024 workgrou
 EFD_BATCH_MAX = 16
 EFD_HANN_ROWS_MAX = 16   # efd_hann_loglike's rows per call (include/emrifd.h)
 EFD_HANN_LOCAL_PARTIALS = 4096   # efd_hann_loglike_local's scratch doubles per row
+EFD_TD_SPLIT_SCRATCH = 1024   # efd_td_split_loglike's scratch doubles per row
 
 # every symbol include/emrifd.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -49,6 +50,9 @@ EXPORTED_SYMBOLS = (
     "efd_modesum_env_evaluations",
     "efd_td_workspace_bytes",
     "efd_td_modesum",
+    "efd_td_modesum_windowed",
+    "efd_td_split",
+    "efd_td_split_loglike",
     "efd_upload",
     "efd_download",
     "efd_stream_order",
@@ -74,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "efd_loglike_cpu",
     "efd_inner_product_cpu",
     "efd_fisher_gram_cpu",
+    "efd_td_split_cpu",
+    "efd_td_split_loglike_cpu",
     "efd_cpu_threads",
     "efd_cpu_last_error",
     "efd_host_trajectory",
@@ -234,6 +240,15 @@ def load(path=None):
         lib.efd_td_workspace_bytes.argtypes = [i32, i32]
         lib.efd_td_modesum.restype = ctypes.c_int
         lib.efd_td_modesum.argtypes = [ctypes.POINTER(TdArgs), vp, sz, vp]
+    if hasattr(lib, "efd_td_split_loglike"):   # the TD templates' transform split
+        lib.efd_td_modesum_windowed.restype = ctypes.c_int
+        lib.efd_td_modesum_windowed.argtypes = [ctypes.POINTER(TdArgs), vp, vp, sz, vp]
+        for name in ("efd_td_split", "efd_td_split_cpu"):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = [vp, i64, i64, i32, dbl, vp, vp, i64, vp]
+        for name in ("efd_td_split_loglike", "efd_td_split_loglike_cpu"):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = [vp, i64, i64, i32, dbl, vp, vp, vp, vp, vp]
     if hasattr(lib, "efd_upload"):   # absent only in older experiment builds
         lib.efd_upload.restype = ctypes.c_int
         lib.efd_upload.argtypes = [vp, vp, sz, vp]

@@ -4209,12 +4209,15 @@ __device__ __forceinline__ int knot_interval(const double* __restrict__ t, int n
     return lo;
 }
 
+// WIN: the store epilogue multiplies each sample by window[s] (efd_td_modesum_windowed; the
+// sum above it is the same code in both instantiations)
+template <bool WIN>
 __global__ __launch_bounds__(TD_THREADS) void k_td_modesum(
     const double* __restrict__ t, int nt, const double* __restrict__ coefT,
     const double* __restrict__ coefA, const int32_t* __restrict__ gm,
     const int32_t* __restrict__ gn, int K, const Header* __restrict__ hdr, double dt,
     int64_t ns, int accumulate_out, double* __restrict__ out, double* __restrict__ hp,
-    double* __restrict__ hc) {
+    double* __restrict__ hc, const double* __restrict__ window) {
     const int64_t s_base = (int64_t)blockIdx.x * (TD_THREADS * TD_SPL) + threadIdx.x;
     const double t_end = t[nt - 1];
     const int G = hdr->groups;
@@ -4315,6 +4318,11 @@ __global__ __launch_bounds__(TD_THREADS) void k_td_modesum(
         if (s >= ns) continue;
         // h = h+ - i hx = -H (zero past the trajectory's end: pad_output)
         double vr = valid[i] ? -Hr[i] : 0.0, vi = valid[i] ? -Hi[i] : 0.0;
+        if constexpr (WIN) {
+            const double wv = window[s];
+            vr *= wv;
+            vi *= wv;
+        }
         if (o) {
             double2 v = make_double2(vr, vi);
             if (accumulate_out) { const double2 p = o[s]; v.x += p.x; v.y += p.y; }
@@ -5606,6 +5614,73 @@ __global__ void k_loglike_final(const double* __restrict__ part, int np, double*
     if (threadIdx.x == 0) out[0] = -0.5 * 4.0 * red[0];
 }
 
+// ---- DFT of a TD template h = h+ - i hx into its two channels (efd_td_split*). Z = fft(w h)
+// in natural order; the Hermitian split (k_polarizations' algebra, on the DFT's own pairing
+// k <-> (n - k) mod n) gives both real series' transforms over the bins k < nb = ceil(n / 2),
+// which are the drivers' positive-frequency bins (fftshift, then frequency >= 0):
+//   H+ = (Z[k] + conj Z[n-k]) / 2,  Hx = i (Z[k] - conj Z[n-k]) / 2,  each times gain (= dt).
+__device__ __forceinline__ void td_split_pair(const double2 a, const double2 b, double gain,
+                                              double2& hp, double2& hc) {
+#pragma clang fp contract(off)
+    hp = make_double2(gain * (0.5 * (a.x + b.x)), gain * (0.5 * (a.y - b.y)));
+    hc = make_double2(gain * (-0.5 * (a.y + b.y)), gain * (0.5 * (a.x - b.x)));
+}
+
+__global__ __launch_bounds__(256) void k_td_split(const double2* __restrict__ Z, int64_t stride,
+                                                  int64_t n, int64_t nb, double gain,
+                                                  const uint8_t* __restrict__ keep,
+                                                  double2* __restrict__ out, int64_t out_stride) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nb) return;
+    const double2* z = Z + (int64_t)blockIdx.y * stride;
+    double2* o = out + (int64_t)blockIdx.y * out_stride;
+    double2 hp = make_double2(0.0, 0.0), hc = hp;
+    if (keep == nullptr || keep[k] != 0) td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
+    o[k] = hp;
+    o[nb + k] = hc;
+}
+
+// logL partials of the split's channels against d ([2][nb]) and w ([2][nb]), the template kept
+// in registers: workgroup (c, r) takes bins [c chunk, (c + 1) chunk) of row r, an ascending
+// stream Z[k] and a descending one Z[n - k]; the row is the slow grid dimension, so the rows'
+// workgroups of one chunk follow each other on one XCD and find d and w in its cache. Partials
+// at part[r gridDim.x + c] (k_loglike_final's layout).
+__global__ __launch_bounds__(256) void k_td_split_loglike(
+    const double2* __restrict__ Z, int64_t stride, int64_t n, int64_t nb, int64_t chunk,
+    double gain, const double2* __restrict__ d, const double* __restrict__ w,
+    double* __restrict__ part) {
+    // d - h w rounded as k_loglike_partial does (product, then difference)
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const double2* z = Z + (int64_t)blockIdx.y * stride;
+    const int64_t k0 = (int64_t)blockIdx.x * chunk;
+    const int64_t k1 = min(nb, k0 + chunk);
+    double acc = 0.0;
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += 256) {
+        double2 hp, hc;
+        td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
+        const double2 d0 = d[k], d1 = d[nb + k];
+        const double w0 = w[k], w1 = w[nb + k];
+        const double ar = d0.x - hp.x * w0, ai = d0.y - hp.y * w0;
+        const double br = d1.x - hc.x * w1, bi = d1.y - hc.y * w1;
+        acc = fma(ar, ar, fma(ai, ai, acc));
+        acc = fma(br, br, fma(bi, bi, acc));
+    }
+    // even n: the Nyquist bin belongs to neither channel's kept bins; a NaN there still
+    // poisons the row, as one anywhere else does through the terms above
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
+        const double2 v = z[n / 2];
+        if (v.x != v.x || v.y != v.y) acc = v.x + v.y;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
 // noise-weighted inner product partials: sum conj(a) b w (complex), one pair per workgroup
 __global__ void k_inner_partial(const double2* __restrict__ a, const double2* __restrict__ b,
                                 const double* __restrict__ w, int64_t total,
@@ -6564,7 +6639,8 @@ size_t efd_td_workspace_bytes(int32_t nt, int32_t K) {
     return make_td_layout(nt, K).total;
 }
 
-int efd_td_modesum(const efd_td_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+static int td_modesum_run(const efd_td_args* a, const double* window, void* workspace,
+                         size_t workspace_bytes, void* stream) {
     if (!a || !workspace) return fail(EFD_ERR_ARG, "efd_td_modesum: NULL argument");
     if (!a->t || !a->phi_phi || !a->phi_r || !a->f_phi || !a->f_r || !a->amp || !a->m ||
         !a->n || !a->ylm_p || !a->ylm_m)
@@ -6612,11 +6688,75 @@ int efd_td_modesum(const efd_td_args* a, void* workspace, size_t workspace_bytes
     const int64_t nblk = (a->nsamples + per_block - 1) / per_block;
     if (nblk > 0x7fffffffLL) return fail(EFD_ERR_ARG, "efd_td_modesum: too many samples");
     if (a->prof_begin) HIP_TRY(hipEventRecord((hipEvent_t)a->prof_begin, st));
-    hipLaunchKernelGGL(k_td_modesum, dim3((unsigned)nblk), dim3(TD_THREADS), 0, st, a->t, nt,
-                       coefT, coefA, gm, gn, K, hdr, a->dt, a->nsamples, a->accumulate ? 1 : 0,
-                       a->out, a->hp, a->hc);
+    if (window)
+        hipLaunchKernelGGL(k_td_modesum<true>, dim3((unsigned)nblk), dim3(TD_THREADS), 0, st, a->t,
+                           nt, coefT, coefA, gm, gn, K, hdr, a->dt, a->nsamples,
+                           a->accumulate ? 1 : 0, a->out, a->hp, a->hc, window);
+    else
+        hipLaunchKernelGGL(k_td_modesum<false>, dim3((unsigned)nblk), dim3(TD_THREADS), 0, st,
+                           a->t, nt, coefT, coefA, gm, gn, K, hdr, a->dt, a->nsamples,
+                           a->accumulate ? 1 : 0, a->out, a->hp, a->hc, (const double*)nullptr);
     HIP_TRY(hipGetLastError());
     if (a->prof_end) HIP_TRY(hipEventRecord((hipEvent_t)a->prof_end, st));
+    return EFD_OK;
+}
+
+int efd_td_modesum(const efd_td_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+    return td_modesum_run(a, nullptr, workspace, workspace_bytes, stream);
+}
+
+int efd_td_modesum_windowed(const efd_td_args* a, const double* window, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return td_modesum_run(a, window, workspace, workspace_bytes, stream);
+}
+
+// the chunks of efd_td_split_loglike for n points: a function of n alone (whole rounds of the
+// 8 XCDs once there are that many), each a multiple of 256 bins
+static int td_split_chunks(int64_t nb, int64_t* chunk) {
+    int64_t np = std::min<int64_t>(EFD_TD_SPLIT_SCRATCH, (nb + 1023) / 1024);
+    if (np > 8) np -= np % 8;
+    int64_t c = (nb + np - 1) / np;
+    c = (c + 255) / 256 * 256;
+    *chunk = c;
+    return (int)((nb + c - 1) / c);
+}
+
+int efd_td_split(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                 const uint8_t* keep, double* out, int64_t out_stride, void* stream) {
+    if (!Z || !out) return fail(EFD_ERR_ARG, "efd_td_split: NULL Z or out");
+    if (n < 1 || n > ((int64_t)1 << 40)) return fail(EFD_ERR_ARG, "efd_td_split: n out of range");
+    if (rows < 1) return fail(EFD_ERR_ARG, "efd_td_split: rows < 1");
+    const int64_t nb = (n + 1) / 2;
+    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split: stride < n");
+    if (out_stride < 2 * nb) return fail(EFD_ERR_ARG, "efd_td_split: out_stride < 2 nb");
+    const int64_t blocks = (nb + 255) / 256;
+    if (blocks > 0x7fffffffLL || rows > 65535)
+        return fail(EFD_ERR_ARG, "efd_td_split: too many bins or rows");
+    hipLaunchKernelGGL(k_td_split, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0,
+                       (hipStream_t)stream, (const double2*)Z, stride, n, nb, gain, keep,
+                       (double2*)out, out_stride);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                         const double* d, const double* w, double* out, double* scratch,
+                         void* stream) {
+    if (!Z || !d || !w || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_td_split_loglike: NULL Z, d, w, out or scratch");
+    if (n < 1 || n > ((int64_t)1 << 40))
+        return fail(EFD_ERR_ARG, "efd_td_split_loglike: n out of range");
+    if (rows < 1 || rows > 65535) return fail(EFD_ERR_ARG, "efd_td_split_loglike: rows out of range");
+    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split_loglike: stride < n");
+    const int64_t nb = (n + 1) / 2;
+    int64_t chunk = 0;
+    const int np = td_split_chunks(nb, &chunk);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_td_split_loglike, dim3((unsigned)np, (unsigned)rows), dim3(256), 0, st,
+                       (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)d, w, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
+    HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
 

@@ -986,4 +986,76 @@ int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int
     return EFD_OK;
 }
 
+// efd_td_split's arithmetic (the translation unit is built with contraction off)
+static inline void td_split_pair(const double* z, int64_t n, int64_t k, double gain, double* hp,
+                                 double* hc) {
+    const int64_t j = k == 0 ? 0 : n - k;
+    const double ar = z[2 * k], ai = z[2 * k + 1], br = z[2 * j], bi = z[2 * j + 1];
+    hp[0] = gain * (0.5 * (ar + br)); hp[1] = gain * (0.5 * (ai - bi));
+    hc[0] = gain * (-0.5 * (ai + bi)); hc[1] = gain * (0.5 * (ar - br));
+}
+
+int efd_td_split_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                     const uint8_t* keep, double* out, int64_t out_stride, void* stream) {
+    (void)stream;
+    const int64_t nb = (n + 1) / 2;
+    if (!Z || !out) return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_cpu: NULL Z or out");
+    if (n < 1 || rows < 1 || stride < n || out_stride < 2 * nb)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_cpu: n, rows, stride or out_stride");
+    for (int32_t r = 0; r < rows; ++r) {
+        const double* z = Z + 2 * (int64_t)r * stride;
+        double* o = out + 2 * (int64_t)r * out_stride;
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+        for (int64_t k = 0; k < nb; ++k) {
+            double hp[2] = {0.0, 0.0}, hc[2] = {0.0, 0.0};
+            if (!keep || keep[k]) td_split_pair(z, n, k, gain, hp, hc);
+            o[2 * k] = hp[0]; o[2 * k + 1] = hp[1];
+            o[2 * (nb + k)] = hc[0]; o[2 * (nb + k) + 1] = hc[1];
+        }
+    }
+    return EFD_OK;
+}
+
+// fixed chunks of 4096 bins, their partials added in chunk order (no dependence on threads)
+int efd_td_split_loglike_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
+                             double gain, const double* d, const double* w, double* out,
+                             double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (!Z || !d || !w || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_loglike_cpu: NULL Z, d, w or out");
+    if (n < 1 || rows < 1 || stride < n)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_loglike_cpu: n, rows or stride");
+    const int64_t nb = (n + 1) / 2;
+    const int64_t chunk = 4096;
+    const int64_t nchunk = (nb + chunk - 1) / chunk;
+    std::vector<double> part((size_t)nchunk);
+    for (int32_t r = 0; r < rows; ++r) {
+        const double* z = Z + 2 * (int64_t)r * stride;
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+        for (int64_t c = 0; c < nchunk; ++c) {
+            const int64_t k1 = std::min(nb, (c + 1) * chunk);
+            double acc = 0.0;
+            for (int64_t k = c * chunk; k < k1; ++k) {
+                double hp[2], hc[2];
+                td_split_pair(z, n, k, gain, hp, hc);
+                const double w0 = w[k], w1 = w[nb + k];
+                const double ar = d[2 * k] - hp[0] * w0, ai = d[2 * k + 1] - hp[1] * w0;
+                const double br = d[2 * (nb + k)] - hc[0] * w1;
+                const double bi = d[2 * (nb + k) + 1] - hc[1] * w1;
+                acc += ar * ar + ai * ai;
+                acc += br * br + bi * bi;
+            }
+            part[(size_t)c] = acc;
+        }
+        double s = 0.0;
+        for (int64_t c = 0; c < nchunk; ++c) s += part[(size_t)c];
+        if ((n & 1) == 0) {   // the Nyquist bin: in no channel, but a NaN there counts
+            const double vr = z[n], vi = z[n + 1];
+            if (vr != vr || vi != vi) s = vr + vi;
+        }
+        out[r] = -0.5 * 4.0 * s;
+    }
+    return EFD_OK;
+}
+
 }  // extern "C"

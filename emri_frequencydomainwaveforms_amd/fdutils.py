@@ -27,7 +27,14 @@ Likelihood uses that.
 
 get_fd_waveform_fromTD is the reference's comparison template: the TD generator's [h+, hx]
 (efd_td_modesum on the device), times the window, through rocFFT (torch.fft), shifted and scaled
-by dt, then masked like the FD template.
+by dt, then masked like the FD template. That is its __call__, kept as it is. For the
+likelihood's walker batches it also has the FD template's fill / fill_batch / loglike_batch
+members when the generator is this package's TD GenerateEMRIWaveform and the mask is the drivers'
+(frequency >= 0 on the shifted grid = the natural-order bins k < ceil(N / 2)): the TD kernel
+emits h = h+ - i hx as one complex series with the window multiplied in its store epilogue
+(efd_td_modesum_windowed: any real window), ONE complex transform per walker gives both channels
+by the Hermitian split (efd_td_split), and the logL is reduced straight from the transform
+(efd_td_split_loglike) without a shift, a gather or a stored template.
 """
 
 import os
@@ -881,6 +888,30 @@ class get_fd_waveform_fromTD:
                               else torch.as_tensor(non_zero_mask, device=dev))
         # the reference's default window is ones_like(mask) (:165-166): the identity
         self.window = None if window is None else torch.as_tensor(window, device=dev)
+        # the batched route (module docstring): False, or EFD_TD_BATCH=0, keeps __call__'s
+        self.batched = os.environ.get("EFD_TD_BATCH", "1") != "0"
+        pm = self.positive_frequency_mask
+        n = self.num_samples = int(pm.numel())
+        self.num_bins = (n + 1) // 2
+        # the drivers' mask (frequency >= 0 on the shifted grid) keeps the natural-order bins
+        # k < ceil(n / 2): the shifted positions n // 2 .. n - 1
+        self._mask_ok = bool(pm.dim() == 1 and pm.dtype == torch.bool and n >= 1 and torch.equal(
+            pm, torch.arange(n, device=dev) >= n // 2))
+        w = self.window
+        self._win64 = None
+        self._win_ok = w is None
+        if (w is not None and w.dim() == 1 and int(w.numel()) == n and not torch.is_complex(w)):
+            self._win64 = w.to(torch.float64).contiguous()
+            self._win_ok = True
+        nz = self.non_zero_mask
+        self._keep = None
+        if nz is not None and nz.dim() == 1 and int(nz.numel()) == self.num_bins:
+            self._keep = nz.to(torch.uint8).contiguous()
+        elif nz is not None:
+            self._mask_ok = False
+        self._zbuf = None
+        self._plans = {}
+        self.info = {}
 
     def __call__(self, *args, **kwargs):
         chans = self.waveform_generator(*args, **kwargs)
@@ -891,3 +922,184 @@ class get_fd_waveform_fromTD:
             ch1[~self.non_zero_mask] = 0.0
             ch2[~self.non_zero_mask] = 0.0
         return [ch1, ch2]
+
+    # -- the batched route: one complex transform per walker, split on the device ---------------
+    # walkers per group: their windowed series share one [rows][N] buffer and one batched
+    # transform (fewer when rows * 16 N bytes and the plan's work area would not fit)
+    WINDOW_GROUP = 8
+    KEEP_PLANS = 2   # hipFFT plans kept: a full group's and a ragged last group's
+
+    @property
+    def can_fill(self):
+        gen = self.waveform_generator
+        inner = getattr(gen, "waveform_generator", None)
+        return bool(self.batched and self._mask_ok and self._win_ok
+                    and hasattr(gen, "time_series_batch")
+                    and getattr(inner, "output_type", None) == "td"
+                    and getattr(inner, "use_gpu", False)
+                    and getattr(getattr(inner, "create_waveform", None), "pad_output", False))
+
+    can_fill_batch = can_fill
+
+    @property
+    def PREFETCH_ASYNC(self):
+        return self.can_fill and bool(getattr(self.waveform_generator, "PREFETCH_ASYNC", False))
+
+    def prefetch(self, params, *args, **kwargs):
+        """The host upstream of a walker batch on the generator's pool (wait=False: without
+        waiting); a no-op off the batched route."""
+        kwargs.pop("f_arr", None)
+        if not self.can_fill or args:
+            return 0
+        return self.waveform_generator.prefetch(params, **kwargs)
+
+    def _group(self, B):
+        """Walkers per group for a batch of B."""
+        from . import _lib
+        return self._rows_that_fit(min(B, max(1, int(self.WINDOW_GROUP)), _lib.EFD_BATCH_MAX))
+
+    def _rows_that_fit(self, rows):
+        """At most `rows`, halved while the series buffer (rows * 16 N bytes) and the plan's work
+        area would not fit in the device's free memory. The work area is known only once the
+        plan exists; hipFFT's for the drivers' odd (Bluestein) lengths measured 101 bytes per
+        sample and row (N = 6.3 M and 12.6 M), 6.3 times the buffer: the estimate takes 7.
+        A group size whose plan is already held fits as it is (its work area is part of what
+        is in use)."""
+        torch = require_gpu()
+        dev = self.positive_frequency_mask.device
+        n = self.num_samples
+        free = torch.cuda.mem_get_info(dev)[0] + (torch.cuda.memory_reserved(dev)
+                                                  - torch.cuda.memory_allocated(dev))
+        if self._zbuf is not None:
+            free += self._zbuf.numel() * 16
+        while rows > 1 and (n, rows) not in self._plans and rows * 16 * n * 8 > free:
+            rows = (rows + 1) // 2
+        return rows
+
+    def _transform(self, Z):
+        """fft along the rows of Z ([rows][N] complex128, contiguous), in place: a hipFFT
+        double-precision plan per (N, rows), or torch.fft where the plan cannot be made."""
+        from . import _hipfft
+        torch = require_gpu()
+        rows, n = int(Z.shape[0]), int(Z.shape[1])
+        key = (n, rows)
+        if key not in self._plans:
+            while len(self._plans) >= self.KEEP_PLANS:
+                old = self._plans.pop(next(iter(self._plans)))
+                if old is not None:
+                    old.destroy()
+            try:
+                self._plans[key] = _hipfft.Z2ZPlan(n, rows)
+            except (RuntimeError, OSError, AttributeError):
+                self._plans[key] = None
+        plan = self._plans[key]
+        if plan is None:
+            Z.copy_(torch.fft.fft(Z, dim=-1))
+            self.info.update(transform="torch.fft", rows=rows, n=n, plan_work_bytes=None)
+            return Z
+        plan(torch.view_as_real(Z).data_ptr(), _hipfft.FORWARD,
+             torch.cuda.current_stream(Z.device).cuda_stream)
+        self.info.update(transform="hipfft", rows=rows, n=n, plan_work_bytes=plan.work_bytes())
+        return Z
+
+    def _spectra(self, params, kwargs):
+        """Z = fft(window * h) of every row of params in the rows of one reused buffer;
+        the generator's device-side status is still unread (check_td_batch)."""
+        torch = require_gpu()
+        if not self.can_fill:
+            raise ValueError("the batched route needs this package's TD GenerateEMRIWaveform on "
+                             "the GPU, the leading positive-frequency mask and a real window of "
+                             "the grid's length (or batched = False)")
+        kw = dict(kwargs)
+        kw.pop("f_arr", None)
+        gen = self.waveform_generator
+        n = self.num_samples
+        if gen.td_samples(kw.get("T", 1.0), kw.get("dt", 10.0)) != n:
+            raise ValueError("positive_frequency_mask does not match the generator's grid")
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
+        B = len(params)
+        if self._zbuf is None or self._zbuf.shape[0] < B:
+            self._zbuf = None
+            self._zbuf = torch.empty((B, n), dtype=torch.complex128,
+                                     device=self.positive_frequency_mask.device)
+        Z = self._zbuf[:B]
+        gen.time_series_batch(params, Z, window=self._win64, check=False, **kw)
+        return self._transform(Z)
+
+    def _split(self, Z, out):
+        """efd_td_split of the rows of Z into out (complex128 [rows][2][num_bins] or
+        [2][num_bins], contiguous)."""
+        from . import _lib
+        torch = require_gpu()
+        rows, nb = int(Z.shape[0]), self.num_bins
+        if (out.dtype != torch.complex128 or not out.is_contiguous() or out.device != Z.device
+                or tuple(out.shape) not in ((rows, 2, nb), (2, nb)) or out.numel() != rows * 2 * nb):
+            raise ValueError(f"out: contiguous complex128 [{rows}][2][{nb}] on {Z.device}")
+        lib = _lib.load()
+        _lib.check(lib.efd_td_split(
+            torch.view_as_real(Z).data_ptr(), int(Z.stride(0)), self.num_samples, rows,
+            float(self.dt), None if self._keep is None else self._keep.data_ptr(),
+            torch.view_as_real(out).data_ptr(), 2 * nb,
+            torch.cuda.current_stream(Z.device).cuda_stream), "efd_td_split", lib)
+
+    def fill(self, out, *params, **kwargs):
+        """[ch1, ch2] into out (complex128 [2][num_bins], device): one windowed TD sum, one
+        complex transform and efd_td_split (bins outside non_zero_mask are exact zeros)."""
+        self._split(self._spectra(np.asarray(params[:14], dtype=np.float64)[None, :], kwargs), out)
+        self.waveform_generator.check_td_batch()
+        return out
+
+    def fill_batch(self, outs, params, **kwargs):
+        """fill for every row of params (walkers x 14) into outs[i] (complex128 [2][num_bins]
+        each; or one [B][2][num_bins] tensor): groups of WINDOW_GROUP walkers, their series in
+        one buffer, one batched transform and the split per group. Same values as B __call__s
+        up to the rounding of two FP64 transform routes."""
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
+        B = len(params)
+        if B == 0:
+            return outs
+        whole = hasattr(outs, "detach")
+        G = self._group(B)
+        self.waveform_generator.prefetch(params, wait=False, **{
+            k: v for k, v in kwargs.items() if k != "f_arr"})
+        for g0 in range(0, B, G):
+            Z = self._spectra(params[g0:g0 + G], kwargs)
+            if whole:
+                self._split(Z, outs[g0:g0 + len(Z)])
+            else:
+                for i in range(len(Z)):
+                    self._split(Z[i:i + 1], outs[g0 + i])
+            self.waveform_generator.check_td_batch()
+        return outs
+
+    def loglike_batch(self, out, params, d, w, scratch, local=None, **kwargs):
+        """The templates' log-likelihoods of a batch of walkers into out (float64 device [B])
+        against d, w (efd_loglike's operands, [2][num_bins]; non_zero_mask folded into w by the
+        caller): the windowed series and their transform as in fill_batch, then
+        efd_td_split_loglike straight from Z (no template is written). scratch holds
+        B * EFD_TD_SPLIT_SCRATCH doubles. A walker whose sum reported a device-side error
+        raises EFDError after its group; one whose series holds a NaN comes back NaN."""
+        from . import _lib
+        torch = require_gpu()
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
+        B = len(params)
+        if B == 0:
+            return out
+        nb = self.num_bins
+        if (tuple(d.shape) != (2, nb) or tuple(w.shape) != (2, nb) or not d.is_contiguous()
+                or not w.is_contiguous() or d.dtype != torch.complex128
+                or w.dtype != torch.float64):
+            raise ValueError(f"d complex128 and w float64, contiguous [2][{nb}]")
+        if scratch.numel() < B * _lib.EFD_TD_SPLIT_SCRATCH or out.numel() < B:
+            raise ValueError("loglike_batch: scratch or out too small")
+        lib = _lib.load()
+        G = self._group(B)
+        for g0 in range(0, B, G):
+            Z = self._spectra(params[g0:g0 + G], kwargs)
+            _lib.check(lib.efd_td_split_loglike(
+                torch.view_as_real(Z).data_ptr(), int(Z.stride(0)), self.num_samples, len(Z),
+                float(self.dt), torch.view_as_real(d).data_ptr(), w.data_ptr(),
+                out[g0:g0 + len(Z)].data_ptr(), scratch.data_ptr(),
+                torch.cuda.current_stream(Z.device).cuda_stream), "efd_td_split_loglike", lib)
+            self.waveform_generator.check_td_batch()
+        return out

@@ -21,8 +21,14 @@ the template buffer, and the 2 x N_pos residual d - h w is never materialised. W
 get_fd_waveform_fromFD around a GenerateEMRIWaveform (the drivers' case), h+ and hx are written
 by efd_polarizations directly into one reusable [2][N_pos] buffer (the stream orders reuse), and
 non_zero_mask is folded into the template weight (w * mask) instead of zeroing h.
+The reference's other template mode, get_fd_waveform_fromTD around the TD GenerateEMRIWaveform
+(emri_pe.py -template td), takes the same batched branch: groups of WINDOW_GROUP walkers, each
+walker's windowed series h+ - i hx written by efd_td_modesum_windowed into one row of a shared
+buffer, one batched complex transform, and efd_td_split_loglike reducing both channels' logL
+straight from it (any window; non_zero_mask folded into w as above).
 Results are numpy float64 arrays ([B]), or device tensors with use_gpu=True, return_cupy=True.
-Time-domain templates (dt only) are not part of this path: get_ll raises NotImplementedError.
+Likelihoods over time-domain DATA (dt only, no df or f_arr) are not part of this path: get_ll
+raises NotImplementedError.
 """
 
 import ctypes
@@ -192,7 +198,8 @@ class Likelihood:
     def get_ll(self, params, *args, **kwargs):
         torch = self.torch
         if self.frequency_domain is False:
-            raise NotImplementedError("time-domain templates are not part of the FD path")
+            raise NotImplementedError("a dt-only (time-domain data) likelihood is not part of "
+                                      "the FD path")
         num_likes = params.shape[0]
         out = torch.empty(num_likes, dtype=torch.float64, device=self.device)
         nch, nb = self._d.shape
@@ -228,12 +235,15 @@ class Likelihood:
             # windows: fdutils.COSINE_WINDOWS): groups of WINDOW_GROUP walkers,
             # their spectra in one buffer and the window's transforms batched over them
             # and the windowed templates' logL reduced in place (efd_hann_loglike or
-            # efd_cosw_loglike, at most EFD_HANN_ROWS_MAX rows a call). The batch takes keyword waveform arguments only;
+            # efd_cosw_loglike, at most EFD_HANN_ROWS_MAX rows a call). TD templates
+            # (get_fd_waveform_fromTD) group the same way: one transform per walker and
+            # efd_td_split_loglike. The batch takes keyword waveform arguments only;
             # extra positional ones go to the per-walker fill below, which forwards them
             G = min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
                         or int(getattr(tm, "WINDOW_GROUP", 8))), _lib.EFD_HANN_ROWS_MAX)
             scr = getattr(self, "_wscratch", None)
-            per_row = max(_lib.EFD_LOGLIKE_SCRATCH, _lib.EFD_HANN_LOCAL_PARTIALS)
+            per_row = max(_lib.EFD_LOGLIKE_SCRATCH, _lib.EFD_HANN_LOCAL_PARTIALS,
+                          _lib.EFD_TD_SPLIT_SCRATCH)
             if scr is None or scr.numel() < G * per_row:
                 scr = self._wscratch = torch.empty(G * per_row, dtype=torch.float64,
                                                    device=self.device)

@@ -28,8 +28,8 @@ _COV = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "walker_
 
 @dataclass
 class PESetup:
-    few: object              # GenerateEMRIWaveform(..., return_list=True)
-    gen: object              # get_fd_waveform_fromFD template
+    few: object              # the template's GenerateEMRIWaveform(..., return_list=True)
+    gen: object              # get_fd_waveform_fromFD (or, template="td", _fromTD) template
     like: object             # Likelihood with the "emri" TransformContainer
     transform: object
     truth14: np.ndarray      # injection parameters (14, FEW order)
@@ -48,8 +48,14 @@ class PESetup:
 
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
-          window=None, start_cov=None):
-    """start_cov: a 6 x 6 covariance of the sampled coordinates for the walker start (e.g.
+          window=None, start_cov=None, template="fd", injectFD=None):
+    """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
+    generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
+    not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
+    length (the window is applied in the time domain, so any window will do).
+    injectFD: None injects the template's own model; True / False force the FD / TD model for
+    the data (the driver's -injectFD: its cross-model runs, :308-311).
+    start_cov: a 6 x 6 covariance of the sampled coordinates for the walker start (e.g.
     fisher_covariance's, which belongs to this source), used in place of the shipped
     walker_cov.npy (the reference's chain covariance of its own source) before the same
     / (2.4 ndim) scaling; None keeps the shipped matrix.
@@ -64,7 +70,11 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     sampler process would once its setup is done: a full collection otherwise walks ~200 k
     objects, 35 ms (130 ms with a dropped setup's garbage), inside whichever likelihood call
     happens to trigger it (tools/api_trace.py, tools/gc_cycles.py)."""
-    from .fdutils import get_fd_waveform_fromFD, get_sensitivity
+    if template not in ("fd", "td"):
+        raise ValueError("template: 'fd' or 'td'")
+    if template == "td" and downsample:
+        raise ValueError("Cannot run downsampling with time domain template")   # emri_pe.py:326
+    from .fdutils import get_fd_waveform_fromFD, get_fd_waveform_fromTD, get_sensitivity
     from .likelihood import Likelihood
     from .trajectory import EMRIInspiral, get_p_at_t
     from .waveform import GenerateEMRIWaveform
@@ -98,9 +108,14 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     like_subset = subset
     window_name = window if window is not None else ("hann" if window_flag else None)
     window = None
-    if window_name is not None:
+    if template == "td" and window_name is not None and not isinstance(window_name, str):
+        window = np.asarray(window_name, dtype=np.float64)
+        if window.ndim != 1 or len(window) != len(frequency):
+            raise ValueError(f"window: a name or a 1-D array of {len(frequency)} samples")
+        info["window"] = "array"
+    elif window_name is not None:
         from .fdutils import COSINE_WINDOWS
-        if window_name not in COSINE_WINDOWS:
+        if not isinstance(window_name, str) or window_name not in COSINE_WINDOWS:
             raise ValueError(f"window: one of {sorted(COSINE_WINDOWS)}")
         if downsample:
             raise ValueError("Cannot run downsampling with windowing")   # emri_pe.py:331
@@ -120,10 +135,22 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
         info.update(downsample=downsample, N_f_downsampled=int(len(newfreq)))
     else:
         f_like = frequency[pos]
-    gen = get_fd_waveform_fromFD(few, pos, dt, window=window)
+    inject_fd = template == "fd" if injectFD is None else bool(injectFD)
+    gen = gen_fd = None
+    if template == "fd" or inject_fd:
+        gen = gen_fd = get_fd_waveform_fromFD(few, pos, dt, window=window)
+    if template == "td" or not inject_fd:
+        # the TD generator (td_gen_list, emri_pe.py:95-110) and its DFT template (:262, :266)
+        td = GenerateEMRIWaveform("FastSchwarzschildEccentricFlux",
+                                  sum_kwargs=dict(pad_output=True, odd_len=True), use_gpu=True,
+                                  return_list=True)
+        gen_td = get_fd_waveform_fromTD(td, pos, dt, window=window)
+        if template == "td":
+            gen, few = gen_td, td
+    info.update(template=template, injectFD=bool(inject_fd))
     like = Likelihood(gen, 2, parameter_transforms={"emri": tc}, vectorized=False,
                       transpose_params=False, subset=like_subset, f_arr=f_like, use_gpu=True)
-    data = gen(*injection, **kw)
+    data = (gen_fd if inject_fd else gen_td)(*injection, **kw)
     like.inject_signal(data_stream=data, noise_fn=[get_sensitivity, get_sensitivity],
                        noise_kwargs=[{}, {}])
     if start_cov is None:

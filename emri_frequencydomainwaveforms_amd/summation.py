@@ -1040,9 +1040,11 @@ class TDEngine:
         return self._ws
 
     def launch(self, inp, dt, nsamples, out=None, hp=None, hc=None, scale=1.0 + 0.0j,
-               accumulate=False, stream=None, prof_events=(None, None)):
+               accumulate=False, stream=None, prof_events=(None, None), window=None):
         """Asynchronous launch. out: float64 view of complex [nsamples] (h = h+ - i hx);
-        hp / hc: real float64 [nsamples]; any of them may be None (not all)."""
+        hp / hc: real float64 [nsamples]; any of them may be None (not all). window: float64
+        [nsamples] on the device, multiplied into every stored sample
+        (efd_td_modesum_windowed); None is efd_td_modesum."""
         torch = _torch()
         dev = inp.t.device
         ws = self._workspace(inp.nt, inp.K, dev)
@@ -1056,6 +1058,14 @@ class TDEngine:
             scale_im=float(np.imag(scale)), accumulate=1 if accumulate else 0, out=ptr(out),
             hp=ptr(hp), hc=ptr(hc), prof_begin=prof_events[0], prof_end=prof_events[1])
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        if window is not None:
+            if (window.dtype != torch.float64 or window.dim() != 1 or not window.is_contiguous()
+                    or int(window.numel()) != int(nsamples) or window.device != dev):
+                raise ValueError(f"window: contiguous float64 [{int(nsamples)}] on {dev}")
+            _lib.check(self.lib.efd_td_modesum_windowed(a, window.data_ptr(), ws.data_ptr(),
+                                                        ws.numel(), st),
+                       "efd_td_modesum_windowed", self.lib)
+            return ws
         _lib.check(self.lib.efd_td_modesum(a, ws.data_ptr(), ws.numel(), st), "efd_td_modesum",
                    self.lib)
         return ws

@@ -656,9 +656,10 @@ class GenerateEMRIWaveform:
                  include_minus_m=True, wait=True, concurrency=None, **kwargs):
         """The host upstream of a batch of 14-parameter sets at once (thread pool; see
         FastSchwarzschildEccentricFlux.prefetch); later calls with the same parameters and
-        kwargs take the results. Only for the FD generator without an explicit mode list."""
+        kwargs take the results. Only without an explicit mode list (the FD and the TD
+        generator share the upstream)."""
         gen = self.waveform_generator
-        if gen.output_type != "fd" or mode_selection is not None or not include_minus_m:
+        if mode_selection is not None or not include_minus_m:
             return 0
         calls = []
         # rows as Python floats (one tolist(): unpacking numpy rows costs ~5x more a walker)
@@ -668,6 +669,91 @@ class GenerateEMRIWaveform:
             calls.append((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps))
         return (gen.prefetch(calls) if wait
                 else gen.prefetch(calls, wait=False, concurrency=concurrency))
+
+    def td_samples(self, T=1.0, dt=10.0):
+        """Samples per waveform of the TD generator's padded output for (T, dt): the row length
+        of time_series_batch."""
+        cw = self.waveform_generator.create_waveform
+        if self.waveform_generator.output_type != "td" or not cw.pad_output:
+            raise ValueError("time_series_batch needs the TD generator with pad_output=True")
+        from .summation import td_length
+        return td_length(T, dt, cw.odd_len)
+
+    def time_series_batch(self, params, out, window=None, T=1.0, dt=10.0, eps=1e-5,
+                          mode_selection=None, include_minus_m=True, check=True, **kwargs):
+        """h = h+ - i hx of every row of params (B x 14, FEW's order) into the rows of out
+        (complex128 [B][N], N = td_samples(T, dt), unit stride along a row), each sample times
+        window[s] when a window (float64 [N] on the device) is given: what B calls of
+        `self(*row, T=T, dt=dt, eps=eps)` return, times the window.
+
+        The host upstream of all rows runs on the prefetch pool (each walker's sum waits for its
+        own upstream only); each walker's inputs go through a staging buffer of its own and one
+        efd_td_modesum_windowed writes its row, all on the current stream with no host
+        synchronisation between walkers. Each walker has its own TD workspace; their device-side
+        status is read once at the end (check=False: by the caller, check_td_batch())."""
+        torch = require_gpu()
+        from .summation import DeviceInputs, TDEngine
+        gen = self.waveform_generator
+        ns = self.td_samples(T, dt)
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
+        B = len(params)
+        if (out.dim() != 2 or tuple(out.shape) != (B, ns) or out.dtype != torch.complex128
+                or (B and out.stride(1) != 1)):
+            raise ValueError(f"out must be complex128 [{B}][{ns}] with contiguous rows")
+        if B > _lib.EFD_BATCH_MAX:
+            raise ValueError(f"time_series_batch: at most {_lib.EFD_BATCH_MAX} rows a call")
+        st = getattr(self, "_td_batch", None)
+        if st is None:
+            st = self._td_batch = dict(engines=[], staging=[], used=0)
+        while len(st["engines"]) < B:
+            st["engines"].append(TDEngine())
+            st["staging"].append({})
+        st["used"] = 0
+        if B == 0:
+            return out
+        self.prefetch(params, T=T, dt=dt, eps=eps, mode_selection=mode_selection,
+                      include_minus_m=include_minus_m, wait=False)
+        try:
+            for i, prm in enumerate(params.tolist()):
+                M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
+                theta, phi, rot = self._angles(qS, phiS, qK, phiK)
+                try:
+                    d = gen.prepare(M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps,
+                                    mode_selection, include_minus_m)
+                except (ValueError, RuntimeError) as e:
+                    # a walker outside the model's domain: an error, never a number
+                    raise _lib.EFDError(f"time_series_batch: upstream of row {i}: {e}") from e
+                K = len(d["m"])
+                scale = complex(rot) * (mu * MRSUN_SI / (dist * Gpc))
+                f_phi, f_r = d.get("f_phi"), d.get("f_r")
+                inp = DeviceInputs.from_host(d["t"], d["teuk"], d["Phi_phi"], d["Phi_r"], f_phi,
+                                             f_r, d["m"], d["n"], d["ylms"][:K], d["ylms"][K:],
+                                             device=out.device, staging=st["staging"][i])
+                st["used"] = i + 1
+                st["engines"][i].launch(inp, dt, ns, out=torch.view_as_real(out[i]), scale=scale,
+                                        window=window)
+        except BaseException:
+            # out is the caller's: nothing may still write it when the exception reaches them
+            torch.cuda.current_stream(out.device).synchronize()
+            raise
+        if check:
+            self.check_td_batch()
+        return out
+
+    def check_td_batch(self):
+        """Synchronise the current stream and raise if a workspace of the last
+        time_series_batch reported a device-side error (one read for the whole group)."""
+        import ctypes
+        torch = require_gpu()
+        st = getattr(self, "_td_batch", None)
+        if st is None or not st["used"]:
+            return
+        eng = st["engines"][:st["used"]]
+        lib = eng[0].lib
+        pw = (ctypes.c_void_p * len(eng))(*[e._ws.data_ptr() for e in eng])
+        stream = torch.cuda.current_stream(eng[0]._ws.device).cuda_stream
+        if lib.efd_modesum_status_batch(pw, len(eng), None, stream) != _lib.EFD_OK:
+            raise _lib.EFDError(f"efd_td_modesum: {_lib.last_error(lib)}")
 
     def fill_channels(self, out, *params, k0=None, **kwargs):
         """Write [h+, hx] over f >= 0 into the rows of out (complex128 [2][N_pos], device).

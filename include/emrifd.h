@@ -281,6 +281,43 @@ size_t efd_td_workspace_bytes(int32_t nt, int32_t K);
 int efd_td_modesum(const efd_td_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * efd_td_modesum with a time-domain window: every stored sample (out, hp and hc alike) is
+ * multiplied by window[s] (real doubles [nsamples], device) in the store epilogue; with
+ * accumulate the outputs += window * new values. window = NULL is efd_td_modesum, bitwise (the
+ * same kernel instantiation). The windowed series is what the reference transforms in
+ * FDutils.get_fft_td_windowed (:49-64: fft(h * window)); any window takes this path.
+ */
+int efd_td_modesum_windowed(const efd_td_args* a, const double* window, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/*
+ * The two channels of a TD template's transform <- get_fd_waveform_fromTD (FDutils.py:142-178:
+ * fftshift(fft(h+ w)) dt and fftshift(fft(hx w)) dt over frequency >= 0). The TD sum writes
+ * h = h+ - i hx as one complex series, so ONE complex transform Z = fft(w h) holds both:
+ *   H+[k] = (Z[k] + conj Z[(n-k) mod n]) / 2,   Hx[k] = i (Z[k] - conj Z[(n-k) mod n]) / 2,
+ * and the drivers' positive-frequency mask on the shifted grid is the natural-order bins
+ * k = 0 .. nb - 1, nb = (n + 1) / 2 (even n: no Nyquist bin, it sits on the negative side; bin 0
+ * pairs with itself). Row r of Z: complex [n] in natural DFT order at Z + 2 r stride doubles
+ * (stride >= n). Asynchronous, allocation-free; EFD_ERR_ARG before any launch for NULL pointers
+ * or size errors.
+ *   efd_td_split: row r's block complex [2][nb] at out + 2 r out_stride doubles (out_stride >=
+ *     2 nb): channel 0 = gain H+, channel 1 = gain Hx; bins with keep[k] == 0 (bytes [nb], or
+ *     NULL: keep all) are written as exact zeros.
+ *   efd_td_split_loglike: out[r] = -1/2 * 4 * sum_c sum_k | d[c][k] - h_r[c][k] w[c][k] |^2 with
+ *     h_r what efd_td_split would write (never stored; the same arithmetic, and efd_loglike's
+ *     rounding of d - h w); d complex [2][nb] and w real [2][nb], shared by the rows; scratch
+ *     holds rows * EFD_TD_SPLIT_SCRATCH device doubles. The partition depends on n only and the
+ *     final reduction has a fixed order: bitwise reproducible, no atomics. A NaN anywhere in a
+ *     row of Z makes that row's out NaN.
+ */
+#define EFD_TD_SPLIT_SCRATCH 1024
+int efd_td_split(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                 const uint8_t* keep, double* out, int64_t out_stride, void* stream);
+int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                         const double* d, const double* w, double* out, double* scratch,
+                         void* stream);
+
+/*
  * Asynchronous host -> device copy of `bytes` from `src` (pinned host memory) to `dst` on
  * `stream`: the input upload of a waveform on a pipeline slot's stream, issued through this
  * library's HIP runtime (no host synchronisation). Plumbing for the Python host layer.
@@ -475,6 +512,11 @@ int efd_inner_product_cpu(const double* a, const double* b, const double* w, int
 int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
                         const double* coef, const double* w, int64_t nelem, double* dh,
                         double* gram, double* scratch, void* stream);
+int efd_td_split_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                     const uint8_t* keep, double* out, int64_t out_stride, void* stream);
+int efd_td_split_loglike_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
+                             double gain, const double* d, const double* w, double* out,
+                             double* scratch, void* stream);
 /* OpenMP threads of the twins (n <= 0: all available); returns the previous setting. */
 int efd_cpu_threads(int n);
 /* Last error message of the calling thread's CPU-twin call. */

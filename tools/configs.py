@@ -22,6 +22,10 @@ config 4  emri_pe.py: nwalkers=16 ntemps=1 injectFD=1 template=fd Tobs=2 eps=1e-
 config 5  downsample=100 (emri_pe.py:322-364 grid), Tobs=4, nwalkers=128 -> B = 64 per
           half-step, on one GPU (the 8-GPU sharding is parallel.py's, exercised by bench.py
           --gpus N at round end)
+config t  emri_pe.py:7: -Tobs 4 -M 3.67e6 -mu 292 -e0 0.579 -eps 1e-2 -dt 10 -injectFD 0
+          -template td -nwalkers 16: the DFT of the TD generator's waveform as the template
+          (get_fd_waveform_fromTD's batched route: one complex transform per walker,
+          efd_td_split_loglike); --only t, with --window hann for -window_flag 1
 
 Parity of these configurations against the oracle is tests/test_gpu_configs.py; this tool only
 times (it never imports oracle/).
@@ -268,6 +272,7 @@ def config_like(name, T, eps, downsample, nwalkers, reps, slots=4, fused=True, g
                 **extra):
     few, like, walkers, kw, nbins = _likelihood_setup(T, eps, downsample, nwalkers, **extra)
     windowed = like.template_model.window is not None
+    td = extra.get("template") == "td"
     like.num_streams = slots
     like.fused_likelihood = fused
     if HANN_PAIR:
@@ -303,7 +308,7 @@ def config_like(name, T, eps, downsample, nwalkers, reps, slots=4, fused=True, g
     _sync()
     dev = (time.perf_counter() - t0) / reps
     cpu = None
-    if not NO_CPU and not windowed:
+    if not NO_CPU and not windowed and not td:
         # the host twin on the same walkers against the likelihood's own d and w
         import bench
         from emri_frequencydomainwaveforms_amd import pe
@@ -317,9 +322,15 @@ def config_like(name, T, eps, downsample, nwalkers, reps, slots=4, fused=True, g
             "host_upstream_ms_per_walker": cache.host_s / B * 1e3,
             "ll_truth": float(ll[0]), "ll_min": float(np.min(ll)),
             "ll_bitwise_repeatable": bool(np.array_equal(ll, ll2)), "streams": slots,
-            "fused_likelihood": fused and not windowed,
+            "fused_likelihood": fused and not windowed and not td,
             "device_note": "Likelihood.get_ll over the half-step batch with the host upstream "
                            "memoised: " + (
+                               "per group of 8 walkers each walker's (windowed) TD series "
+                               "h+ - i hx into a row of one buffer (efd_td_modesum_windowed), "
+                               "one batched complex128 transform and the two channels' logL "
+                               "reduced from it (efd_td_split_loglike): "
+                               f"{getattr(like.template_model, 'info', {})}"
+                               if td else
                                "per group of 8 walkers the FD spectra S in one batched mode "
                                "sum, the Hann window's correction as one four-step transform "
                                "pipeline over the rows' supports (efd_hann_convolve) and the "
@@ -351,6 +362,8 @@ def main():
     ap.add_argument("--hann-pair", action="store_true", help="windowed config: the logL in "
                     "its mirror-pair form after the transforms (efd_hann_loglike) instead of "
                     "the per-bin form reduced inside them (efd_hann_loglike_local)")
+    ap.add_argument("--window", default=None, help="config t: a window name "
+                    "(fdutils.COSINE_WINDOWS), as -window_flag 1 is hann")
     ap.add_argument("--python-groups", action="store_true", help="configs 4, 5: each fused "
                     "group's staging and launches as Python steps instead of one native call "
                     "(efd_fused_group)")
@@ -378,6 +391,14 @@ def main():
                                16, args.reps, args.slots, not args.unfused, args.fused_group,
                                M=3670041.7362535275, mu=292.0583167470244,
                                e0=0.5794130830706371, window_flag=True))
+        print(json.dumps(out[-1]), flush=True)
+    if "t" in which:
+        out.append(config_like("emri_pe.py:7 TD template: Tobs=4yr M=3.67e6 mu=292 e0=0.579 "
+                               "eps=1e-2 nwalkers=16 injectFD=0 template=td"
+                               + (f" window={args.window}" if args.window else ""), 4.0, 1e-2,
+                               None, 16, args.reps, args.slots, not args.unfused,
+                               args.fused_group, M=3670041.7362535275, mu=292.0583167470244,
+                               e0=0.5794130830706371, template="td", window=args.window))
         print(json.dumps(out[-1]), flush=True)
     if "5" in which:
         out.append(config_like("config5: emri_pe downsample=100 Tobs=4yr eps=1e-2 "
