@@ -1,4 +1,5 @@
-"""Build libemrifd.so in-tree (no JIT cache, so the .so travels with the repo snapshot):
+"""Build libemrifd.so in-tree (no JIT cache, so the .so travels with the repo snapshot). Every
+source is compiled to an object under build/, all of them at once, and one link step follows:
 
   csrc/emrifd_cpu.cpp -> g++ -O3 -march=x86-64-v4 -fopenmp (the host twin, efd_*_cpu; AVX-512 is
                          on both this container's Sapphire Rapids and the GPU box's EPYC 9575F)
@@ -6,7 +7,10 @@
   and the walker batches' staging
   csrc/emrifd_modes.cpp -> g++ -O3 -ffast-math -fopenmp (libmvec; knots over threads for one-at-a-time
                           calls): amplitudes, mode selection
-  csrc/emrifd.hip     -> hipcc --offload-arch=gfx950, linked with both objects and libgomp
+  csrc/emrifd.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode sum, the window path,
+                         the channel split and reductions) -> hipcc --offload-arch=gfx950 -c each;
+                         they share only csrc/emrifd_common.h (no relocatable device code)
+  link                -> hipcc -shared over the six objects, with libgomp and libmvec
 """
 
 import glob
@@ -16,6 +20,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "emrifd.hip")
+# the HIP translation units, the mode sum (SRC) first
+HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_window.hip"), os.path.join(CSRC, "emrifd_reduce.hip")]
 CPU_SRC = os.path.join(CSRC, "emrifd_cpu.cpp")
 HOST_SRC = os.path.join(CSRC, "emrifd_host.cpp")
 MODES_SRC = os.path.join(CSRC, "emrifd_modes.cpp")
@@ -23,11 +29,32 @@ OUT = os.path.join(HERE, "libemrifd.so")
 OBJDIR = os.path.join(HERE, "build")
 ARCH = os.environ.get("EFD_OFFLOAD_ARCH", "gfx950")
 CPU_ARCH = os.environ.get("EFD_CPU_ARCH", "x86-64-v4")
+LINK_LIBS = ["-lgomp", "-lmvec"]
+
+
+def obj_path(src):
+    """The object under OBJDIR that src compiles to."""
+    return os.path.join(OBJDIR, os.path.splitext(os.path.basename(src))[0] + ".o")
+
+
+HOST_OBJS = [obj_path(s) for s in (CPU_SRC, HOST_SRC, MODES_SRC)]
+
+
+def hip_compile_cmd(src, obj, flags=()):
+    """One HIP unit to an object (also how an experiment compiles its variant of a unit)."""
+    return ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *flags, "-c", src,
+            "-o", obj]
+
+
+def link_cmd(objs, out):
+    return ["hipcc", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", out, *objs, *LINK_LIBS]
 
 
 def _inputs():
+    """Every file the library is compiled from: all of csrc/ (a new source or header needs no
+    entry here) and the public header."""
     hdr = os.path.join(os.path.dirname(HERE), "include", "emrifd.h")
-    return [SRC, CPU_SRC, HOST_SRC, MODES_SRC, hdr] + glob.glob(os.path.join(CSRC, "*.inc"))
+    return [p for p in glob.glob(os.path.join(CSRC, "*")) if os.path.isfile(p)] + [hdr]
 
 
 def source_id():
@@ -64,23 +91,25 @@ def build(force=False, verbose=False, extra=()):
     if not force and not extra and built_id() == sid:
         return OUT
     os.makedirs(OBJDIR, exist_ok=True)
-    obj = os.path.join(OBJDIR, "emrifd_cpu.o")
-    hobj = os.path.join(OBJDIR, "emrifd_host.o")
-    cpu = ["g++", "-O3", f"-march={CPU_ARCH}", "-fopenmp", "-ffp-contract=off", "-fPIC",
-           "-std=c++17", "-c", CPU_SRC, "-o", obj]
-    host = ["g++", "-O3", f"-march={CPU_ARCH}", "-ffp-contract=off", "-fopenmp", "-fPIC",
-            "-std=c++17", "-c", HOST_SRC, "-o", hobj]
-    mobj = os.path.join(OBJDIR, "emrifd_modes.o")
-    modes = ["g++", "-O3", f"-march={CPU_ARCH}", "-ffast-math", "-fopenmp", "-fPIC",
-             "-std=c++17", "-c", MODES_SRC, "-o", mobj]
+    gxx = ["g++", "-O3", f"-march={CPU_ARCH}", "-fPIC", "-std=c++17", "-fopenmp"]
     bid = [f'-DEFD_BUILD_ID="{sid}"'] if not extra else []
-    hip = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", *bid,
-           *extra,
-           "-o", OUT + ".tmp", obj, hobj, mobj, SRC, "-lgomp", "-lmvec"]
-    for cmd in (cpu, host, modes, hip):
+    # the longest compile (the mode sum) first; six compilers at once, one per source
+    cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in HIP_UNITS]
+    cmds += [[*gxx, "-ffp-contract=off", "-c", CPU_SRC, "-o", obj_path(CPU_SRC)],
+             [*gxx, "-ffp-contract=off", "-c", HOST_SRC, "-o", obj_path(HOST_SRC)],
+             [*gxx, "-ffast-math", "-c", MODES_SRC, "-o", obj_path(MODES_SRC)]]
+    procs = []
+    for cmd in cmds:
         if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
+            print(" ".join(cmd), flush=True)
+        procs.append(subprocess.Popen(cmd))
+    failed = [cmd for cmd, p in zip(cmds, procs) if p.wait() != 0]   # (waits for every one)
+    if failed:
+        raise subprocess.CalledProcessError(1, failed[0])
+    link = link_cmd(HOST_OBJS + [obj_path(s) for s in HIP_UNITS], OUT + ".tmp")
+    if verbose:
+        print(" ".join(link), flush=True)
+    subprocess.run(link, check=True)
     os.replace(OUT + ".tmp", OUT)
     return OUT
 

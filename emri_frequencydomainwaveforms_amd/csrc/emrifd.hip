@@ -37,23 +37,23 @@
 //                         records stream through a double-buffered LDS stage, and the tile
 //                         writes its bins (or h+/hx) once -- no atomics, no host sync.
 // The SPA evaluation is FP64 VALU work (phases reach ~1e7 rad); MFMA is not applicable.
+//
+// This unit is the mode sum (FD and TD) and its C ABI. The window path (efd_hann_*, efd_cosw_*)
+// is emrifd_window.hip; the channel split and the reductions (efd_polarizations, efd_loglike,
+// efd_inner_product, efd_td_split*, efd_fisher_gram) are emrifd_reduce.hip. The three share
+// only emrifd_common.h.
 
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdlib>
-#include <cstdio>
-#include <algorithm>
-#include <atomic>
-#include <mutex>
-#include <cstring>
-#include <string>
-#include <type_traits>
-
-#include "../../include/emrifd.h"
+#include "emrifd_common.h"
 
 #define EFD_VERSION 100  // 0.1.0
+
+// the thread's last error (efd_last_error), set by every unit through fail
+static thread_local std::string g_err;
+
+int efdhip::fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
 
 namespace {
 
@@ -129,20 +129,6 @@ __device__ __forceinline__ double env_rsqrt(double x) {
 #define EFD_HD __device__
 #include "env_fit.inc"
 #undef EFD_HD
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            return fail(EFD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // ----------------------------------------------------------------------------------------
 // Data layouts in HBM
@@ -4333,1580 +4319,6 @@ __global__ __launch_bounds__(TD_THREADS) void k_td_modesum(
     }
 }
 
-// h+ / hx split with FEW's array flip
-__global__ void k_polarizations(const double2* __restrict__ S, int64_t nf, int64_t k0,
-                                double2* __restrict__ hp, double2* __restrict__ hc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t k = k0 + i;
-    if (k >= nf) return;
-    const double2 a = S[k], b = S[nf - 1 - k];
-    // h+ = (a + conj b)/2 ; hx = i (a - conj b)/2
-    hp[i] = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    hc[i] = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
-}
-
-// ---- The Hann window's convolution (fdutils.HannConvolution; efd_hann_*). A row's correction
-// C = K (*) S (circular, mod nf) is the linear convolution of the row's support [first, last) with
-// the lag kernel, on m-point transforms (m >= nf + (last - first) - 1): the caller's Y[s] holds
-// S[first + s] / scale for s < last - first, zero up to m (efd_hann_stage), and after its
-// transforms (the kernel's spectrum includes 1/m) C[k] = scale Y[((k - first) mod nf) + m - nf].
-// info[r] = {bits of scale = max(|Re|, |Im|), first nonzero bin, last nonzero bin + 1, 0}; a
-// NaN anywhere in the row makes the scale NaN (the bit pattern orders above every finite
-// value), so the row's outputs are NaN.
-__global__ void k_hann_info_init(uint64_t* __restrict__ info, int32_t rows) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    info[4 * r + 0] = 0;
-    info[4 * r + 1] = ~0ull;
-    info[4 * r + 2] = 0;
-    info[4 * r + 3] = 0;
-}
-// lanes (optional, int32 [rows][2]): each row's paired-grid lane range from its mode sum
-// (efd_modesum_lane_ranges); bins outside {l, nf-1-l : lo <= l < hi} hold no term, so the scan
-// covers [min(lo, nf-hi), max(hi, nf-lo)) only
-__global__ __launch_bounds__(256) void k_hann_extent(const double2* __restrict__ S, int64_t stride,
-                                                     int64_t nf, const int32_t* __restrict__ lanes,
-                                                     uint64_t* __restrict__ info) {
-    const double2* row = S + (int64_t)blockIdx.y * stride;
-    int64_t k_lo = 0, k_hi = nf;
-    if (lanes != nullptr) {
-        const int64_t llo = lanes[2 * blockIdx.y], lhi = lanes[2 * blockIdx.y + 1];
-        if (llo >= lhi) {
-            k_hi = 0;   // no segment: an all-zero row
-        } else {
-            k_lo = max((int64_t)0, min(llo, nf - lhi));
-            k_hi = min(nf, max(lhi, nf - llo));
-        }
-    }
-    uint64_t mx = 0, lo = ~0ull, hi = 0;
-#pragma unroll 8
-    for (int64_t k = k_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < k_hi;
-         k += (int64_t)gridDim.x * blockDim.x) {
-        const double2 v = row[k];
-        const uint64_t bx = (uint64_t)__double_as_longlong(fabs(v.x));
-        const uint64_t by = (uint64_t)__double_as_longlong(fabs(v.y));
-        mx = max(mx, max(bx, by));
-        if ((bx | by) != 0) {          // nonzero (or NaN)
-            lo = min(lo, (uint64_t)k);
-            hi = (uint64_t)k + 1;      // k grows along the thread's stride
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = max(mx, (uint64_t)__shfl_xor((unsigned long long)mx, o, 64));
-        lo = min(lo, (uint64_t)__shfl_xor((unsigned long long)lo, o, 64));
-        hi = max(hi, (uint64_t)__shfl_xor((unsigned long long)hi, o, 64));
-    }
-    // the block's 4 waves through LDS, then one thread's 3 atomics per block (a few hundred
-    // per row: contention on the row's 3 words stays small)
-    __shared__ uint64_t red[3][4];
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wv] = mx;
-        red[1][wv] = lo;
-        red[2][wv] = hi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 4; ++i) {
-            mx = max(mx, red[0][i]);
-            lo = min(lo, red[1][i]);
-            hi = max(hi, red[2][i]);
-        }
-        uint64_t* in = info + 4 * blockIdx.y;
-        if (mx) atomicMax((unsigned long long*)&in[0], (unsigned long long)mx);
-        if (hi) {
-            atomicMin((unsigned long long*)&in[1], (unsigned long long)lo);
-            atomicMax((unsigned long long*)&in[2], (unsigned long long)hi);
-        }
-    }
-}
-struct HannRow {
-    int64_t first, len;
-    double scale;   // 0 for an all-zero row (its Y is zero)
-};
-__device__ __forceinline__ HannRow hann_row(const uint64_t* __restrict__ info, int r) {
-    HannRow h;
-    const uint64_t lo = info[4 * r + 1], hi = info[4 * r + 2];
-    h.first = hi ? (int64_t)lo : 0;
-    h.len = hi ? (int64_t)(hi - lo) : 0;
-    h.scale = __longlong_as_double((long long)info[4 * r + 0]);
-    return h;
-}
-__global__ __launch_bounds__(256) void k_hann_stage(const double2* __restrict__ S, int64_t stride,
-                                                    const uint64_t* __restrict__ info, int64_t m,
-                                                    float2* __restrict__ Y) {
-    const int r = blockIdx.y;
-    const HannRow h = hann_row(info, r);
-    const double2* row = S + (int64_t)r * stride + h.first;
-    float2* y = Y + (int64_t)r * m;
-    const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;   // NaN scale: NaN row
-    const bool bad = h.len > m;     // the host sized m from info: never, but never write past Y
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < m;
-         s += (int64_t)gridDim.x * blockDim.x) {
-        float2 v = make_float2(0.f, 0.f);
-        if (bad) {
-            v = make_float2(__int_as_float(0x7fc00000), 0.f);
-        } else if (s < h.len) {
-            const double2 x = row[s];
-            v = make_float2((float)(x.x * inv), (float)(x.y * inv));
-        }
-        y[s] = v;
-    }
-}
-// ---- The Hann correction's convolution as one four-step FFT pipeline (efd_hann_convolve).
-// Y = ifft_m(fft_m(y) * kf) for power-of-two m = R * C, C = 8192, R = m / C (256..4096), in
-// complex64, with y the scaled support of each row (efd_hann_stage's values, computed on the
-// fly). Index s = C r + c (row r, column c), frequency f = f_r + R f_c:
-//   (A) columns: length-R FFT over r of every column c, times w_m^(c f_r)   -> [f_r][c]
-//   (B) rows:    length-C FFT over c of every row f_r gives X[f_r + R f_c] at [f_r][f_c]; times
-//                the lag kernel's spectrum in the same order (kfp[f_r C + f_c] = kf[f_r + R f_c],
-//                1/m included); inverse length-C FFT                           -> [f_r][c]
-//   (C) columns: times w_m^(-c f_r), inverse length-R FFT over f_r          -> [r][c] = Y[s]
-// The spectrum is never put in natural order: the two transposes on each side of rocFFT's
-// 2^24-point transform (five kernels per direction) and the separate stage and multiply passes
-// are gone; three passes over Y remain. Stockham radix-8 passes (a radix-4 or -2 one last) in
-// LDS, ~70 KB per workgroup so two share a CU (one's global loads overlap the other's
-// transforms), twiddles from __sincosf (absolute error ~5e-7: the correction needs ~3 digits).
-constexpr int FC_C = 8192;             // row length (LDS: 8192 x 8 B + 1/16 padding = 68 KB)
-constexpr int FC_NT = 512;             // threads of a column or row workgroup
-constexpr float FC_2PI = 6.283185307179586f;
-constexpr float FC_SQRT_HALF = 0.70710678118654752f;
-
-// complex64 values as 2-wide float vectors: the arithmetic below compiles to packed FP32
-// instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32, one issue slot per complex add or
-// half a complex multiply), about half the VALU instructions of scalar float2 code
-typedef float fcv __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ fcv cmulf(fcv a, fcv b) {
-    const fcv t = a.xx * b;
-    return __builtin_elementwise_fma(a.yy, b.yx * (fcv){-1.0f, 1.0f}, t);
-}
-// x times -i (SIGN -1) or +i (SIGN +1)
-template <int SIGN>
-__device__ __forceinline__ fcv cmuli(fcv x) {
-    return x.yx * (SIGN < 0 ? (fcv){1.0f, -1.0f} : (fcv){-1.0f, 1.0f});
-}
-// natural-order DFTs of 4 and 8 points in registers, exp(SIGN 2 pi i n k / N)
-template <int SIGN>
-__device__ __forceinline__ void fc_dft4(fcv& a0, fcv& a1, fcv& a2, fcv& a3) {
-    const fcv t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3;
-    const fcv t3 = cmuli<SIGN>(a1 - a3);
-    a0 = t0 + t2;
-    a1 = t1 + t3;
-    a2 = t0 - t2;
-    a3 = t1 - t3;
-}
-template <int SIGN>
-__device__ __forceinline__ void fc_dft8(fcv* v) {
-    fcv e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-    fcv o0 = v[1], o1 = v[3], o2 = v[5], o3 = v[7];
-    fc_dft4<SIGN>(e0, e1, e2, e3);
-    fc_dft4<SIGN>(o0, o1, o2, o3);
-    // o_k times w8^k, w8 = (1 + SIGN i) / sqrt 2: w8 o = (o + SIGN i o) / sqrt 2,
-    // w8^3 o = (-o + SIGN i o) / sqrt 2
-    o1 = FC_SQRT_HALF * (o1 + cmuli<SIGN>(o1));
-    o2 = cmuli<SIGN>(o2);
-    o3 = FC_SQRT_HALF * (cmuli<SIGN>(o3) - o3);
-    v[0] = e0 + o0;
-    v[1] = e1 + o1;
-    v[2] = e2 + o2;
-    v[3] = e3 + o3;
-    v[4] = e0 - o0;
-    v[5] = e1 - o1;
-    v[6] = e2 - o2;
-    v[7] = e3 - o3;
-}
-// element e of line j in LDS: columns pass [e][j] rows padded to NCOL + 1, rows pass one line
-// with a pad element every 16
-template <int NCOL>
-struct FcColIdx {
-    // (2 columns: no pad, so m = 2^25's 4096-row blocks fit two workgroups per CU; 8 columns: no
-    // pad either, the reads of 4 lines x 8 columns by 32 lanes then fill the 64 banks (the pad
-    // of 9 made them 2-way, r05z5: 0.47 of the LDS cycles conflicts) and only the first
-    // pass's stores, 2 lines x 8 columns per 16-lane group at 8 lines apart, are 2-way)
-    static constexpr int STRIDE = (NCOL > 2 && NCOL != 8) ? NCOL + 1 : NCOL;
-    __device__ __forceinline__ int operator()(int j, int e) const { return e * STRIDE + j; }
-};
-struct FcRowIdx {
-    __device__ __forceinline__ int operator()(int, int e) const { return e + (e >> 4); }
-};
-
-// One Stockham pass of radix RAD over 2^LOGL lines of length L held in LDS (in place: every
-// thread reads its butterflies into registers, barrier, writes). SIGN -1: forward.
-template <int RAD, int SIGN, int NITEM, int LOGL, class Idx>
-__device__ __forceinline__ void fc_pass(fcv* sm, int L, int lgNs, Idx idx) {
-    fcv v[NITEM][RAD];
-    const int Ns = 1 << lgNs;
-    const int tid = threadIdx.x;
-    const int bfly = L / RAD;
-#pragma unroll
-    for (int q = 0; q < NITEM; ++q) {
-        const int item = tid + q * FC_NT;
-        const int j = item & ((1 << LOGL) - 1), b = item >> LOGL;
-        const int k = b & (Ns - 1);
-#pragma unroll
-        for (int r = 0; r < RAD; ++r) v[q][r] = sm[idx(j, b + r * bfly)];
-        if (lgNs > 0) {
-            float sn, cs;
-            // 2 pi k / (Ns RAD): the power-of-two division as an exponent shift
-            __sincosf((float)SIGN * FC_2PI * ldexpf((float)k, -(lgNs + (RAD == 8 ? 3 : RAD == 4 ? 2 : 1))),
-                      &sn, &cs);
-            const fcv w1 = {cs, sn};
-            fcv w = w1;
-#pragma unroll
-            for (int r = 1; r < RAD; ++r) {
-                v[q][r] = cmulf(v[q][r], w);
-                if (r + 1 < RAD) w = cmulf(w, w1);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NITEM; ++q) {
-        const int item = tid + q * FC_NT;
-        const int j = item & ((1 << LOGL) - 1), b = item >> LOGL;
-        const int d = ((b >> lgNs) << lgNs) * RAD + (b & (Ns - 1));
-        if (RAD == 8) {
-            fc_dft8<SIGN>(v[q]);
-        } else if (RAD == 4) {
-            fc_dft4<SIGN>(v[q][0], v[q][1], v[q][2], v[q][3]);
-        } else {
-            const fcv a0 = v[q][0], a1 = v[q][1];
-            v[q][0] = a0 + a1;
-            v[q][1] = a0 - a1;
-        }
-#pragma unroll
-        for (int r = 0; r < RAD; ++r) sm[idx(j, d + r * Ns)] = v[q][r];
-    }
-    __syncthreads();
-}
-
-// the whole length-L transform of 2^LOGL lines (natural order in, natural order out): radix-8
-// passes, then one radix-4 or radix-2 pass for the rest
-template <int SIGN, int L, int LOGL, class Idx>
-__device__ __forceinline__ void fc_fft(fcv* sm, Idx idx) {
-    constexpr int N8 = ((L / 8) << LOGL) / FC_NT;
-    static_assert(((L / 8) << LOGL) % FC_NT == 0, "radix-8 butterflies: whole rounds per thread");
-    int lg = 0;
-#pragma unroll 1
-    for (; (8 << lg) <= L; lg += 3) fc_pass<8, SIGN, N8, LOGL>(sm, L, lg, idx);
-    if ((4 << lg) == L) fc_pass<4, SIGN, ((L / 4) << LOGL) / FC_NT, LOGL>(sm, L, lg, idx);
-    else if ((2 << lg) == L) fc_pass<2, SIGN, ((L / 2) << LOGL) / FC_NT, LOGL>(sm, L, lg, idx);
-}
-
-template <int R>
-struct FcCols {
-    static constexpr int NCOL = R >= 4096 ? 2 : R >= 2048 ? 4 : R >= 1024 ? 8 : 16;
-    static constexpr int LOGL = NCOL == 2 ? 1 : NCOL == 4 ? 2 : NCOL == 8 ? 3 : 4;
-};
-
-// (A) and (C): NCOL columns per workgroup. FWD: load the scaled support of row blockIdx.y
-// straight from S (efd_hann_stage's values), forward FFT, twiddle, store. Inverse: load,
-// conjugate twiddle, inverse FFT, store in natural order.
-// (<= 128 VGPRs: two 8-wave workgroups per CU, 4 waves per SIMD)
-template <bool FWD, int R, int C = FC_C>
-__global__ __launch_bounds__(FC_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k_fc_cols(const double2* __restrict__ S, int64_t stride, const uint64_t* __restrict__ info,
-               float2* __restrict__ Yv) {
-    constexpr int NCOL = FcCols<R>::NCOL, LOGL = FcCols<R>::LOGL;
-    constexpr int64_t M = (int64_t)R * C;
-    constexpr int NQ = R * NCOL / FC_NT;   // elements per thread
-    static_assert(R * NCOL % FC_NT == 0, "whole rounds of elements per thread");
-    __shared__ fcv sm[R * FcColIdx<NCOL>::STRIDE];
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
-    const FcColIdx<NCOL> idx;
-    const int row = blockIdx.y;
-    // XCD-aware column blocks: workgroups are dealt round-robin over the 8 XCDs (x = b mod 8),
-    // so XCD x takes the contiguous eighth [x G/8, (x+1) G/8) of the G column blocks in order;
-    // a block's rows are NCOL * 8 or 16 B wide, and the neighbouring blocks sharing their
-    // 128-B lines then hit the same L2
-    constexpr int G = C / NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
-    const int c0 = ((blockIdx.x & 7) * (G / 8) + (blockIdx.x >> 3)) * NCOL;
-    fcv* y = Y + (int64_t)row * M;
-    if (FWD) {
-        const HannRow h = hann_row(info, row);
-        const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;
-        const double2* src = S + (int64_t)row * stride + h.first;
-        const bool bad = h.len > M;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = threadIdx.x + q * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;
-            const int64_t s = (int64_t)e * C + c0 + j;
-            fcv v = {0.f, 0.f};
-            if (bad) {
-                v = (fcv){__int_as_float(0x7fc00000), 0.f};
-            } else if (s < h.len) {
-                const double2 x = src[s];
-                v = (fcv){(float)(x.x * inv), (float)(x.y * inv)};
-            }
-            sm[idx(j, e)] = v;
-        }
-        __syncthreads();
-        fc_fft<-1, R, LOGL>(sm, idx);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = threadIdx.x + q * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;   // e = f_r
-            const int c = c0 + j;
-            const uint32_t p = (uint32_t)c * (uint32_t)e;   // < C R = M: no reduction
-            float sn, cs;
-            __sincosf(-FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-            y[(int64_t)e * C + c] = cmulf(sm[idx(j, e)], (fcv){cs, sn});
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = threadIdx.x + q * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;   // e = f_r
-            const int c = c0 + j;
-            const uint32_t p = (uint32_t)c * (uint32_t)e;   // < C R = M: no reduction
-            float sn, cs;
-            __sincosf(FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-            sm[idx(j, e)] = cmulf(y[(int64_t)e * C + c], (fcv){cs, sn});
-        }
-        __syncthreads();
-        fc_fft<1, R, LOGL>(sm, idx);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = threadIdx.x + q * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;
-            y[(int64_t)e * C + c0 + j] = sm[idx(j, e)];
-        }
-    }
-}
-
-// (B): one row f_r per workgroup: forward FFT, times the kernel's spectrum, inverse FFT, as
-// three register stages per direction with two LDS exchanges between them (8192 = 32 x 16 x 16):
-//   forward  (A) thread t = n2 (n = n2 + 256 n1): DFT-32 over n1, times w_8192^(n2 k1)
-//            (B) task (k1, n2a) (n2 = n2a + 16 n2b): DFT-16 over n2b, times w_256^(n2a k2a)
-//            (C) task (k1, k2a): DFT-16 over n2a -> X[k1 + 32 k2a + 512 k2b], natural index k
-//   times the kernel's spectrum at k, then the transpose of the same steps: the inverse of (C) on
-//   the same task's registers (no exchange), of (B), of (A) -> x[n2 + 256 n1], natural order.
-// Four exchanges of 64 KB per row instead of the Stockham passes' ten (five radix-8/2 passes per
-// direction, each a 64-KB LDS read and write) and the multiply's own pass; every exchange is
-// bank-conflict free (exchange 1: rows of 257 elements, lanes along k1 at stride 514 words;
-// exchange 2: [k2a][n2a][k1], lanes along k1). Twiddle powers from two __sincosf (w, w^8).
-constexpr int FR_NT = 256;     // threads of the row workgroup (32 elements each)
-constexpr int FR_S1 = 257;     // exchange 1: LDS row stride of [k1][n2] (elements)
-// cos and sin of 2 pi j / 32
-constexpr float FC_COS32[32] = {
-    1.000000000e+00f, 9.807852804e-01f, 9.238795325e-01f, 8.314696123e-01f, 7.071067812e-01f,
-    5.555702330e-01f, 3.826834324e-01f, 1.950903220e-01f, 0.0f, -1.950903220e-01f,
-    -3.826834324e-01f, -5.555702330e-01f, -7.071067812e-01f, -8.314696123e-01f,
-    -9.238795325e-01f, -9.807852804e-01f, -1.000000000e+00f, -9.807852804e-01f,
-    -9.238795325e-01f, -8.314696123e-01f, -7.071067812e-01f, -5.555702330e-01f,
-    -3.826834324e-01f, -1.950903220e-01f, 0.0f, 1.950903220e-01f, 3.826834324e-01f,
-    5.555702330e-01f, 7.071067812e-01f, 8.314696123e-01f, 9.238795325e-01f, 9.807852804e-01f};
-// w_N^j = exp(SIGN 2 pi i j / N) for N = 16, 32 (compile-time j: constant-folded)
-template <int SIGN, int N>
-__device__ __forceinline__ fcv fc_w(int j) {
-    const int q = (j * (32 / N)) & 31;
-    return (fcv){FC_COS32[q], (float)SIGN * FC_COS32[(q + 24) & 31]};
-}
-// natural-order DFT-16 (4 x 4) and DFT-32 (4 x 8) in registers, exp(SIGN 2 pi i n k / N)
-template <int SIGN>
-__device__ __forceinline__ void fc_dft16(fcv* v) {
-    fcv t[4][4];
-#pragma unroll
-    for (int n1 = 0; n1 < 4; ++n1) {   // DFT-4 over n2 of x[n1 + 4 n2]
-        fcv a0 = v[n1], a1 = v[n1 + 4], a2 = v[n1 + 8], a3 = v[n1 + 12];
-        fc_dft4<SIGN>(a0, a1, a2, a3);
-        t[n1][0] = a0; t[n1][1] = a1; t[n1][2] = a2; t[n1][3] = a3;
-    }
-#pragma unroll
-    for (int n1 = 1; n1 < 4; ++n1)
-#pragma unroll
-        for (int k1 = 1; k1 < 4; ++k1) t[n1][k1] = cmulf(t[n1][k1], fc_w<SIGN, 16>(n1 * k1));
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {   // DFT-4 over n1 -> X[k1 + 4 k2]
-        fcv a0 = t[0][k1], a1 = t[1][k1], a2 = t[2][k1], a3 = t[3][k1];
-        fc_dft4<SIGN>(a0, a1, a2, a3);
-        v[k1] = a0; v[k1 + 4] = a1; v[k1 + 8] = a2; v[k1 + 12] = a3;
-    }
-}
-template <int SIGN>
-__device__ __forceinline__ void fc_dft32(fcv* v) {
-    fcv t[8][4];
-#pragma unroll
-    for (int n1 = 0; n1 < 8; ++n1) {   // DFT-4 over n2 of x[n1 + 8 n2]
-        fcv a0 = v[n1], a1 = v[n1 + 8], a2 = v[n1 + 16], a3 = v[n1 + 24];
-        fc_dft4<SIGN>(a0, a1, a2, a3);
-        t[n1][0] = a0; t[n1][1] = a1; t[n1][2] = a2; t[n1][3] = a3;
-    }
-#pragma unroll
-    for (int n1 = 1; n1 < 8; ++n1)
-#pragma unroll
-        for (int k1 = 1; k1 < 4; ++k1) t[n1][k1] = cmulf(t[n1][k1], fc_w<SIGN, 32>(n1 * k1));
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {   // DFT-8 over n1 -> X[k1 + 4 k2]
-        fcv e[8];
-#pragma unroll
-        for (int n1 = 0; n1 < 8; ++n1) e[n1] = t[n1][k1];
-        fc_dft8<SIGN>(e);
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) v[k1 + 4 * k2] = e[k2];
-    }
-}
-// v[j] *= w^j, j = 0 .. N-1, w = exp(i theta): powers from w and w^8 (at most 3 + 7 products)
-template <int N>
-__device__ __forceinline__ void fc_twiddle_pow(fcv* v, float theta) {
-    float s1, c1, s8, c8;
-    __sincosf(theta, &s1, &c1);
-    __sincosf(8.0f * theta, &s8, &c8);
-    const fcv w1 = {c1, s1}, w8 = {c8, s8};
-    fcv p[8];
-    p[0] = (fcv){1.0f, 0.0f};
-    p[1] = w1;
-#pragma unroll
-    for (int j = 2; j < 8; ++j) p[j] = cmulf(p[j - 1], w1);
-    fcv b = (fcv){1.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < N / 8; ++a) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (a + j > 0) v[8 * a + j] = cmulf(v[8 * a + j], a == 0 ? p[j] : (j == 0 ? b : cmulf(b, p[j])));
-        b = a == 0 ? w8 : cmulf(b, w8);
-    }
-}
-// v[j] *= w0 w^j, j = 0 .. N-1, w = exp(i theta): fc_twiddle_pow with the constant factor w0
-// folded into the powers (8 products instead of N)
-template <int N>
-__device__ __forceinline__ void fc_twiddle_pow_from(fcv* v, fcv w0, float theta) {
-    float s1, c1, s8, c8;
-    __sincosf(theta, &s1, &c1);
-    __sincosf(8.0f * theta, &s8, &c8);
-    const fcv w1 = {c1, s1}, w8 = {c8, s8};
-    fcv p[8];
-    p[0] = w0;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) p[j] = cmulf(p[j - 1], w1);
-    fcv b = (fcv){1.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < N / 8; ++a) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[8 * a + j] = cmulf(v[8 * a + j], a == 0 ? p[j] : cmulf(b, p[j]));
-        b = a == 0 ? w8 : cmulf(b, w8);
-    }
-}
-__global__ __launch_bounds__(FR_NT)
-void k_fc_rows(const float2* __restrict__ kfpv, int64_t m, int rows, float2* __restrict__ Yv) {
-    static_assert(FC_C == 32 * 16 * 16 && FR_NT == 256, "row transform: 8192 = 32 x 16 x 16");
-    __shared__ fcv sm[32 * FR_S1];   // exchange 1 [k1][n2] (stride 257); exchange 2 [k2a][n2a][k1]
-    const fcv* kfp = reinterpret_cast<const fcv*>(kfpv);
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
-    // (row f_r, walker) pairs: XCD x = b mod 8 takes the contiguous eighth of them in f_r-major
-    // order, so a kernel-spectrum row is read from HBM once per XCD and from its L2 for the
-    // group's other walkers (gridDim.x = R * rows, a multiple of 8)
-    const int64_t npair = (int64_t)gridDim.x;
-    const int64_t p = (int64_t)(blockIdx.x & 7) * (npair >> 3) + (blockIdx.x >> 3);
-    const int fr = (int)(p / rows), wk = (int)(p - (int64_t)fr * rows);
-    fcv* y = Y + (int64_t)wk * m + (int64_t)fr * FC_C;
-    const fcv* kr = kfp + (int64_t)fr * FC_C;
-    const int t = threadIdx.x;
-    constexpr float W8192 = FC_2PI / 8192.0f, W256 = FC_2PI / 256.0f;
-    {   // forward (A): n2 = t
-        fcv v[32];
-#pragma unroll
-        for (int n1 = 0; n1 < 32; ++n1) v[n1] = y[t + 256 * n1];
-        fc_dft32<-1>(v);
-        fc_twiddle_pow<32>(v, -W8192 * (float)t);
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) sm[k1 * FR_S1 + t] = v[k1];
-    }
-    __syncthreads();
-    fcv u[2][16];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // forward (B): task (k1, n2a)
-        const int q = t + 256 * h, k1 = q & 31, n2a = q >> 5;
-#pragma unroll
-        for (int n2b = 0; n2b < 16; ++n2b) u[h][n2b] = sm[k1 * FR_S1 + n2a + 16 * n2b];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h, k1 = q & 31, n2a = q >> 5;
-        fc_dft16<-1>(u[h]);
-        fc_twiddle_pow<16>(u[h], -W256 * (float)n2a);
-#pragma unroll
-        for (int k2a = 0; k2a < 16; ++k2a) sm[(k2a * 16 + n2a) * 32 + k1] = u[h][k2a];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // forward (C), the kernel's spectrum, inverse (C): (k1, k2a)
-        const int q = t + 256 * h, k1 = q & 31, k2a = q >> 5;
-#pragma unroll
-        for (int n2a = 0; n2a < 16; ++n2a) u[h][n2a] = sm[(k2a * 16 + n2a) * 32 + k1];
-        fc_dft16<-1>(u[h]);
-#pragma unroll
-        for (int k2b = 0; k2b < 16; ++k2b)
-            u[h][k2b] = cmulf(u[h][k2b], kr[k1 + 32 * k2a + 512 * k2b]);
-        fc_dft16<1>(u[h]);
-        fc_twiddle_pow<16>(u[h], W256 * (float)k2a);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h, k1 = q & 31, k2a = q >> 5;
-#pragma unroll
-        for (int n2a = 0; n2a < 16; ++n2a) sm[(k2a * 16 + n2a) * 32 + k1] = u[h][n2a];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // inverse (B): task (k1, n2a)
-        const int q = t + 256 * h, k1 = q & 31, n2a = q >> 5;
-#pragma unroll
-        for (int k2a = 0; k2a < 16; ++k2a) u[h][k2a] = sm[(k2a * 16 + n2a) * 32 + k1];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h, k1 = q & 31, n2a = q >> 5;
-        fc_dft16<1>(u[h]);   // -> n2b
-        // times w_8192^(-n2 k1), n2 = n2a + 16 n2b: w^(n2a k1) (w^(16 k1))^n2b
-        float s0, c0;
-        __sincosf(W8192 * (float)(n2a * k1), &s0, &c0);
-        const fcv w0 = {c0, s0};
-#pragma unroll
-        for (int n2b = 0; n2b < 16; ++n2b) u[h][n2b] = cmulf(u[h][n2b], w0);
-        fc_twiddle_pow<16>(u[h], W8192 * 16.0f * (float)k1);
-#pragma unroll
-        for (int n2b = 0; n2b < 16; ++n2b) sm[k1 * FR_S1 + n2a + 16 * n2b] = u[h][n2b];
-    }
-    __syncthreads();
-    {   // inverse (A): n2 = t -> x[n2 + 256 n1]
-        fcv v[32];
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) v[k1] = sm[k1 * FR_S1 + t];
-        fc_dft32<1>(v);
-#pragma unroll
-        for (int n1 = 0; n1 < 32; ++n1) y[t + 256 * n1] = v[n1];
-    }
-}
-
-// (B) for rows of C = 16384 (m = 2^24 as 1024 x 16384: wider column segments, 128 B of S and 64 B
-// of Y per row of a column block), register-staged as k_fc_rows with 512 threads of 32 elements
-// (16384 = 32 x 32 x 16; n = n2 + 512 n1, n2 = n2a + 16 n2b; k = k1 + 32 k2a + 1024 k2b): forward
-// (A) thread n2: DFT-32 over n1, times w_16384^(n2 k1); (B) task (k1, n2a): DFT-32 over n2b,
-// times w_512^(n2a k2a); (C) task (k1, k2a), two per thread: DFT-16 over n2a; the kernel's
-// spectrum; the transposed steps back. (Round 5 also kept complex exchanges with 128 KB of LDS,
-// one workgroup per CU: 650 against 575-579 us, r05z; deleted in round 6.)
-constexpr int FC_C16 = 16384;
-// Every exchange in two passes (real parts, then imaginary parts) through a float array: 69.6 KB of LDS and at most 128 VGPRs, so two workgroups share a CU and one's
-// loads and stores overlap the other's transforms (one per CU leaves HBM idle while it
-// computes). Exchange 1 [k1][n2] stride 513, exchange 2 [k2a][n2a][k1] unpadded: every b32
-// access of a 32-lane bank group hits 32 distinct banks (ds_read_b32 / ds_write_b32 bank
-// (a/4) mod 32; stride 514 read exchange 1 2-way, r05z5: 0.20 of the LDS cycles conflicts).
-constexpr int FR16_T1 = 513, FR16_T2 = 512;
-__global__ __launch_bounds__(FC_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k_fc_rows16k_h(const float2* __restrict__ kfpv, int64_t m, int rows, float2* __restrict__ Yv) {
-    static_assert(FC_NT == 512 && FC_C16 == 32 * 32 * 16, "16384 = 32 x 32 x 16, 512 threads");
-    __shared__ float sf[32 * (FR16_T1 > FR16_T2 ? FR16_T1 : FR16_T2)];
-    const fcv* kfp = reinterpret_cast<const fcv*>(kfpv);
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
-    const int64_t npair = (int64_t)gridDim.x;
-    const int64_t p = (int64_t)(blockIdx.x & 7) * (npair >> 3) + (blockIdx.x >> 3);
-    const int fr = (int)(p / rows), wk = (int)(p - (int64_t)fr * rows);
-    fcv* y = Y + (int64_t)wk * m + (int64_t)fr * FC_C16;
-    const fcv* kr = kfp + (int64_t)fr * FC_C16;
-    const int t = threadIdx.x;
-    const int kb = t & 31, nb = t >> 5;
-    constexpr float W16K = FC_2PI / 16384.0f, W512 = FC_2PI / 512.0f;
-    fcv v[32], u[32], w[2][16];
-#pragma unroll
-    for (int n1 = 0; n1 < 32; ++n1) v[n1] = y[t + 512 * n1];
-    fc_dft32<-1>(v);   // forward (A): n2 = t
-    fc_twiddle_pow<32>(v, -W16K * (float)t);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {   // exchange 1 -> (B) task (k1 = kb, n2a = nb)
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) sf[k1 * FR16_T1 + t] = c ? v[k1].y : v[k1].x;
-        __syncthreads();
-#pragma unroll
-        for (int n2b = 0; n2b < 32; ++n2b) {
-            const float x = sf[kb * FR16_T1 + nb + 16 * n2b];
-            if (c) u[n2b].y = x; else u[n2b].x = x;
-        }
-        __syncthreads();
-    }
-    fc_dft32<-1>(u);
-    fc_twiddle_pow<32>(u, -W512 * (float)nb);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {   // exchange 2 -> (C) tasks (k1, k2a)
-#pragma unroll
-        for (int k2a = 0; k2a < 32; ++k2a) sf[k2a * FR16_T2 + nb * 32 + kb] = c ? u[k2a].y : u[k2a].x;
-        __syncthreads();
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int q = t + 512 * h, k1 = q & 31, k2a = q >> 5;
-#pragma unroll
-            for (int n2a = 0; n2a < 16; ++n2a) {
-                const float x = sf[k2a * FR16_T2 + n2a * 32 + k1];
-                if (c) w[h][n2a].y = x; else w[h][n2a].x = x;
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {   // forward (C), the kernel's spectrum, inverse (C)
-        const int q = t + 512 * h, k1 = q & 31, k2a = q >> 5;
-        fc_dft16<-1>(w[h]);
-#pragma unroll
-        for (int k2b = 0; k2b < 16; ++k2b)
-            w[h][k2b] = cmulf(w[h][k2b], kr[k1 + 32 * k2a + 1024 * k2b]);
-        fc_dft16<1>(w[h]);
-        fc_twiddle_pow<16>(w[h], W512 * (float)k2a);
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {   // exchange 2 back -> inverse (B)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int q = t + 512 * h, k1 = q & 31, k2a = q >> 5;
-#pragma unroll
-            for (int n2a = 0; n2a < 16; ++n2a)
-                sf[k2a * FR16_T2 + n2a * 32 + k1] = c ? w[h][n2a].y : w[h][n2a].x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k2a = 0; k2a < 32; ++k2a) {
-            const float x = sf[k2a * FR16_T2 + nb * 32 + kb];
-            if (c) u[k2a].y = x; else u[k2a].x = x;
-        }
-        __syncthreads();
-    }
-    fc_dft32<1>(u);   // -> n2b, times w_16384^(-n2 k1)
-    {
-        float s0, c0;
-        __sincosf(W16K * (float)(nb * kb), &s0, &c0);
-        fc_twiddle_pow_from<32>(u, (fcv){c0, s0}, W16K * 16.0f * (float)kb);
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {   // exchange 1 back -> inverse (A): n2 = t
-#pragma unroll
-        for (int n2b = 0; n2b < 32; ++n2b) sf[kb * FR16_T1 + nb + 16 * n2b] = c ? u[n2b].y : u[n2b].x;
-        __syncthreads();
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) {
-            const float x = sf[k1 * FR16_T1 + t];
-            if (c) v[k1].y = x; else v[k1].x = x;
-        }
-        if (c == 0) __syncthreads();
-    }
-    fc_dft32<1>(v);
-    // the store offsets from an opaque copy of t: else the compiler keeps the loads' 32
-    // addresses live across the kernel (spilled to scratch)
-    int to = t;
-    __asm__ volatile("" : "+v"(to));
-#pragma unroll
-    for (int n1 = 0; n1 < 32; ++n1) y[to + 512 * n1] = v[n1];
-}
-
-// (A) for R = 1024 with rows of C = 16384 (m = 2^24 as 1024 x 16384), NCOL = 8 columns per
-// workgroup, register-staged (1024 = 16 x 8 x 8; n = n2 + 64 n1, n2 = n2a + 8 n2b; k = k1 + 16 k2a
-// + 128 k2b): task (j, n2): DFT-16 over n1, times w_1024^(n2 k1); (B) tasks (j, k1, n2a), two per
-// thread: DFT-8 over n2b, times w_64^(n2a k2a); (C) tasks (j, k1, k2a), two per thread: DFT-8
-// over n2a -> f_r = k. Exchange 1 [k1][n2][j], exchange 2 [k1][k2a][n2a (pad to 9)][j]: lanes
-// along j then n2a / k2a, conflict-free. 252 against the Stockham kernel's 369 us (r05z3). The
-// inverse columns stay on the Stockham kernel k_fc_cols<false, 1024, 16384>: the staged inverse
-// measured 549 against 476 us (r05z3; deleted in round 6).
-constexpr int FCD_R = 1024, FCD_NCOL = 8, FCD_S2 = 9;
-__global__ __launch_bounds__(FC_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k_fc_cols1024(const double2* __restrict__ S, int64_t stride, const uint64_t* __restrict__ info,
-                   float2* __restrict__ Yv) {
-    static_assert(FC_NT == 512 && FCD_R * FCD_NCOL == 16 * FC_NT, "16 elements per thread");
-    constexpr int C = FC_C16;
-    constexpr int64_t M = (int64_t)FCD_R * C;
-    // exchange 1: 16 x 64 x 8 = 8192; exchange 2: 16 x 8 x 9 x 8 = 9216 elements (73.7 KB)
-    __shared__ fcv sm[16 * 8 * FCD_S2 * FCD_NCOL];
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
-    const int row = blockIdx.y;
-    constexpr int G = C / FCD_NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
-    const int c0 = ((blockIdx.x & 7) * (G / 8) + (blockIdx.x >> 3)) * FCD_NCOL;
-    fcv* y = Y + (int64_t)row * M;
-    const int t = threadIdx.x;
-    const int j = t & 7;
-    const int c = c0 + j;
-    constexpr float W1024 = FC_2PI / 1024.0f, W64 = FC_2PI / 64.0f;
-    auto e1 = [](int k1, int n2, int jj) { return (k1 * 64 + n2) * FCD_NCOL + jj; };
-    auto e2 = [](int k1, int k2a, int n2a, int jj) {
-        return ((k1 * 8 + k2a) * FCD_S2 + n2a) * FCD_NCOL + jj;
-    };
-    {
-        const HannRow h = hann_row(info, row);
-        const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;
-        const double2* src = S + (int64_t)row * stride + h.first;
-        const bool bad = h.len > M;
-        {   // (A): task (j, n2)
-            const int n2 = t >> 3;
-            fcv v[16];
-#pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) {
-                const int64_t s = (int64_t)(n2 + 64 * n1) * C + c;
-                fcv x = {0.f, 0.f};
-                if (bad) {
-                    x = (fcv){__int_as_float(0x7fc00000), 0.f};
-                } else if (s < h.len) {
-                    const double2 d = src[s];
-                    x = (fcv){(float)(d.x * inv), (float)(d.y * inv)};
-                }
-                v[n1] = x;
-            }
-            fc_dft16<-1>(v);
-            fc_twiddle_pow<16>(v, -W1024 * (float)n2);
-#pragma unroll
-            for (int k1 = 0; k1 < 16; ++k1) sm[e1(k1, n2, j)] = v[k1];
-        }
-        __syncthreads();
-        fcv u[2][8];
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {   // (B): tasks (j, n2a, k1)
-            const int q = t + FC_NT * hh, n2a = (q >> 3) & 7, k1 = q >> 6;
-#pragma unroll
-            for (int n2b = 0; n2b < 8; ++n2b) u[hh][n2b] = sm[e1(k1, n2a + 8 * n2b, j)];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const int q = t + FC_NT * hh, n2a = (q >> 3) & 7, k1 = q >> 6;
-            fc_dft8<-1>(u[hh]);
-            fc_twiddle_pow<8>(u[hh], -W64 * (float)n2a);
-#pragma unroll
-            for (int k2a = 0; k2a < 8; ++k2a) sm[e2(k1, k2a, n2a, j)] = u[hh][k2a];
-        }
-        __syncthreads();
-        int to = t;   // opaque: no store address kept live from (A)
-        __asm__ volatile("" : "+v"(to));
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {   // (C): tasks (j, k2a, k1)
-            const int q = to + FC_NT * hh, k2a = (q >> 3) & 7, k1 = q >> 6;
-            fcv w[8];
-#pragma unroll
-            for (int a = 0; a < 8; ++a) w[a] = sm[e2(k1, k2a, a, j)];
-            fc_dft8<-1>(w);
-#pragma unroll
-            for (int k2b = 0; k2b < 8; ++k2b) {
-                const int fr = k1 + 16 * k2a + 128 * k2b;
-                const uint32_t pp = (uint32_t)c * (uint32_t)fr;   // < C R = M: no reduction
-                float sn, cs;
-                __sincosf(-FC_2PI * ((float)pp * (1.0f / (float)M)), &sn, &cs);
-                y[(int64_t)fr * C + c] = cmulf(w[k2b], (fcv){cs, sn});
-            }
-        }
-    }
-}
-
-// S_w at bin k: the 3-point stencil on S and the correction's difference (neighbours mod nf).
-// S is zero outside the row's support [first, first + len) (cyclic; efd_hann_extent's bounds),
-// so it is read only there: the support is ~40% of test.sh's grid, and the skipped reads were
-// half of the reduction's HBM bytes (the correction C = Y is nonzero everywhere)
-__device__ __forceinline__ double2 hann_sw(const double2* __restrict__ S,
-                                           const float2* __restrict__ Y, int64_t nf, int64_t k,
-                                           double c, int64_t first, int64_t len, int64_t off) {
-    const int64_t kp = k + 1 < nf ? k + 1 : 0, km = k > 0 ? k - 1 : nf - 1;
-    int64_t qp = kp - first, qm = km - first, q0 = k - first;
-    qp += qp < 0 ? nf : 0;
-    qm += qm < 0 ? nf : 0;
-    q0 += q0 < 0 ? nf : 0;
-    const double2 z = make_double2(0.0, 0.0);
-    const double2 s = q0 < len ? S[k] : z, sp = qp < len ? S[kp] : z, sm = qm < len ? S[km] : z;
-    const float2 cp = Y[qp + off], cm = Y[qm + off];
-    return make_double2(0.5 * s.x - 0.25 * (sp.x + sm.x) - c * ((double)cp.x - (double)cm.x),
-                        0.5 * s.y - 0.25 * (sp.y + sm.y) - c * ((double)cp.y - (double)cm.y));
-}
-// h+ = (a + conj b)/2, hx = i (a - conj b)/2 of the windowed spectrum at k (a) and nf-1-k (b)
-__device__ __forceinline__ void hann_pol(const double2* __restrict__ S,
-                                         const float2* __restrict__ Y, int64_t nf, int64_t k,
-                                         double c, int64_t first, int64_t len, int64_t off,
-                                         double2& vp, double2& vc) {
-    const double2 a = hann_sw(S, Y, nf, k, c, first, len, off);
-    const double2 b = hann_sw(S, Y, nf, nf - 1 - k, c, first, len, off);
-    vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
-}
-__global__ void k_hann_polarizations(const double2* __restrict__ S, const float2* __restrict__ Y,
-                                     const uint64_t* __restrict__ info, int64_t m, int64_t nf,
-                                     int64_t k0, double2* __restrict__ hp,
-                                     double2* __restrict__ hc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t k = k0 + i;
-    if (k >= nf) return;
-    const HannRow h = hann_row(info, 0);
-    const double c = h.scale / (4.0 * (double)(nf - 1));
-    double2 vp, vc;
-    hann_pol(S, Y, nf, k, c, h.first, h.len, m - nf, vp, vc);
-    hp[i] = vp;
-    hc[i] = vc;
-}
-// the windowed templates' log-likelihood partials of every row: efd_loglike's terms (d - h w,
-// product rounded then difference) for both channels of every bin [k0, nf). One workgroup per
-// (bin chunk, row): a thread holds one row's sum (70 VGPRs, 7 waves per SIMD: the loads of many
-// waves in flight; the earlier form kept all rows' sums and loads in one thread, 233 VGPRs and
-// 2 waves per SIMD, 0.53 of HBM). The rows of a chunk are consecutive workgroups of one XCD
-// (workgroup b runs on XCD b mod 8), so d and w (48 B per bin, the same for every row) come from
-// HBM once and from that XCD's L2 for the other rows. part[row * nchunk + chunk].
-constexpr int HANN_ROWS_MAX = 16;
-// RPT rows per workgroup (rows = RPT x the row groups; a thread reads its bin's d and w once
-// for all of them: 48 B of the ~176 a bin-row loads from L1/L2). The rows of a chunk's row
-// groups are consecutive workgroups of one XCD as with one row each; every row's partial sums
-// the same bins in the same order, so the output is bitwise that of RPT = 1.
-template <int RPT>
-__global__ __launch_bounds__(256) void k_hann_loglike_partial(
-    const double2* __restrict__ S, int64_t stride, const float2* __restrict__ Y,
-    const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0,
-    const double2* __restrict__ d, const double* __restrict__ w, int rows, int nchunk,
-    double* __restrict__ part) {
-#pragma clang fp contract(off)
-    const int ngr = rows / RPT;
-    const int j = (int)(blockIdx.x >> 3);
-    const int r0 = (j % ngr) * RPT, chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
-    double c[RPT];
-    int64_t first[RPT], len[RPT];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        const HannRow h = hann_row(info, r0 + q);
-        c[q] = h.scale / (4.0 * (double)(nf - 1));
-        first[q] = h.first;
-        len[q] = h.len;
-    }
-    const int64_t nb = nf - k0;
-    double acc[RPT];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) acc[q] = 0.0;
-    for (int64_t i = (int64_t)chunk * 256 + threadIdx.x; i < nb; i += (int64_t)nchunk * 256) {
-        const double2 d0 = d[i], d1 = d[nb + i];
-        const double w0 = w[i], w1 = w[nb + i];
-#pragma unroll
-        for (int q = 0; q < RPT; ++q) {
-            double2 vp, vc;
-            hann_pol(S + (int64_t)(r0 + q) * stride, Y + (int64_t)(r0 + q) * m, nf, k0 + i, c[q],
-                     first[q], len[q], m - nf, vp, vc);
-            const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
-            const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
-            acc[q] = fma(x0, x0, fma(y0, y0, acc[q]));
-            acc[q] = fma(x1, x1, fma(y1, y1, acc[q]));
-        }
-    }
-    // a butterfly over each wave, then the 4 waves in turn (fixed order)
-    __shared__ double red[RPT][4];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        double a = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPT && chunk < nchunk) {
-        const int q = threadIdx.x;
-        part[(int64_t)(r0 + q) * nchunk + chunk] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
-    }
-}
-
-// ---- Cosine-sum windows (efd_cosw_*; fdutils.CosineWindowConvolution): scipy's symmetric
-// w[n] = sum_j (-1)^j a_j cos(2 pi j n / (nf - 1)), j <= J <= 3 (hamming, blackman, nuttall,
-// blackmanharris). The Hann expansion at the shifts +-j (1 + e), e = 1 / (nf - 1), with the same
-// correction C (the transforms above, unchanged):
-//   S_w[k] = a_0 S[k] + sum_j b_j (S[k+j] + S[k-j]) + sum_j b_j j e (C[k+j] - C[k-j]),
-//   b_j = (-1)^j a_j / 2, indices mod nf.
-// A bin's 2J+1 S and 2J Y neighbours overlap its neighbours' (26 loads a bin pair at J = 3
-// against the Hann kernels' 10), so a workgroup stages its tile's bins and their mirrors, each
-// with a halo of J, in LDS once (S zeroed outside the row's support as hann_sw reads it; Y at
-// hann_sw's index) and every thread takes its neighbours from there.
-struct CoswCoef {
-    double a0;
-    double b[3];   // (-1)^j a_j / 2 for j = 1..3 (0 past J)
-    double g[3];   // b_j j / (nf - 1): times the row's scale, the weight of Y[k+j] - Y[k-j]
-};
-constexpr int COSW_TILE = 256;
-template <int J>
-struct CoswTile {
-    // side 0: bins kb - J + e; side 1: the mirrors, bins nf - kb - COSW_TILE - J + e
-    double2 s[2][COSW_TILE + 2 * J];
-    float2 y[2][COSW_TILE + 2 * J];
-};
-// kb: the tile's first bin. A tile's last bins may lie past nf - 1 (and their mirrors below 0):
-// such places hold 0 and no thread with a bin reads them. nf >= 2J + 1, so one wrap each way
-// brings every neighbour of a bin in [0, nf) back into the grid.
-// A thread fetches place threadIdx.x of both sides, and the first 2J lanes of waves 0 and 1 the
-// halo place COSW_TILE + lane of side 0 and 1: straight-line loads into registers (cosw_fetch),
-// all in flight together, then the LDS stores (cosw_put).
-struct CoswRegs {
-    double2 s[3];
-    float2 y[3];
-};
-__device__ __forceinline__ void cosw_fetch_one(const double2* __restrict__ S,
-                                               const float2* __restrict__ Y, int64_t nf,
-                                               int64_t kk, int64_t first, int64_t len,
-                                               int64_t off, double2& sv, float2& yv) {
-    kk += kk < 0 ? nf : 0;
-    kk -= kk >= nf ? nf : 0;
-    sv = make_double2(0.0, 0.0);
-    yv = make_float2(0.f, 0.f);
-    if (kk >= 0 && kk < nf) {
-        int64_t q = kk - first;
-        q += q < 0 ? nf : 0;
-        if (q < len) sv = S[kk];
-        yv = Y[q + off];
-    }
-}
-template <int J>
-__device__ __forceinline__ void cosw_fetch(CoswRegs& r, const double2* __restrict__ S,
-                                           const float2* __restrict__ Y, int64_t nf, int64_t kb,
-                                           int64_t first, int64_t len, int64_t off) {
-    const int64_t base0 = kb - J, base1 = nf - kb - COSW_TILE - J;
-    const int x = threadIdx.x, hs = x >> 6, hl = x & 63;
-    cosw_fetch_one(S, Y, nf, base0 + x, first, len, off, r.s[0], r.y[0]);
-    cosw_fetch_one(S, Y, nf, base1 + x, first, len, off, r.s[1], r.y[1]);
-    if (hs < 2 && hl < 2 * J)
-        cosw_fetch_one(S, Y, nf, (hs == 0 ? base0 : base1) + COSW_TILE + hl, first, len, off,
-                       r.s[2], r.y[2]);
-}
-template <int J>
-__device__ __forceinline__ void cosw_put(CoswTile<J>& t, const CoswRegs& r) {
-    const int x = threadIdx.x, hs = x >> 6, hl = x & 63;
-    t.s[0][x] = r.s[0];
-    t.y[0][x] = r.y[0];
-    t.s[1][x] = r.s[1];
-    t.y[1][x] = r.y[1];
-    if (hs < 2 && hl < 2 * J) {
-        t.s[hs][COSW_TILE + hl] = r.s[2];
-        t.y[hs][COSW_TILE + hl] = r.y[2];
-    }
-}
-// S_w of the bin staged at place c (g: CoswCoef.g times the row's scale)
-template <int J>
-__device__ __forceinline__ double2 cosw_sw(const double2* s, const float2* y, int c,
-                                           const CoswCoef& cf, const double* g) {
-#pragma clang fp contract(off)
-    const double2 s0 = s[c];
-    double2 v = make_double2(cf.a0 * s0.x, cf.a0 * s0.y);
-#pragma unroll
-    for (int j = 1; j <= J; ++j) {
-        const double2 sp = s[c + j], sm = s[c - j];
-        const float2 yp = y[c + j], ym = y[c - j];
-        v.x = (v.x + cf.b[j - 1] * (sp.x + sm.x)) + g[j - 1] * ((double)yp.x - (double)ym.x);
-        v.y = (v.y + cf.b[j - 1] * (sp.y + sm.y)) + g[j - 1] * ((double)yp.y - (double)ym.y);
-    }
-    return v;
-}
-// hann_pol's split for thread x of a staged tile: bin kb + x (a) and its mirror (b)
-template <int J>
-__device__ __forceinline__ void cosw_pol(const CoswTile<J>& t, int x, const CoswCoef& cf,
-                                         const double* g, double2& vp, double2& vc) {
-    const double2 a = cosw_sw<J>(t.s[0], t.y[0], x + J, cf, g);
-    const double2 b = cosw_sw<J>(t.s[1], t.y[1], COSW_TILE - 1 - x + J, cf, g);
-    vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
-}
-template <int J>
-__global__ __launch_bounds__(COSW_TILE) void k_cosw_polarizations(
-    const double2* __restrict__ S, const float2* __restrict__ Y,
-    const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0, CoswCoef cf,
-    double2* __restrict__ hp, double2* __restrict__ hc) {
-    __shared__ CoswTile<J> t;
-    const int64_t ib = (int64_t)blockIdx.x * COSW_TILE;
-    const HannRow h = hann_row(info, 0);
-    CoswRegs r;
-    cosw_fetch<J>(r, S, Y, nf, k0 + ib, h.first, h.len, m - nf);
-    cosw_put<J>(t, r);
-    __syncthreads();
-    const int64_t i = ib + threadIdx.x;
-    if (k0 + i >= nf) return;
-    double g[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) g[j] = cf.g[j] * h.scale;   // a NaN scale: a NaN row
-    double2 vp, vc;
-    cosw_pol<J>(t, threadIdx.x, cf, g, vp, vc);
-    hp[i] = vp;
-    hc[i] = vc;
-}
-// k_hann_loglike_partial with the general stencil: the same workgroup-to-XCD mapping, row
-// groups, term order and reductions; a row's tile is staged by its workgroup alone and its
-// partial sums the same bins in the same order whatever RPT and the other rows are.
-template <int J, int RPT>
-__global__ __launch_bounds__(COSW_TILE) void k_cosw_loglike_partial(
-    const double2* __restrict__ S, int64_t stride, const float2* __restrict__ Y,
-    const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0, CoswCoef cf,
-    const double2* __restrict__ d, const double* __restrict__ w, int rows, int nchunk,
-    double* __restrict__ part) {
-#pragma clang fp contract(off)
-    __shared__ CoswTile<J> t[RPT];
-    const int ngr = rows / RPT;
-    const int j = (int)(blockIdx.x >> 3);
-    const int r0 = (j % ngr) * RPT, chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
-    double g[RPT][3];
-    int64_t first[RPT], len[RPT];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        const HannRow h = hann_row(info, r0 + q);
-#pragma unroll
-        for (int jj = 0; jj < 3; ++jj) g[q][jj] = cf.g[jj] * h.scale;
-        first[q] = h.first;
-        len[q] = h.len;
-    }
-    const int64_t nb = nf - k0;
-    double acc[RPT];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) acc[q] = 0.0;
-    // (the tile loop is uniform over the workgroup: the barriers sit outside the bin's test)
-    for (int64_t ib = (int64_t)chunk * COSW_TILE; ib < nb; ib += (int64_t)nchunk * COSW_TILE) {
-        // the bin's d and w are asked for ahead of the staging, so that their latency runs
-        // beside the tile's and not after the barrier
-        const int64_t i = ib + threadIdx.x;
-        double2 d0 = make_double2(0.0, 0.0), d1 = d0;
-        double w0 = 0.0, w1 = 0.0;
-        if (i < nb) {
-            d0 = d[i];
-            d1 = d[nb + i];
-            w0 = w[i];
-            w1 = w[nb + i];
-        }
-        CoswRegs r[RPT];
-#pragma unroll
-        for (int q = 0; q < RPT; ++q)
-            cosw_fetch<J>(r[q], S + (int64_t)(r0 + q) * stride, Y + (int64_t)(r0 + q) * m, nf,
-                          k0 + ib, first[q], len[q], m - nf);
-#pragma unroll
-        for (int q = 0; q < RPT; ++q) cosw_put<J>(t[q], r[q]);
-        __syncthreads();
-        if (i < nb) {
-#pragma unroll
-            for (int q = 0; q < RPT; ++q) {
-                double2 vp, vc;
-                cosw_pol<J>(t[q], threadIdx.x, cf, g[q], vp, vc);
-                const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
-                const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
-                acc[q] = fma(x0, x0, fma(y0, y0, acc[q]));
-                acc[q] = fma(x1, x1, fma(y1, y1, acc[q]));
-            }
-        }
-        __syncthreads();
-    }
-    // a butterfly over each wave, then the 4 waves in turn (fixed order)
-    __shared__ double red[RPT][4];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        double a = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPT && chunk < nchunk) {
-        const int q = threadIdx.x;
-        part[(int64_t)(r0 + q) * nchunk + chunk] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
-    }
-}
-
-// (C) with the windowed logL fused in (efd_hann_loglike_local). Per bin the two channels' terms
-// of a bin k and of its mirror k' = nf-1-k combine into one term on each (with the same weight
-// w on both channels, p = d0 - w h+, q = d1 - w hx: |p|^2 + |q|^2 = (|p - iq|^2 + |p + iq|^2)/2,
-// p - iq = (d0 - i d1) - w S_w[k], p + iq = (d0 + i d1) - w conj(S_w[k'])), so the logL is
-//   (1/2) sum_j |dl[j] - wl[j] S_w[j]|^2 over the whole grid
-// with dl[k] = d0 - i d1 (k >= k0), dl[k'] = conj(d0 + i d1), wl = w at both (the caller's
-// layout: fdutils.HannConvolution.local_data; the self-mirror bin kself takes its second term
-// from dl[nf]). Every term is local to its bin, so the inverse column pass reduces them as it
-// produces the correction: the correction array is neither written nor read back.
-// The pipeline's kernel spectrum carries the difference factor 2i sin(2 pi f / m), so the
-// transform yields Dc[s] = Y[s+1] - Y[s-1] directly (no neighbour column needed): valid for
-// s in [m - nf, m - 1) when m >= nf + len, and at s = m - 1 (bin u = nf - 1, whose +1 neighbour
-// wraps to u = 0) Y[m] = Y[0] differs from C(u = 0) = Y[m - nf] by y[0] (K[(-(m-nf)) mod nf] -
-// K[0]) alone (kfix = K[0] - K[(-(m-nf)) mod nf], added back). emit (one row): write
-// dl[j] = wl[j] S_w[j] (and dl[nf] = dl[kself]) instead, the data of an injection made by this
-// same arithmetic (its logL against itself is then exactly 0).
-// Workgroups: 1-D, b -> XCD b mod 8; XCD x takes column blocks [x G/8, (x+1) G/8) and on it the
-// rows of one column block are consecutive, so dl / wl (24 B a bin, the same for every row) come
-// from HBM once and from the XCD's L2 for the other rows. part[row * G + column block], halved.
-// one element of the fused logL: bin offset u >= 0 from the row's first bin, its differenced
-// correction dvf (the transform's output), its prefetched data dv and weight w
-struct HannLl {
-    const double2* Sr;   // the row of S
-    int nfi, first, len;
-    double cc, scale;    // e / 4 times the row's scale (NaN: aliased row); the scale
-    double2 kfix;
-    const double2* dl;
-    int64_t kself, nf;
-    double2* emit;
-};
-__device__ __forceinline__ void hann_ll_elem(const HannLl& x, int u, fcv dvf, double2 dv, double w,
-                                             double& acc) {
-#pragma clang fp contract(off)
-    const double2 z = make_double2(0.0, 0.0);
-    double dx = (double)dvf.x, dy = (double)dvf.y;
-    if (u == x.nfi - 1 && x.len > 0) {   // the +1 neighbour wraps: Y[0] -> C(u = 0)
-        const double inv = 1.0 / x.scale;
-        const double2 s0 = x.Sr[x.first];
-        const double yx = s0.x * inv, yy = s0.y * inv;
-        dx += yx * x.kfix.x - yy * x.kfix.y;
-        dy += yx * x.kfix.y + yy * x.kfix.x;
-    }
-    int k = u + x.first;
-    k -= k >= x.nfi ? x.nfi : 0;
-    const int kp = k + 1 < x.nfi ? k + 1 : 0, km = k > 0 ? k - 1 : x.nfi - 1;
-    const int qp = u + 1 < x.nfi ? u + 1 : 0, qm = u > 0 ? u - 1 : x.nfi - 1;
-    const double2 s = u < x.len ? x.Sr[k] : z, sp = qp < x.len ? x.Sr[kp] : z,
-                  sn = qm < x.len ? x.Sr[km] : z;
-    const double wx = 0.5 * s.x - 0.25 * (sp.x + sn.x) - x.cc * dx;
-    const double wy = 0.5 * s.y - 0.25 * (sp.y + sn.y) - x.cc * dy;
-    if (x.emit != nullptr) {
-        const double2 o = make_double2(wx * w, wy * w);
-        x.emit[k] = o;
-        if (k == x.kself) x.emit[x.nf] = o;
-        return;
-    }
-    const double rx = dv.x - wx * w, ry = dv.y - wy * w;
-    acc = fma(rx, rx, fma(ry, ry, acc));
-    if (k == x.kself) {
-        const double2 d2 = x.dl[x.nf];
-        const double tx = d2.x - wx * w, ty = d2.y - wy * w;
-        acc = fma(tx, tx, fma(ty, ty, acc));
-    }
-}
-// the row's context (hann_row) for hann_ll_elem
-__device__ __forceinline__ HannLl hann_ll_ctx(const double2* S, int64_t stride,
-                                              const uint64_t* info, int row, int64_t M,
-                                              int64_t nf, const double2* dl, int64_t kself,
-                                              double2 kfix, double2* emit) {
-    const HannRow h = hann_row(info, row);
-    HannLl x;
-    x.Sr = S + (int64_t)row * stride;
-    x.nfi = (int)nf;
-    x.first = (int)h.first;
-    x.len = (int)h.len;
-    // a support longer than m - nf leaves Y[m - nf - 1] aliased: the row's logL is NaN
-    x.cc = h.len > M - nf ? __longlong_as_double(0x7ff8000000000000ll)
-                          : h.scale / (4.0 * (double)(nf - 1));
-    x.scale = h.scale;
-    x.kfix = kfix;
-    x.dl = dl;
-    x.kself = kself;
-    x.nf = nf;
-    x.emit = emit;
-    return x;
-}
-// the workgroup's partial (wave butterflies, then the waves in order): part[row G + cb], halved
-__device__ __forceinline__ void hann_ll_store(double acc, double* red, double* part, int64_t at) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) t += red[wv];
-        part[at] = 0.5 * t;
-    }
-}
-template <int R, int C>
-__global__ __launch_bounds__(FC_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
-void k_fc_cols_ll(const double2* __restrict__ S, int64_t stride, const uint64_t* __restrict__ info,
-                  const float2* __restrict__ Yv, int64_t nf, const double2* __restrict__ dl,
-                  const double* __restrict__ wl, int64_t kself, double2 kfix, int rows,
-                  double* __restrict__ part, double2* __restrict__ emit) {
-#pragma clang fp contract(off)
-    constexpr int NCOL = FcCols<R>::NCOL, LOGL = FcCols<R>::LOGL;
-    constexpr int64_t M = (int64_t)R * C;
-    constexpr int NQ = R * NCOL / FC_NT;
-    static_assert(R * NCOL % FC_NT == 0, "whole rounds of elements per thread");
-    constexpr int G = C / NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
-    __shared__ fcv sm[R * FcColIdx<NCOL>::STRIDE];
-    __shared__ double red[FC_NT / 64];
-    const fcv* Y = reinterpret_cast<const fcv*>(Yv);
-    const FcColIdx<NCOL> idx;
-    const int q8 = (int)(blockIdx.x >> 3);
-    const int row = q8 % rows, cb = (int)(blockIdx.x & 7) * (G / 8) + q8 / rows;
-    const int c0 = cb * NCOL;
-    const fcv* y = Y + (int64_t)row * M;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int i = threadIdx.x + q * FC_NT;
-        const int e = i / NCOL, j = i % NCOL;
-        const uint32_t p = (uint32_t)(c0 + j) * (uint32_t)e;
-        float sn, cs;
-        __sincosf(FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-        sm[idx(j, e)] = cmulf(y[(int64_t)e * C + c0 + j], (fcv){cs, sn});
-    }
-    __syncthreads();
-    fc_fft<1, R, LOGL>(sm, idx);
-    const HannLl x = hann_ll_ctx(S, stride, info, row, M, nf, dl, kself, kfix, emit);
-    const int offi = (int)(M - nf);
-    // the elements' data (dl, wl) requested QH at a time before any of them is used: QH loads
-    // of each in flight per thread (the epilogue is latency-bound otherwise, one round trip per
-    // few elements; all 16 at once spill past 128 VGPRs); indices fit 32 bits (nf < 2^31,
-    // m <= 2^25)
-    constexpr int QH = NQ >= 8 ? 8 : NQ;
-    static_assert(NQ % QH == 0, "whole rounds of prefetched elements");
-    double acc = 0.0;
-#pragma unroll
-    for (int q0 = 0; q0 < NQ; q0 += QH) {
-        double2 dv[QH];
-        double wv[QH];
-#pragma unroll
-        for (int t = 0; t < QH; ++t) {
-            const int i = threadIdx.x + (q0 + t) * FC_NT;
-            const int u = (i / NCOL) * C + c0 + i % NCOL - offi;
-            int k = u + x.first;
-            k -= k >= x.nfi ? x.nfi : 0;
-            dv[t] = make_double2(0.0, 0.0);
-            wv[t] = 0.0;
-            if (u >= 0) {
-                wv[t] = wl[k];
-                if (emit == nullptr) dv[t] = dl[k];
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < QH; ++t) {
-            const int i = threadIdx.x + (q0 + t) * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;
-            const int u = e * C + c0 + j - offi;   // the correction's bin offset from first
-            if (u >= 0) hann_ll_elem(x, u, sm[idx(j, e)], dv[t], wv[t], acc);
-        }
-    }
-    if (emit != nullptr) return;
-    hann_ll_store(acc, red, part, (int64_t)row * G + cb);
-}
-
-// fused log-likelihood partials: one workgroup per chunk, then a second pass
-__global__ void k_loglike_partial(const double2* __restrict__ h, const double2* __restrict__ d,
-                                  const double* __restrict__ w, int64_t total,
-                                  double* __restrict__ part) {
-    // d - h*w rounded like the reference's numpy (product rounded, then difference): no FMA
-    // contraction here, so a template equal to the injection gives exactly 0
-#pragma clang fp contract(off)
-    __shared__ double red[256];
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const double2 dv = d[i];
-        const double ww = w[i];
-        double rr = dv.x, ri = dv.y;
-        if (h) {
-            const double2 hv = h[i];
-            rr -= hv.x * ww;
-            ri -= hv.y * ww;
-        }
-        acc = fma(rr, rr, fma(ri, ri, acc));
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-
-// (one row per workgroup: partials part[row * np ...], out[row])
-__global__ void k_loglike_final(const double* __restrict__ part, int np, double* __restrict__ out) {
-    part += (int64_t)blockIdx.x * np;
-    out += blockIdx.x;
-    __shared__ double red[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) acc += part[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = -0.5 * 4.0 * red[0];
-}
-
-// ---- DFT of a TD template h = h+ - i hx into its two channels (efd_td_split*). Z = fft(w h)
-// in natural order; the Hermitian split (k_polarizations' algebra, on the DFT's own pairing
-// k <-> (n - k) mod n) gives both real series' transforms over the bins k < nb = ceil(n / 2),
-// which are the drivers' positive-frequency bins (fftshift, then frequency >= 0):
-//   H+ = (Z[k] + conj Z[n-k]) / 2,  Hx = i (Z[k] - conj Z[n-k]) / 2,  each times gain (= dt).
-__device__ __forceinline__ void td_split_pair(const double2 a, const double2 b, double gain,
-                                              double2& hp, double2& hc) {
-#pragma clang fp contract(off)
-    hp = make_double2(gain * (0.5 * (a.x + b.x)), gain * (0.5 * (a.y - b.y)));
-    hc = make_double2(gain * (-0.5 * (a.y + b.y)), gain * (0.5 * (a.x - b.x)));
-}
-
-__global__ __launch_bounds__(256) void k_td_split(const double2* __restrict__ Z, int64_t stride,
-                                                  int64_t n, int64_t nb, double gain,
-                                                  const uint8_t* __restrict__ keep,
-                                                  double2* __restrict__ out, int64_t out_stride) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= nb) return;
-    const double2* z = Z + (int64_t)blockIdx.y * stride;
-    double2* o = out + (int64_t)blockIdx.y * out_stride;
-    double2 hp = make_double2(0.0, 0.0), hc = hp;
-    if (keep == nullptr || keep[k] != 0) td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
-    o[k] = hp;
-    o[nb + k] = hc;
-}
-
-// logL partials of the split's channels against d ([2][nb]) and w ([2][nb]), the template kept
-// in registers: workgroup (c, r) takes bins [c chunk, (c + 1) chunk) of row r, an ascending
-// stream Z[k] and a descending one Z[n - k]; the row is the slow grid dimension, so the rows'
-// workgroups of one chunk follow each other on one XCD and find d and w in its cache. Partials
-// at part[r gridDim.x + c] (k_loglike_final's layout).
-__global__ __launch_bounds__(256) void k_td_split_loglike(
-    const double2* __restrict__ Z, int64_t stride, int64_t n, int64_t nb, int64_t chunk,
-    double gain, const double2* __restrict__ d, const double* __restrict__ w,
-    double* __restrict__ part) {
-    // d - h w rounded as k_loglike_partial does (product, then difference)
-#pragma clang fp contract(off)
-    __shared__ double red[256];
-    const double2* z = Z + (int64_t)blockIdx.y * stride;
-    const int64_t k0 = (int64_t)blockIdx.x * chunk;
-    const int64_t k1 = min(nb, k0 + chunk);
-    double acc = 0.0;
-    for (int64_t k = k0 + threadIdx.x; k < k1; k += 256) {
-        double2 hp, hc;
-        td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
-        const double2 d0 = d[k], d1 = d[nb + k];
-        const double w0 = w[k], w1 = w[nb + k];
-        const double ar = d0.x - hp.x * w0, ai = d0.y - hp.y * w0;
-        const double br = d1.x - hc.x * w1, bi = d1.y - hc.y * w1;
-        acc = fma(ar, ar, fma(ai, ai, acc));
-        acc = fma(br, br, fma(bi, bi, acc));
-    }
-    // even n: the Nyquist bin belongs to neither channel's kept bins; a NaN there still
-    // poisons the row, as one anywhere else does through the terms above
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
-        const double2 v = z[n / 2];
-        if (v.x != v.x || v.y != v.y) acc = v.x + v.y;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
-}
-
-// noise-weighted inner product partials: sum conj(a) b w (complex), one pair per workgroup
-__global__ void k_inner_partial(const double2* __restrict__ a, const double2* __restrict__ b,
-                                const double* __restrict__ w, int64_t total,
-                                double2* __restrict__ part) {
-    __shared__ double rre[256], rim[256];
-    double accr = 0.0, acci = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const double2 av = a[i], bv = b[i];
-        const double ww = w ? w[i] : 1.0;
-        // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
-        accr = fma(ww, fma(av.x, bv.x, av.y * bv.y), accr);
-        acci = fma(ww, fma(av.x, bv.y, -av.y * bv.x), acci);
-    }
-    rre[threadIdx.x] = accr;
-    rim[threadIdx.x] = acci;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            rre[threadIdx.x] += rre[threadIdx.x + s];
-            rim[threadIdx.x] += rim[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(rre[0], rim[0]);
-}
-
-__global__ void k_inner_final(const double2* __restrict__ part, int np, double scale,
-                              double2* __restrict__ out) {
-    __shared__ double rre[256], rim[256];
-    double accr = 0.0, acci = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) {
-        accr += part[i].x;
-        acci += part[i].y;
-    }
-    rre[threadIdx.x] = accr;
-    rim[threadIdx.x] = acci;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            rre[threadIdx.x] += rre[threadIdx.x + s];
-            rim[threadIdx.x] += rim[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = make_double2(scale * rre[0], scale * rim[0]);
-}
-
-// ---- weighted Gram matrix of stencil-combined rows (efd_fisher_gram) ----------------------
-// One pass over h and w. A workgroup of 4 waves stages FG_CHUNK elements at a time: thread t
-// forms D_i[e] = sum_s coef[i][s] h[i npoint + s][e] for its element (the stencil is applied per
-// element, before any product: the Gram matrix of the raw rows combined afterwards loses the
-// digits the differences cancel) and writes D_i and w to LDS, and D_i to dh. Then each wave
-// takes 4 x 4 tiles (i, j) of the upper triangle's tile grid, its lanes run over the chunk's
-// elements (lane l: l, l + 64, l + 128, l + 192; consecutive 16-byte LDS slots per read) and
-// keep the tile's 16 sums in registers across the workgroup's chunks.
-// What makes gram[i][j] a function of rows i, j, w and nelem alone (the subset promise):
-//   - chunk c goes to workgroup c mod gridDim.x, and gridDim.x is a function of nelem;
-//   - every pair sees the same element -> lane map, the same butterfly over the lanes and the
-//     same final order over the workgroups, whichever wave and tile hold it;
-//   - a term is fma(w, fma(ar, br, ai * bi), acc): symmetric in (a, b), so (j, i) of a
-//     reordered call rounds as (i, j) does; contraction is off, the fmas are the written ones.
-constexpr int FG_THREADS = 256;
-constexpr int FG_CHUNK = 256;
-constexpr int FG_MAXB = 1024;   // workgroups (4 per CU); EFD_FISHER_SCRATCH = FG_MAXB * 136
-
-struct fg_coef {
-    double c[EFD_FISHER_MAX_PARAMS * 4];
-};
-
-__host__ __device__ inline int fg_pair_index(int i, int j, int P) {   // i <= j, row-major upper
-    return i * P - (i * (i - 1)) / 2 + (j - i);
-}
-
-// TP: tile rows = ceil(nparam / 4); the upper triangle has TP (TP + 1) / 2 tiles, wave v takes
-// tiles v, v + 4, v + 8
-template <int NPOINT, int TP>
-__global__ __launch_bounds__(FG_THREADS) void k_fisher_partial(
-    const double2* __restrict__ h, int64_t row_stride, int nparam, fg_coef cf,
-    const double* __restrict__ w, int64_t nelem, double2* __restrict__ dh,
-    double* __restrict__ part) {
-#pragma clang fp contract(off)
-    constexpr int NTILE = TP * (TP + 1) / 2;
-    constexpr int MAXT = (NTILE + 3) / 4;
-    __shared__ double2 D[4 * TP * FG_CHUNK];
-    __shared__ double wl[FG_CHUNK];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // rows nparam .. 4 TP - 1 pad the last tile row: zero, written once
-    for (int r = nparam; r < 4 * TP; ++r) D[r * FG_CHUNK + tid] = make_double2(0.0, 0.0);
-    int ti[MAXT], tj[MAXT];
-#pragma unroll
-    for (int k = 0; k < MAXT; ++k) {
-        int t = wv + 4 * k, I = 0;
-        while (I < TP - 1 && t >= TP - I) {   // tile row I holds TP - I tiles (J = I .. TP-1)
-            t -= TP - I;
-            ++I;
-        }
-        ti[k] = I;
-        tj[k] = I + t;   // >= TP: this wave has no k-th tile
-    }
-    double acc[MAXT][16];
-#pragma unroll
-    for (int k = 0; k < MAXT; ++k)
-#pragma unroll
-        for (int p = 0; p < 16; ++p) acc[k][p] = 0.0;
-
-    const int64_t nchunk = (nelem + FG_CHUNK - 1) / FG_CHUNK;
-    for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
-        const int64_t e = c * FG_CHUNK + tid;
-        const bool live = e < nelem;
-        wl[tid] = live ? (w ? w[e] : 1.0) : 0.0;
-        for (int i = 0; i < nparam; ++i) {
-            double dr = 0.0, di = 0.0;
-            if (live) {
-                const double2* r = h + row_stride * ((int64_t)i * NPOINT) + e;
-                double2 v[NPOINT];
-#pragma unroll
-                for (int s = 0; s < NPOINT; ++s) v[s] = r[row_stride * s];
-                const double c0 = cf.c[i * NPOINT];
-                dr = c0 * v[0].x;
-                di = c0 * v[0].y;
-#pragma unroll
-                for (int s = 1; s < NPOINT; ++s) {
-                    const double cs = cf.c[i * NPOINT + s];
-                    dr = fma(cs, v[s].x, dr);
-                    di = fma(cs, v[s].y, di);
-                }
-                if (dh) dh[(int64_t)i * nelem + e] = make_double2(dr, di);
-            }
-            D[i * FG_CHUNK + tid] = make_double2(dr, di);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < MAXT; ++k) {
-            if (tj[k] >= TP) continue;
-            const double2* A = D + 4 * ti[k] * FG_CHUNK;
-            const double2* B = D + 4 * tj[k] * FG_CHUNK;
-#pragma unroll
-            for (int q = 0; q < FG_CHUNK / 64; ++q) {
-                const int x = lane + 64 * q;
-                const double ww = wl[x];
-                double2 a[4], b[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    a[r] = A[r * FG_CHUNK + x];
-                    b[r] = B[r * FG_CHUNK + x];
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-                        acc[k][4 * r + s] = fma(ww, fma(a[r].x, b[s].x, a[r].y * b[s].y),
-                                                acc[k][4 * r + s]);
-            }
-        }
-        __syncthreads();
-    }
-    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
-    const int npair = nparam * (nparam + 1) / 2;
-#pragma unroll
-    for (int k = 0; k < MAXT; ++k) {
-        if (tj[k] >= TP) continue;
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {
-            double v = acc[k][p];
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-            const int gi = 4 * ti[k] + (p >> 2), gj = 4 * tj[k] + (p & 3);
-            if (lane == 0 && gi <= gj && gj < nparam)
-                part[(int64_t)blockIdx.x * npair + fg_pair_index(gi, gj, nparam)] = v;
-        }
-    }
-}
-
-// one workgroup per pair: the workgroups' partials in a fixed order, mirrored into both halves
-__global__ void k_fisher_final(const double* __restrict__ part, int nb, int nparam,
-                               double* __restrict__ gram) {
-    __shared__ double red[256];
-    const int npair = nparam * (nparam + 1) / 2;
-    const int p = blockIdx.x;
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[(int64_t)b * npair + p];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        int i = 0, q = p;
-        while (q >= nparam - i) {
-            q -= nparam - i;
-            ++i;
-        }
-        const int j = i + q;
-        const double g = 4.0 * red[0];
-        gram[i * nparam + j] = g;
-        gram[j * nparam + i] = g;
-    }
-}
-
-template <int NPOINT>
-void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_stride, int nparam,
-               const fg_coef& cf, const double* w, int64_t nelem, double2* dh, double* part) {
-    switch (tp) {
-        case 1:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 1>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        case 2:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 2>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        case 3:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 3>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        default:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 4>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-    }
-}
-
 }  // namespace
 
 // ========================================================================================
@@ -6710,56 +5122,6 @@ int efd_td_modesum_windowed(const efd_td_args* a, const double* window, void* wo
     return td_modesum_run(a, window, workspace, workspace_bytes, stream);
 }
 
-// the chunks of efd_td_split_loglike for n points: a function of n alone (whole rounds of the
-// 8 XCDs once there are that many), each a multiple of 256 bins
-static int td_split_chunks(int64_t nb, int64_t* chunk) {
-    int64_t np = std::min<int64_t>(EFD_TD_SPLIT_SCRATCH, (nb + 1023) / 1024);
-    if (np > 8) np -= np % 8;
-    int64_t c = (nb + np - 1) / np;
-    c = (c + 255) / 256 * 256;
-    *chunk = c;
-    return (int)((nb + c - 1) / c);
-}
-
-int efd_td_split(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
-                 const uint8_t* keep, double* out, int64_t out_stride, void* stream) {
-    if (!Z || !out) return fail(EFD_ERR_ARG, "efd_td_split: NULL Z or out");
-    if (n < 1 || n > ((int64_t)1 << 40)) return fail(EFD_ERR_ARG, "efd_td_split: n out of range");
-    if (rows < 1) return fail(EFD_ERR_ARG, "efd_td_split: rows < 1");
-    const int64_t nb = (n + 1) / 2;
-    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split: stride < n");
-    if (out_stride < 2 * nb) return fail(EFD_ERR_ARG, "efd_td_split: out_stride < 2 nb");
-    const int64_t blocks = (nb + 255) / 256;
-    if (blocks > 0x7fffffffLL || rows > 65535)
-        return fail(EFD_ERR_ARG, "efd_td_split: too many bins or rows");
-    hipLaunchKernelGGL(k_td_split, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0,
-                       (hipStream_t)stream, (const double2*)Z, stride, n, nb, gain, keep,
-                       (double2*)out, out_stride);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
-                         const double* d, const double* w, double* out, double* scratch,
-                         void* stream) {
-    if (!Z || !d || !w || !out || !scratch)
-        return fail(EFD_ERR_ARG, "efd_td_split_loglike: NULL Z, d, w, out or scratch");
-    if (n < 1 || n > ((int64_t)1 << 40))
-        return fail(EFD_ERR_ARG, "efd_td_split_loglike: n out of range");
-    if (rows < 1 || rows > 65535) return fail(EFD_ERR_ARG, "efd_td_split_loglike: rows out of range");
-    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split_loglike: stride < n");
-    const int64_t nb = (n + 1) / 2;
-    int64_t chunk = 0;
-    const int np = td_split_chunks(nb, &chunk);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_td_split_loglike, dim3((unsigned)np, (unsigned)rows), dim3(256), 0, st,
-                       (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)d, w, scratch);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
 int efd_upload(void* dst, const void* src, size_t bytes, void* stream) {
     if (bytes == 0) return EFD_OK;
     if (!dst || !src) return fail(EFD_ERR_ARG, "efd_upload: NULL pointer");
@@ -6798,376 +5160,6 @@ int efd_stream_order(void* src, void* const* dst, int32_t count) {
         if (dst[i] != src) e = hipStreamWaitEvent((hipStream_t)dst[i], ev[dev], 0);
     if (dev != cur) HIP_TRY(hipSetDevice(cur));
     HIP_TRY(e);
-    return EFD_OK;
-}
-
-int efd_polarizations(const double* S, int64_t nf, int64_t k0, double* hp, double* hc,
-                      void* stream) {
-    if (!S || !hp || !hc || nf <= 0 || k0 < 0 || k0 > nf)
-        return fail(EFD_ERR_ARG, "efd_polarizations: bad arguments");
-    const int64_t cnt = nf - k0;
-    if (cnt == 0) return EFD_OK;
-    const int threads = 256;
-    const int64_t blocks = (cnt + threads - 1) / threads;
-    hipLaunchKernelGGL(k_polarizations, dim3((unsigned)blocks), dim3(threads), 0,
-                       (hipStream_t)stream, (const double2*)S, nf, k0, (double2*)hp, (double2*)hc);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-static bool hann_rows_ok(const char* fn, const void* S, int64_t stride, int64_t nf,
-                         int32_t rows) {
-    if (!S || nf < 3 || rows < 1 || rows > 65535 || stride < nf) {
-        fail(EFD_ERR_ARG, std::string(fn) + ": bad arguments");
-        return false;
-    }
-    return true;
-}
-int efd_hann_extent(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                    const int32_t* lanes, uint64_t* info, void* stream) {
-    if (!hann_rows_ok("efd_hann_extent", S, stride, nf, rows) || !info)
-        return fail(EFD_ERR_ARG, "efd_hann_extent: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_hann_info_init, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, info,
-                       rows);
-    HIP_TRY(hipGetLastError());
-    // (with lane ranges the rows' supports are a fraction of the grid: fewer workgroups; each
-    // block's 3 atomics on its row's words serialise, so the grid stays small -- 512 blocks a
-    // row took 94 against 44 us for 32, r05z8 -- and the loop is unrolled for loads in flight)
-    const int64_t cap = lanes ? std::max(16, 512 / rows) : std::max(64, 1024 / rows);
-    const int64_t blocks = std::min<int64_t>(cap, (nf + 255) / 256);
-    hipLaunchKernelGGL(k_hann_extent, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, st,
-                       (const double2*)S, stride, nf, lanes, info);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-int efd_hann_stage(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                   const uint64_t* info, int64_t m, float* Y, void* stream) {
-    if (!hann_rows_ok("efd_hann_stage", S, stride, nf, rows) || !info || !Y || m < nf)
-        return fail(EFD_ERR_ARG, "efd_hann_stage: bad arguments");
-    const int64_t blocks = std::min<int64_t>(4096, (m + 255) / 256);
-    hipLaunchKernelGGL(k_hann_stage, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0,
-                       (hipStream_t)stream, (const double2*)S, stride, info, m, (float2*)Y);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-// the four-step split's row length C for a transform length m (the lag kernel's spectrum is
-// laid out [f_r][f_c], R = m / C): 16384 at m = 2^24 (1024 x 16384: the column kernels read
-// 128 B segments, r05z; the 2048 x 8192 split measured 1.08 against 0.73 ms of column passes and
-// was deleted in round 6), else 8192
-int efd_hann_four_step_cols(int64_t m) {
-    return m == ((int64_t)1 << 24) ? FC_C16 : FC_C;
-}
-// the four-step pipeline for power-of-two m in [2^21, 2^25]: forward columns (staging folded
-// in) and rows (the kernel spectrum kfp between the row transforms), then either the inverse
-// columns (Y = the correction, efd_hann_convolve) or the inverse columns with the windowed logL
-// reduced in place (ll != nullptr: efd_hann_loglike_local)
-}  // extern "C"
-struct HannLocal {
-    const double2* dl;
-    const double* wl;
-    int64_t kself;
-    double2 kfix;
-    double* part;
-    double2* emit;
-};
-template <int RR, int CC>
-static int hann_pipeline(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                         const uint64_t* info, const float* kfp, float* Y, const HannLocal* ll,
-                         hipStream_t st) {
-    constexpr int NC = FcCols<RR>::NCOL;
-    constexpr int64_t M = (int64_t)RR * CC;
-    float2* y = (float2*)Y;
-    if constexpr (CC == FC_C16) {
-        static_assert(RR == FCD_R && NC == FCD_NCOL, "1024 x 16384 split");
-        hipLaunchKernelGGL(k_fc_cols1024, dim3(CC / NC, (unsigned)rows), dim3(FC_NT), 0, st,
-                           (const double2*)S, stride, info, y);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_fc_rows16k_h, dim3(RR * (unsigned)rows), dim3(FC_NT), 0, st,
-                           (const float2*)kfp, M, (int)rows, y);
-    } else {
-        hipLaunchKernelGGL((k_fc_cols<true, RR, CC>), dim3(CC / NC, (unsigned)rows), dim3(FC_NT),
-                           0, st, (const double2*)S, stride, info, y);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_fc_rows, dim3(RR * (unsigned)rows), dim3(FR_NT), 0, st,
-                           (const float2*)kfp, M, (int)rows, y);
-    }
-    HIP_TRY(hipGetLastError());
-    if (ll == nullptr) {
-        hipLaunchKernelGGL((k_fc_cols<false, RR, CC>), dim3(CC / NC, (unsigned)rows),
-                           dim3(FC_NT), 0, st, (const double2*)nullptr, (int64_t)0,
-                           (const uint64_t*)nullptr, y);
-    } else {
-        hipLaunchKernelGGL((k_fc_cols_ll<RR, CC>), dim3((CC / NC) * (unsigned)rows), dim3(FC_NT),
-                           0, st, (const double2*)S, stride, info, (const float2*)y, nf, ll->dl,
-                           ll->wl, ll->kself, ll->kfix, (int)rows, ll->part, ll->emit);
-    }
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-static int hann_pipeline_m(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                           const uint64_t* info, int64_t m, const float* kfp, float* Y,
-                           const HannLocal* ll, hipStream_t st) {
-    if (m == ((int64_t)1 << 24))
-        return hann_pipeline<(1 << 24) / FC_C16, FC_C16>(S, stride, nf, rows, info, kfp, Y, ll, st);
-    switch (m / FC_C) {   // R = 2048 is m = 2^24, the 1024 x 16384 split above
-        case 256: return hann_pipeline<256, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 512: return hann_pipeline<512, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 1024: return hann_pipeline<1024, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 4096: return hann_pipeline<4096, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        default: return fail(EFD_ERR_ARG, "efd_hann_convolve: no four-step split for this m");
-    }
-}
-extern "C" {
-static bool hann_four_step_m(int64_t m, int64_t nf) {
-    return m >= nf && m >= ((int64_t)1 << 21) && m <= ((int64_t)1 << 25) && (m & (m - 1)) == 0;
-}
-int efd_hann_convolve(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                      const uint64_t* info, int64_t m, const float* kfp, float* Y, void* stream) {
-    if (!hann_rows_ok("efd_hann_convolve", S, stride, nf, rows) || !info || !kfp || !Y ||
-        !hann_four_step_m(m, nf))
-        return fail(EFD_ERR_ARG, "efd_hann_convolve: bad arguments (m: a power of two in "
-                                 "[2^21, 2^25], >= nf)");
-    return hann_pipeline_m(S, stride, nf, rows, info, m, kfp, Y, nullptr, (hipStream_t)stream);
-}
-int efd_hann_loglike_local_partials(int64_t m) {
-    if (m == ((int64_t)1 << 24)) return FC_C16 / FcCols<(1 << 24) / FC_C16>::NCOL;
-    switch (m / FC_C) {
-        case 256: return FC_C / FcCols<256>::NCOL;
-        case 512: return FC_C / FcCols<512>::NCOL;
-        case 1024: return FC_C / FcCols<1024>::NCOL;
-        case 4096: return FC_C / FcCols<4096>::NCOL;
-        default: return 0;
-    }
-}
-int efd_hann_loglike_local(const double* S, int64_t stride, int64_t nf, int32_t rows,
-                           const uint64_t* info, int64_t m, const float* kfd, float* Y,
-                           const double* dl, const double* wl, int64_t kself, double* out,
-                           double* scratch, double* emit, void* stream) {
-    const int np = hann_four_step_m(m, nf) ? efd_hann_loglike_local_partials(m) : 0;
-    if (!hann_rows_ok("efd_hann_loglike_local", S, stride, nf, rows) || !info || !kfd || !Y ||
-        !wl || np == 0 || kself < -1 || kself >= nf ||
-        (emit ? rows != 1 : (!dl || !out || !scratch || rows > HANN_ROWS_MAX)))
-        return fail(EFD_ERR_ARG, "efd_hann_loglike_local: bad arguments (m: a power of two in "
-                                 "[2^21, 2^25], >= nf; rows <= 16, or 1 with emit)");
-    // kfix = K[0] - K[(-(m - nf)) mod nf], K[j] = -i pi/nf + (pi/nf) cot(pi j/nf), K[0] = i pi
-    // (nf - 1)/nf (fdutils.HannConvolution.kernel_spectrum's lag kernel)
-    const double pn = M_PI / (double)nf;
-    const int64_t jw = ((-(m - nf)) % nf + nf) % nf;
-    double2 kfix = make_double2(0.0, pn * (double)(nf - 1));
-    if (jw != 0) {
-        kfix.x -= pn / std::tan(pn * (double)jw);
-        kfix.y += pn;
-    } else {
-        kfix = make_double2(0.0, 0.0);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const HannLocal ll{(const double2*)dl, wl, kself, kfix, scratch, (double2*)emit};
-    const int rc = hann_pipeline_m(S, stride, nf, rows, info, m, kfd, Y, &ll, st);
-    if (rc != EFD_OK || emit) return rc;
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-int efd_hann_polarizations(const double* S, const float* Y, const uint64_t* info, int64_t m,
-                           int64_t nf, int64_t k0, double* hp, double* hc, void* stream) {
-    if (!S || !Y || !info || !hp || !hc || nf < 3 || m < nf || k0 < 0 || k0 > nf)
-        return fail(EFD_ERR_ARG, "efd_hann_polarizations: bad arguments");
-    const int64_t cnt = nf - k0;
-    if (cnt == 0) return EFD_OK;
-    const int threads = 256;
-    const int64_t blocks = (cnt + threads - 1) / threads;
-    hipLaunchKernelGGL(k_hann_polarizations, dim3((unsigned)blocks), dim3(threads), 0,
-                       (hipStream_t)stream, (const double2*)S, (const float2*)Y, info, m, nf, k0,
-                       (double2*)hp, (double2*)hc);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-int efd_hann_loglike(const double* S, int64_t stride, const float* Y, const uint64_t* info,
-                     int64_t m, int32_t rows, int64_t nf, int64_t k0, const double* d,
-                     const double* w, double* out, double* scratch, void* stream) {
-    if (!hann_rows_ok("efd_hann_loglike", S, stride, nf, rows) || !Y || !info || !d || !w ||
-        !out || !scratch || m < nf || k0 < 0 || k0 >= nf || rows > HANN_ROWS_MAX)
-        return fail(EFD_ERR_ARG, "efd_hann_loglike: bad arguments (rows <= 16)");
-    const int64_t nb = nf - k0;
-    const int threads = 256;
-    // chunks: a multiple of 8 (one per XCD in turn), at most EFD_LOGLIKE_SCRATCH per row
-    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH,
-                                          ((nb + threads - 1) / threads + 7) / 8 * 8);
-    hipStream_t st = (hipStream_t)stream;
-    static_assert(EFD_LOGLIKE_SCRATCH % 8 == 0, "chunks: whole rounds of the 8 XCDs");
-    // two rows a workgroup when the rows pair up (d and w read once for both: 362 -> 318 us,
-    // r05zr; an odd row count takes one row a workgroup)
-    const int rpt = (rows % 2 == 0) ? 2 : 1;
-    hipLaunchKernelGGL(rpt == 2 ? k_hann_loglike_partial<2> : k_hann_loglike_partial<1>,
-                       dim3((unsigned)(np * (rows / rpt))), dim3(threads), 0, st,
-                       (const double2*)S, stride, (const float2*)Y, info, m, nf, k0,
-                       (const double2*)d, w, (int)rows, np, scratch);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-// the stencil's weights from the window's coefficients a_0..a_J (host doubles)
-static bool cosw_coef(const double* a, int32_t nterm, int64_t nf, CoswCoef& cf) {
-    if (!a || nterm < 2 || nterm > 4 || nf < 2 * (int64_t)(nterm - 1) + 1) return false;
-    cf.a0 = a[0];
-    for (int j = 1; j <= 3; ++j) {
-        cf.b[j - 1] = j < nterm ? ((j & 1) ? -0.5 : 0.5) * a[j] : 0.0;
-        cf.g[j - 1] = cf.b[j - 1] * (double)j / (double)(nf - 1);
-    }
-    return true;
-}
-}  // extern "C"
-template <int J>
-static void cosw_launch_pol(int64_t blocks, hipStream_t st, const double* S, const float* Y,
-                            const uint64_t* info, int64_t m, int64_t nf, int64_t k0,
-                            const CoswCoef& cf, double* hp, double* hc) {
-    hipLaunchKernelGGL(k_cosw_polarizations<J>, dim3((unsigned)blocks), dim3(COSW_TILE), 0, st,
-                       (const double2*)S, (const float2*)Y, info, m, nf, k0, cf, (double2*)hp,
-                       (double2*)hc);
-}
-template <int J>
-static void cosw_launch_ll(int rpt, int np, hipStream_t st, const double* S, int64_t stride,
-                           const float* Y, const uint64_t* info, int64_t m, int32_t rows,
-                           int64_t nf, int64_t k0, const CoswCoef& cf, const double* d,
-                           const double* w, double* scratch) {
-    hipLaunchKernelGGL((rpt == 2 ? k_cosw_loglike_partial<J, 2> : k_cosw_loglike_partial<J, 1>),
-                       dim3((unsigned)(np * (rows / rpt))), dim3(COSW_TILE), 0, st,
-                       (const double2*)S, stride, (const float2*)Y, info, m, nf, k0, cf,
-                       (const double2*)d, w, (int)rows, np, scratch);
-}
-extern "C" {
-int efd_cosw_polarizations(const double* S, const float* Y, const uint64_t* info, int64_t m,
-                           int64_t nf, int64_t k0, const double* a, int32_t nterm, double* hp,
-                           double* hc, void* stream) {
-    CoswCoef cf;
-    if (!S || !Y || !info || !hp || !hc || !cosw_coef(a, nterm, nf, cf) || m < nf || k0 < 0 ||
-        k0 > nf)
-        return fail(EFD_ERR_ARG, "efd_cosw_polarizations: bad arguments (2 <= nterm <= 4, "
-                                 "nf >= 2 (nterm - 1) + 1)");
-    const int64_t cnt = nf - k0;
-    if (cnt == 0) return EFD_OK;
-    const int64_t blocks = (cnt + COSW_TILE - 1) / COSW_TILE;
-    hipStream_t st = (hipStream_t)stream;
-    switch (nterm - 1) {
-        case 1: cosw_launch_pol<1>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-        case 2: cosw_launch_pol<2>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-        default: cosw_launch_pol<3>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-int efd_cosw_loglike(const double* S, int64_t stride, const float* Y, const uint64_t* info,
-                     int64_t m, int32_t rows, int64_t nf, int64_t k0, const double* a,
-                     int32_t nterm, const double* d, const double* w, double* out,
-                     double* scratch, void* stream) {
-    CoswCoef cf;
-    if (!hann_rows_ok("efd_cosw_loglike", S, stride, nf, rows) || !Y || !info || !d || !w ||
-        !out || !scratch || !cosw_coef(a, nterm, nf, cf) || m < nf || k0 < 0 || k0 >= nf ||
-        rows > HANN_ROWS_MAX)
-        return fail(EFD_ERR_ARG, "efd_cosw_loglike: bad arguments (rows <= 16, 2 <= nterm <= 4, "
-                                 "nf >= 2 (nterm - 1) + 1)");
-    const int64_t nb = nf - k0;
-    // efd_hann_loglike's chunks and row grouping
-    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH,
-                                          ((nb + COSW_TILE - 1) / COSW_TILE + 7) / 8 * 8);
-    hipStream_t st = (hipStream_t)stream;
-    const int rpt = (rows % 2 == 0) ? 2 : 1;
-    switch (nterm - 1) {
-        case 1:
-            cosw_launch_ll<1>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-        case 2:
-            cosw_launch_ll<2>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-        default:
-            cosw_launch_ll<3>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-    }
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-int efd_loglike(const double* h, const double* d, const double* w, int32_t nchan, int64_t nbin,
-                double* out, double* scratch, void* stream) {
-    if (!d || !w || !out || !scratch || nchan <= 0 || nbin <= 0)
-        return fail(EFD_ERR_ARG, "efd_loglike: bad arguments");
-    const int64_t total = (int64_t)nchan * nbin;
-    const int threads = 256;
-    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH, (total + threads - 1) / threads);
-    hipStream_t st = (hipStream_t)stream;
-    // fixed partition + fixed reduction tree: bitwise reproducible
-    hipLaunchKernelGGL(k_loglike_partial, dim3(np), dim3(threads), 0, st, (const double2*)h,
-                       (const double2*)d, w, total, scratch);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3(1), dim3(256), 0, st, scratch, np, out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-int efd_inner_product(const double* a, const double* b, const double* w, int32_t nchan,
-                      int64_t nbin, double* out, double* scratch, void* stream) {
-    if (!a || !b || !out || !scratch || nchan <= 0 || nbin <= 0)
-        return fail(EFD_ERR_ARG, "efd_inner_product: bad arguments");
-    const int64_t total = (int64_t)nchan * nbin;
-    const int threads = 256;
-    const int np = (int)std::min<int64_t>(EFD_INNER_SCRATCH / 2, (total + threads - 1) / threads);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_inner_partial, dim3(np), dim3(threads), 0, st, (const double2*)a,
-                       (const double2*)b, w, total, (double2*)scratch);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_inner_final, dim3(1), dim3(256), 0, st, (const double2*)scratch, np,
-                       4.0, (double2*)out);
-    HIP_TRY(hipGetLastError());
-    return EFD_OK;
-}
-
-static_assert(EFD_FISHER_SCRATCH == FG_MAXB * (EFD_FISHER_MAX_PARAMS * (EFD_FISHER_MAX_PARAMS + 1) / 2),
-              "EFD_FISHER_SCRATCH holds every workgroup's upper triangle");
-
-int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
-                    const double* coef, const double* w, int64_t nelem, double* dh, double* gram,
-                    double* scratch, void* stream) {
-    if (nparam < 1 || nparam > EFD_FISHER_MAX_PARAMS)
-        return fail(EFD_ERR_ARG, "efd_fisher_gram: nparam outside 1..16");
-    if (npoint != 1 && npoint != 2 && npoint != 4)
-        return fail(EFD_ERR_ARG, "efd_fisher_gram: npoint must be 1, 2 or 4");
-    if (!h || !coef || !gram || !scratch)
-        return fail(EFD_ERR_ARG, "efd_fisher_gram: NULL h, coef, gram or scratch");
-    if (nelem <= 0) return fail(EFD_ERR_ARG, "efd_fisher_gram: nelem <= 0");
-    if (row_stride < nelem) return fail(EFD_ERR_ARG, "efd_fisher_gram: row_stride < nelem");
-    fg_coef cf;
-    for (int i = 0; i < EFD_FISHER_MAX_PARAMS * 4; ++i)
-        cf.c[i] = i < nparam * npoint ? coef[i] : 0.0;
-    // the partition is a function of nelem alone
-    const int nb = (int)std::min<int64_t>(FG_MAXB, (nelem + FG_CHUNK - 1) / FG_CHUNK);
-    const int tp = (nparam + 3) / 4;
-    hipStream_t st = (hipStream_t)stream;
-    switch (npoint) {
-        case 1:
-            fg_launch<1>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-        case 2:
-            fg_launch<2>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-        default:
-            fg_launch<4>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-    }
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fisher_final, dim3((unsigned)(nparam * (nparam + 1) / 2)), dim3(256), 0,
-                       st, scratch, nb, nparam, gram);
-    HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
 

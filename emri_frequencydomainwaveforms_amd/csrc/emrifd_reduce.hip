@@ -1,0 +1,515 @@
+// emrifd_reduce.hip -- the small kernels of libemrifd.so (MI355X, gfx950) that turn spectra into
+// channels and numbers, and their C ABI (include/emrifd.h): the h+ / hx split
+// (efd_polarizations), the log-likelihood and inner product (efd_loglike, efd_inner_product),
+// the TD template's half-spectrum split and its fused likelihood (efd_td_split*), and the
+// Fisher matrix's Gram kernel (efd_fisher_gram). Shares only emrifd_common.h with the mode sum
+// (emrifd.hip) and the window path (emrifd_window.hip).
+
+#include "emrifd_common.h"
+
+namespace {
+
+// h+ / hx split with FEW's array flip
+__global__ void k_polarizations(const double2* __restrict__ S, int64_t nf, int64_t k0,
+                                double2* __restrict__ hp, double2* __restrict__ hc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t k = k0 + i;
+    if (k >= nf) return;
+    const double2 a = S[k], b = S[nf - 1 - k];
+    // h+ = (a + conj b)/2 ; hx = i (a - conj b)/2
+    hp[i] = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
+    hc[i] = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
+}
+
+// fused log-likelihood partials: one workgroup per chunk, then a second pass
+__global__ void k_loglike_partial(const double2* __restrict__ h, const double2* __restrict__ d,
+                                  const double* __restrict__ w, int64_t total,
+                                  double* __restrict__ part) {
+    // d - h*w rounded like the reference's numpy (product rounded, then difference): no FMA
+    // contraction here, so a template equal to the injection gives exactly 0
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double2 dv = d[i];
+        const double ww = w[i];
+        double rr = dv.x, ri = dv.y;
+        if (h) {
+            const double2 hv = h[i];
+            rr -= hv.x * ww;
+            ri -= hv.y * ww;
+        }
+        acc = fma(rr, rr, fma(ri, ri, acc));
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// (one row per workgroup: partials part[row * np ...], out[row])
+__global__ void k_loglike_final(const double* __restrict__ part, int np, double* __restrict__ out) {
+    part += (int64_t)blockIdx.x * np;
+    out += blockIdx.x;
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) acc += part[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = -0.5 * 4.0 * red[0];
+}
+
+// ---- DFT of a TD template h = h+ - i hx into its two channels (efd_td_split*). Z = fft(w h)
+// in natural order; the Hermitian split (k_polarizations' algebra, on the DFT's own pairing
+// k <-> (n - k) mod n) gives both real series' transforms over the bins k < nb = ceil(n / 2),
+// which are the drivers' positive-frequency bins (fftshift, then frequency >= 0):
+//   H+ = (Z[k] + conj Z[n-k]) / 2,  Hx = i (Z[k] - conj Z[n-k]) / 2,  each times gain (= dt).
+__device__ __forceinline__ void td_split_pair(const double2 a, const double2 b, double gain,
+                                              double2& hp, double2& hc) {
+#pragma clang fp contract(off)
+    hp = make_double2(gain * (0.5 * (a.x + b.x)), gain * (0.5 * (a.y - b.y)));
+    hc = make_double2(gain * (-0.5 * (a.y + b.y)), gain * (0.5 * (a.x - b.x)));
+}
+
+__global__ __launch_bounds__(256) void k_td_split(const double2* __restrict__ Z, int64_t stride,
+                                                  int64_t n, int64_t nb, double gain,
+                                                  const uint8_t* __restrict__ keep,
+                                                  double2* __restrict__ out, int64_t out_stride) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nb) return;
+    const double2* z = Z + (int64_t)blockIdx.y * stride;
+    double2* o = out + (int64_t)blockIdx.y * out_stride;
+    double2 hp = make_double2(0.0, 0.0), hc = hp;
+    if (keep == nullptr || keep[k] != 0) td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
+    o[k] = hp;
+    o[nb + k] = hc;
+}
+
+// logL partials of the split's channels against d ([2][nb]) and w ([2][nb]), the template kept
+// in registers: workgroup (c, r) takes bins [c chunk, (c + 1) chunk) of row r, an ascending
+// stream Z[k] and a descending one Z[n - k]; the row is the slow grid dimension, so the rows'
+// workgroups of one chunk follow each other on one XCD and find d and w in its cache. Partials
+// at part[r gridDim.x + c] (k_loglike_final's layout).
+__global__ __launch_bounds__(256) void k_td_split_loglike(
+    const double2* __restrict__ Z, int64_t stride, int64_t n, int64_t nb, int64_t chunk,
+    double gain, const double2* __restrict__ d, const double* __restrict__ w,
+    double* __restrict__ part) {
+    // d - h w rounded as k_loglike_partial does (product, then difference)
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const double2* z = Z + (int64_t)blockIdx.y * stride;
+    const int64_t k0 = (int64_t)blockIdx.x * chunk;
+    const int64_t k1 = min(nb, k0 + chunk);
+    double acc = 0.0;
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += 256) {
+        double2 hp, hc;
+        td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
+        const double2 d0 = d[k], d1 = d[nb + k];
+        const double w0 = w[k], w1 = w[nb + k];
+        const double ar = d0.x - hp.x * w0, ai = d0.y - hp.y * w0;
+        const double br = d1.x - hc.x * w1, bi = d1.y - hc.y * w1;
+        acc = fma(ar, ar, fma(ai, ai, acc));
+        acc = fma(br, br, fma(bi, bi, acc));
+    }
+    // even n: the Nyquist bin belongs to neither channel's kept bins; a NaN there still
+    // poisons the row, as one anywhere else does through the terms above
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
+        const double2 v = z[n / 2];
+        if (v.x != v.x || v.y != v.y) acc = v.x + v.y;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+// noise-weighted inner product partials: sum conj(a) b w (complex), one pair per workgroup
+__global__ void k_inner_partial(const double2* __restrict__ a, const double2* __restrict__ b,
+                                const double* __restrict__ w, int64_t total,
+                                double2* __restrict__ part) {
+    __shared__ double rre[256], rim[256];
+    double accr = 0.0, acci = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double2 av = a[i], bv = b[i];
+        const double ww = w ? w[i] : 1.0;
+        // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
+        accr = fma(ww, fma(av.x, bv.x, av.y * bv.y), accr);
+        acci = fma(ww, fma(av.x, bv.y, -av.y * bv.x), acci);
+    }
+    rre[threadIdx.x] = accr;
+    rim[threadIdx.x] = acci;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            rre[threadIdx.x] += rre[threadIdx.x + s];
+            rim[threadIdx.x] += rim[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(rre[0], rim[0]);
+}
+
+__global__ void k_inner_final(const double2* __restrict__ part, int np, double scale,
+                              double2* __restrict__ out) {
+    __shared__ double rre[256], rim[256];
+    double accr = 0.0, acci = 0.0;
+    for (int i = threadIdx.x; i < np; i += blockDim.x) {
+        accr += part[i].x;
+        acci += part[i].y;
+    }
+    rre[threadIdx.x] = accr;
+    rim[threadIdx.x] = acci;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            rre[threadIdx.x] += rre[threadIdx.x + s];
+            rim[threadIdx.x] += rim[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = make_double2(scale * rre[0], scale * rim[0]);
+}
+
+// ---- weighted Gram matrix of stencil-combined rows (efd_fisher_gram) ----------------------
+// One pass over h and w. A workgroup of 4 waves stages FG_CHUNK elements at a time: thread t
+// forms D_i[e] = sum_s coef[i][s] h[i npoint + s][e] for its element (the stencil is applied per
+// element, before any product: the Gram matrix of the raw rows combined afterwards loses the
+// digits the differences cancel) and writes D_i and w to LDS, and D_i to dh. Then each wave
+// takes 4 x 4 tiles (i, j) of the upper triangle's tile grid, its lanes run over the chunk's
+// elements (lane l: l, l + 64, l + 128, l + 192; consecutive 16-byte LDS slots per read) and
+// keep the tile's 16 sums in registers across the workgroup's chunks.
+// What makes gram[i][j] a function of rows i, j, w and nelem alone (the subset promise):
+//   - chunk c goes to workgroup c mod gridDim.x, and gridDim.x is a function of nelem;
+//   - every pair sees the same element -> lane map, the same butterfly over the lanes and the
+//     same final order over the workgroups, whichever wave and tile hold it;
+//   - a term is fma(w, fma(ar, br, ai * bi), acc): symmetric in (a, b), so (j, i) of a
+//     reordered call rounds as (i, j) does; contraction is off, the fmas are the written ones.
+constexpr int FG_THREADS = 256;
+constexpr int FG_CHUNK = 256;
+constexpr int FG_MAXB = 1024;   // workgroups (4 per CU); EFD_FISHER_SCRATCH = FG_MAXB * 136
+
+struct fg_coef {
+    double c[EFD_FISHER_MAX_PARAMS * 4];
+};
+
+__host__ __device__ inline int fg_pair_index(int i, int j, int P) {   // i <= j, row-major upper
+    return i * P - (i * (i - 1)) / 2 + (j - i);
+}
+
+// TP: tile rows = ceil(nparam / 4); the upper triangle has TP (TP + 1) / 2 tiles, wave v takes
+// tiles v, v + 4, v + 8
+template <int NPOINT, int TP>
+__global__ __launch_bounds__(FG_THREADS) void k_fisher_partial(
+    const double2* __restrict__ h, int64_t row_stride, int nparam, fg_coef cf,
+    const double* __restrict__ w, int64_t nelem, double2* __restrict__ dh,
+    double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int NTILE = TP * (TP + 1) / 2;
+    constexpr int MAXT = (NTILE + 3) / 4;
+    __shared__ double2 D[4 * TP * FG_CHUNK];
+    __shared__ double wl[FG_CHUNK];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // rows nparam .. 4 TP - 1 pad the last tile row: zero, written once
+    for (int r = nparam; r < 4 * TP; ++r) D[r * FG_CHUNK + tid] = make_double2(0.0, 0.0);
+    int ti[MAXT], tj[MAXT];
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k) {
+        int t = wv + 4 * k, I = 0;
+        while (I < TP - 1 && t >= TP - I) {   // tile row I holds TP - I tiles (J = I .. TP-1)
+            t -= TP - I;
+            ++I;
+        }
+        ti[k] = I;
+        tj[k] = I + t;   // >= TP: this wave has no k-th tile
+    }
+    double acc[MAXT][16];
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k)
+#pragma unroll
+        for (int p = 0; p < 16; ++p) acc[k][p] = 0.0;
+
+    const int64_t nchunk = (nelem + FG_CHUNK - 1) / FG_CHUNK;
+    for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
+        const int64_t e = c * FG_CHUNK + tid;
+        const bool live = e < nelem;
+        wl[tid] = live ? (w ? w[e] : 1.0) : 0.0;
+        for (int i = 0; i < nparam; ++i) {
+            double dr = 0.0, di = 0.0;
+            if (live) {
+                const double2* r = h + row_stride * ((int64_t)i * NPOINT) + e;
+                double2 v[NPOINT];
+#pragma unroll
+                for (int s = 0; s < NPOINT; ++s) v[s] = r[row_stride * s];
+                const double c0 = cf.c[i * NPOINT];
+                dr = c0 * v[0].x;
+                di = c0 * v[0].y;
+#pragma unroll
+                for (int s = 1; s < NPOINT; ++s) {
+                    const double cs = cf.c[i * NPOINT + s];
+                    dr = fma(cs, v[s].x, dr);
+                    di = fma(cs, v[s].y, di);
+                }
+                if (dh) dh[(int64_t)i * nelem + e] = make_double2(dr, di);
+            }
+            D[i * FG_CHUNK + tid] = make_double2(dr, di);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MAXT; ++k) {
+            if (tj[k] >= TP) continue;
+            const double2* A = D + 4 * ti[k] * FG_CHUNK;
+            const double2* B = D + 4 * tj[k] * FG_CHUNK;
+#pragma unroll
+            for (int q = 0; q < FG_CHUNK / 64; ++q) {
+                const int x = lane + 64 * q;
+                const double ww = wl[x];
+                double2 a[4], b[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    a[r] = A[r * FG_CHUNK + x];
+                    b[r] = B[r * FG_CHUNK + x];
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        acc[k][4 * r + s] = fma(ww, fma(a[r].x, b[s].x, a[r].y * b[s].y),
+                                                acc[k][4 * r + s]);
+            }
+        }
+        __syncthreads();
+    }
+    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
+    const int npair = nparam * (nparam + 1) / 2;
+#pragma unroll
+    for (int k = 0; k < MAXT; ++k) {
+        if (tj[k] >= TP) continue;
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {
+            double v = acc[k][p];
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+            const int gi = 4 * ti[k] + (p >> 2), gj = 4 * tj[k] + (p & 3);
+            if (lane == 0 && gi <= gj && gj < nparam)
+                part[(int64_t)blockIdx.x * npair + fg_pair_index(gi, gj, nparam)] = v;
+        }
+    }
+}
+
+// one workgroup per pair: the workgroups' partials in a fixed order, mirrored into both halves
+__global__ void k_fisher_final(const double* __restrict__ part, int nb, int nparam,
+                               double* __restrict__ gram) {
+    __shared__ double red[256];
+    const int npair = nparam * (nparam + 1) / 2;
+    const int p = blockIdx.x;
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[(int64_t)b * npair + p];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        int i = 0, q = p;
+        while (q >= nparam - i) {
+            q -= nparam - i;
+            ++i;
+        }
+        const int j = i + q;
+        const double g = 4.0 * red[0];
+        gram[i * nparam + j] = g;
+        gram[j * nparam + i] = g;
+    }
+}
+
+template <int NPOINT>
+void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_stride, int nparam,
+               const fg_coef& cf, const double* w, int64_t nelem, double2* dh, double* part) {
+    switch (tp) {
+        case 1:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 1>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        case 2:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 2>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        case 3:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 3>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+        default:
+            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 4>), dim3(nb), dim3(FG_THREADS), 0, st, h,
+                               row_stride, nparam, cf, w, nelem, dh, part);
+            break;
+    }
+}
+
+}  // namespace
+
+void efdhip::launch_loglike_final(int rows, const double* part, int np, double* out,
+                                  hipStream_t st) {
+    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, part, np, out);
+}
+
+// ========================================================================================
+// C ABI
+// ========================================================================================
+extern "C" {
+
+int efd_polarizations(const double* S, int64_t nf, int64_t k0, double* hp, double* hc,
+                      void* stream) {
+    if (!S || !hp || !hc || nf <= 0 || k0 < 0 || k0 > nf)
+        return fail(EFD_ERR_ARG, "efd_polarizations: bad arguments");
+    const int64_t cnt = nf - k0;
+    if (cnt == 0) return EFD_OK;
+    const int threads = 256;
+    const int64_t blocks = (cnt + threads - 1) / threads;
+    hipLaunchKernelGGL(k_polarizations, dim3((unsigned)blocks), dim3(threads), 0,
+                       (hipStream_t)stream, (const double2*)S, nf, k0, (double2*)hp, (double2*)hc);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_loglike(const double* h, const double* d, const double* w, int32_t nchan, int64_t nbin,
+                double* out, double* scratch, void* stream) {
+    if (!d || !w || !out || !scratch || nchan <= 0 || nbin <= 0)
+        return fail(EFD_ERR_ARG, "efd_loglike: bad arguments");
+    const int64_t total = (int64_t)nchan * nbin;
+    const int threads = 256;
+    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH, (total + threads - 1) / threads);
+    hipStream_t st = (hipStream_t)stream;
+    // fixed partition + fixed reduction tree: bitwise reproducible
+    hipLaunchKernelGGL(k_loglike_partial, dim3(np), dim3(threads), 0, st, (const double2*)h,
+                       (const double2*)d, w, total, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_loglike_final, dim3(1), dim3(256), 0, st, scratch, np, out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_inner_product(const double* a, const double* b, const double* w, int32_t nchan,
+                      int64_t nbin, double* out, double* scratch, void* stream) {
+    if (!a || !b || !out || !scratch || nchan <= 0 || nbin <= 0)
+        return fail(EFD_ERR_ARG, "efd_inner_product: bad arguments");
+    const int64_t total = (int64_t)nchan * nbin;
+    const int threads = 256;
+    const int np = (int)std::min<int64_t>(EFD_INNER_SCRATCH / 2, (total + threads - 1) / threads);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_inner_partial, dim3(np), dim3(threads), 0, st, (const double2*)a,
+                       (const double2*)b, w, total, (double2*)scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_inner_final, dim3(1), dim3(256), 0, st, (const double2*)scratch, np,
+                       4.0, (double2*)out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+static_assert(EFD_FISHER_SCRATCH == FG_MAXB * (EFD_FISHER_MAX_PARAMS * (EFD_FISHER_MAX_PARAMS + 1) / 2),
+              "EFD_FISHER_SCRATCH holds every workgroup's upper triangle");
+
+int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
+                    const double* coef, const double* w, int64_t nelem, double* dh, double* gram,
+                    double* scratch, void* stream) {
+    if (nparam < 1 || nparam > EFD_FISHER_MAX_PARAMS)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: nparam outside 1..16");
+    if (npoint != 1 && npoint != 2 && npoint != 4)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: npoint must be 1, 2 or 4");
+    if (!h || !coef || !gram || !scratch)
+        return fail(EFD_ERR_ARG, "efd_fisher_gram: NULL h, coef, gram or scratch");
+    if (nelem <= 0) return fail(EFD_ERR_ARG, "efd_fisher_gram: nelem <= 0");
+    if (row_stride < nelem) return fail(EFD_ERR_ARG, "efd_fisher_gram: row_stride < nelem");
+    fg_coef cf;
+    for (int i = 0; i < EFD_FISHER_MAX_PARAMS * 4; ++i)
+        cf.c[i] = i < nparam * npoint ? coef[i] : 0.0;
+    // the partition is a function of nelem alone
+    const int nb = (int)std::min<int64_t>(FG_MAXB, (nelem + FG_CHUNK - 1) / FG_CHUNK);
+    const int tp = (nparam + 3) / 4;
+    hipStream_t st = (hipStream_t)stream;
+    switch (npoint) {
+        case 1:
+            fg_launch<1>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+        case 2:
+            fg_launch<2>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+        default:
+            fg_launch<4>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
+                         (double2*)dh, scratch);
+            break;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fisher_final, dim3((unsigned)(nparam * (nparam + 1) / 2)), dim3(256), 0,
+                       st, scratch, nb, nparam, gram);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+// the chunks of efd_td_split_loglike for n points: a function of n alone (whole rounds of the
+// 8 XCDs once there are that many), each a multiple of 256 bins
+static int td_split_chunks(int64_t nb, int64_t* chunk) {
+    int64_t np = std::min<int64_t>(EFD_TD_SPLIT_SCRATCH, (nb + 1023) / 1024);
+    if (np > 8) np -= np % 8;
+    int64_t c = (nb + np - 1) / np;
+    c = (c + 255) / 256 * 256;
+    *chunk = c;
+    return (int)((nb + c - 1) / c);
+}
+
+int efd_td_split(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                 const uint8_t* keep, double* out, int64_t out_stride, void* stream) {
+    if (!Z || !out) return fail(EFD_ERR_ARG, "efd_td_split: NULL Z or out");
+    if (n < 1 || n > ((int64_t)1 << 40)) return fail(EFD_ERR_ARG, "efd_td_split: n out of range");
+    if (rows < 1) return fail(EFD_ERR_ARG, "efd_td_split: rows < 1");
+    const int64_t nb = (n + 1) / 2;
+    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split: stride < n");
+    if (out_stride < 2 * nb) return fail(EFD_ERR_ARG, "efd_td_split: out_stride < 2 nb");
+    const int64_t blocks = (nb + 255) / 256;
+    if (blocks > 0x7fffffffLL || rows > 65535)
+        return fail(EFD_ERR_ARG, "efd_td_split: too many bins or rows");
+    hipLaunchKernelGGL(k_td_split, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0,
+                       (hipStream_t)stream, (const double2*)Z, stride, n, nb, gain, keep,
+                       (double2*)out, out_stride);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                         const double* d, const double* w, double* out, double* scratch,
+                         void* stream) {
+    if (!Z || !d || !w || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_td_split_loglike: NULL Z, d, w, out or scratch");
+    if (n < 1 || n > ((int64_t)1 << 40))
+        return fail(EFD_ERR_ARG, "efd_td_split_loglike: n out of range");
+    if (rows < 1 || rows > 65535) return fail(EFD_ERR_ARG, "efd_td_split_loglike: rows out of range");
+    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split_loglike: stride < n");
+    const int64_t nb = (n + 1) / 2;
+    int64_t chunk = 0;
+    const int np = td_split_chunks(nb, &chunk);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_td_split_loglike, dim3((unsigned)np, (unsigned)rows), dim3(256), 0, st,
+                       (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)d, w, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 The reference reaches this through `GenerateEMRIWaveform(..., sum_kwargs=dict(pad_output=True,
 output_type="fd", odd_len=True))` (check_mode_by_mode.py:69-83) and reads the grid back from
 `.waveform_generator.create_waveform.frequency` (check_mode_by_mode.py:250, emri_pe.py:238).
-Everything numerical runs in libemrifd.so (csrc/emrifd.hip) through the C ABI of
+Everything numerical runs in libemrifd.so (csrc/emrifd*.hip) through the C ABI of
 include/emrifd.h; PyTorch only provides device memory and the stream.
 
 Grid (FEW 1.x [FEW-ext], reproduces the published 6311631 positive bins at T = 4 yr,

@@ -3,7 +3,9 @@
     python tools/exp_variants.py build NAME[=SRC][:-DFLAG[=V][,-DFLAG2...]] ...   # here, hipcc only
     python tools/exp_variants.py run NAME ...                              # on the GPU box
 
-`build` writes exp/libemrifd_<NAME>.so (git-ignored, travels with gpurun). `run` loads each
+`build` compiles only the variant's mode-sum unit (csrc/emrifd.hip, or SRC: a copy of it) and
+links it with the in-tree objects of the other units, so every variant exports the whole ABI. It
+writes exp/libemrifd_<NAME>.so (git-ignored, copied to the GPU box with the tree). `run` loads each
 variant in its own child process, runs config 2's full device pipeline, and prints one JSON line
 per variant: k_modesum ms (HIP events, mean of 5 launches), the spectrum's max deviation from
 the in-tree library's (relative to max|S|), and the -DEFD_EXP counters when compiled in.
@@ -33,22 +35,29 @@ def lib_path(name):
 
 def build(specs):
     from emri_frequencydomainwaveforms_amd import _build
-    _build.build()   # the host objects (twin, upstream) every variant links, as the in-tree one
-    objs = [os.path.join(_build.OBJDIR, o)
-            for o in ("emrifd_cpu.o", "emrifd_host.o", "emrifd_modes.o")]
+    # a variant is its own compile of the mode-sum unit (csrc/emrifd.hip: every EFD_EXP block is
+    # there), linked with the in-tree objects of everything else -- the host objects (twin,
+    # upstream) and the window and reduction units -- so it exports the whole ABI
+    objs = _build.HOST_OBJS + [_build.obj_path(s) for s in _build.HIP_UNITS[1:]]
+    _build.build(force=not all(map(os.path.exists, objs)))   # (a library can travel without them)
     os.makedirs(EXP, exist_ok=True)
-    procs = []
+    jobs = []
     for spec in specs:
         name, _, flags = spec.partition(":")
-        # NAME=SOURCE: another kernel source (e.g. an earlier revision saved under exp/)
+        # NAME=SOURCE: another mode-sum source (e.g. an earlier revision saved under exp/; it
+        # includes emrifd_common.h and the tables by name, hence -I csrc)
         name, _, src = name.partition("=")
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-               *[f for f in flags.split(",") if f], "-o", lib_path(name), *objs, src or SRC,
-               "-lgomp", "-lmvec"]
+        obj = os.path.join(EXP, f"emrifd_{name}.o")
+        cmd = _build.hip_compile_cmd(src or SRC, obj, ["-I", _build.CSRC,
+                                                       *[f for f in flags.split(",") if f]])
         print(" ".join(cmd), flush=True)
-        procs.append(subprocess.Popen(cmd))
-    if any(p.wait() != 0 for p in procs):
-        sys.exit("variant build failed")
+        jobs.append((name, obj, subprocess.Popen(cmd)))
+    for name, obj, p in jobs:
+        if p.wait() != 0:
+            sys.exit("variant build failed")
+        cmd = _build.link_cmd(objs + [obj], lib_path(name))
+        print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
 
 
 def child(name, ref_path):
