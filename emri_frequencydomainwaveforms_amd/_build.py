@@ -7,10 +7,11 @@ source is compiled to an object under build/, all of them at once, and one link 
   and the walker batches' staging
   csrc/emrifd_modes.cpp -> g++ -O3 -ffast-math -fopenmp (libmvec; knots over threads for one-at-a-time
                           calls): amplitudes, mode selection
-  csrc/emrifd.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode sum, the window path,
-                         the channel split and reductions) -> hipcc --offload-arch=gfx950 -c each;
-                         they share only csrc/emrifd_common.h (no relocatable device code)
-  link                -> hipcc -shared over the six objects, with libgomp and libmvec
+  csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode
+                         sum, its preparation, the window path, the channel split and reductions)
+                         -> hipcc --offload-arch=gfx950 -c each; all share csrc/emrifd_common.h,
+                         the first two also csrc/emrifd_layout.h (no relocatable device code)
+  link                -> hipcc -shared over the seven objects, with libgomp and libmvec
 """
 
 import glob
@@ -20,8 +21,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "emrifd.hip")
-# the HIP translation units, the mode sum (SRC) first
-HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_window.hip"), os.path.join(CSRC, "emrifd_reduce.hip")]
+# the HIP translation units, the mode sum (SRC) first, then its preparation: the two longest
+HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_prepare.hip"), os.path.join(CSRC, "emrifd_window.hip"),
+             os.path.join(CSRC, "emrifd_reduce.hip")]
 CPU_SRC = os.path.join(CSRC, "emrifd_cpu.cpp")
 HOST_SRC = os.path.join(CSRC, "emrifd_host.cpp")
 MODES_SRC = os.path.join(CSRC, "emrifd_modes.cpp")
@@ -93,7 +95,7 @@ def build(force=False, verbose=False, extra=()):
     os.makedirs(OBJDIR, exist_ok=True)
     gxx = ["g++", "-O3", f"-march={CPU_ARCH}", "-fPIC", "-std=c++17", "-fopenmp"]
     bid = [f'-DEFD_BUILD_ID="{sid}"'] if not extra else []
-    # the longest compile (the mode sum) first; six compilers at once, one per source
+    # the longest compile (the mode sum) first; seven compilers at once, one per source
     cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in HIP_UNITS]
     cmds += [[*gxx, "-ffp-contract=off", "-c", CPU_SRC, "-o", obj_path(CPU_SRC)],
              [*gxx, "-ffp-contract=off", "-c", HOST_SRC, "-o", obj_path(HOST_SRC)],

@@ -1,7 +1,8 @@
 // emrifd_common.h -- what the library's HIP units share: emrifd.hip (mode sum),
-// emrifd_window.hip (window path) and emrifd_reduce.hip (channels and reductions). They share no
-// device code; each is compiled on its own (no relocatable device code) and linked into
-// libemrifd.so. Names declared here have external linkage so that the units can reach them,
+// emrifd_prepare.hip (its preparation), emrifd_window.hip (window path) and emrifd_reduce.hip
+// (channels and reductions). They share no device code; each is compiled on its own (no
+// relocatable device code) and linked into libemrifd.so. The two units of the mode-sum chain
+// share emrifd_layout.h on top of this. Names declared here have external linkage so that the units can reach them,
 // and hidden visibility so that the library still exports only include/emrifd.h.
 #pragma once
 

@@ -5,7 +5,8 @@
 //
 // The reference's CPU path is the numpy/CPU branch of the same FEW generator
 // (check_mode_by_mode.py:50-60, emri_pe.py:68-80, FDutils.py:7-17). FEW's CPU backend is absent
-// offline, so the twin restates this library's own construction on the CPU:
+// offline, so the twin restates this library's own construction on the CPU (kernels of
+// emrifd_prepare.hip down to k_items, of emrifd.hip from k_tile_keys on):
 //   (m, n) grouping, members ascending h                       k_group
 //   group amplitudes Bp = sum_l y0 A, Bm = sum_l y1 A           k_group_amp
 //   not-a-knot splines: trajectory (Phi_phi, Phi_r, f_phi, f_r, knot slopes of f_phi and f_r),
@@ -44,22 +45,9 @@ struct double2 {
 #include "spa_tables.inc"
 #undef EFD_TABLE
 
-constexpr int TL = 768;             // lanes per tile (the kernel's TILE * BPL)
-constexpr int MAXRUNS = 8;
-constexpr int MAX_NT = 1024;
-constexpr int MAX_K = 8192;
-constexpr int FAST_J = 4;
-constexpr double FAST_Y = 153.0;
-constexpr double PI = 3.141592653589793238462643383279502884;
-constexpr double TWO_PI = 6.283185307179586476925286766559005768;
-constexpr double VS = 0.18633899812498247470;             // sqrt|KRH_1|
-constexpr double FDD_SCALE = 0.29827892638794838654;      // sqrt(3/(2 pi)) |KRH_1|^(1/4)
-constexpr double INV_FDD_SCALE = 3.3525667136785156343;
-constexpr double KTH0 = -0.069444444444444444444;
-// the kernel's cosine on |r| <= pi/512 (emrifd.hip, sincos_tab): minimax line in r^2
-constexpr double COS_A = 1.000000000029531;
-constexpr double COS_B = -0.5;
-constexpr double KTAB_WMIN = 0x1p-8, KTAB_WMAX = 0x1p10;
+// the constants of the device code (MAXRUNS, FAST_J, VS, COS_A, ...), defined once for both
+#include "emrifd_constants.h"
+constexpr int TL = TILE * BPL;      // lanes per tile
 using std::fabs;
 using std::fma;
 using std::fmax;

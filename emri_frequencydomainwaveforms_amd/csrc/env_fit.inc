@@ -1,5 +1,5 @@
 // env_fit.inc -- the SPA envelope of an interval record as polynomials in w = t - t_j, shared by
-// the preparation kernel k_items (emrifd.hip, EFD_HD = __device__) and the host twin
+// the preparation kernel k_items (emrifd_prepare.hip, EFD_HD = __device__) and the host twin
 // (emrifd_cpu.cpp, EFD_HD empty). Both define TWO_PI, KTH0, the KRH / KTHN tables and
 // env_rsqrt first.
 //

@@ -53,24 +53,31 @@ def test_build_inputs_cover_every_source_file():
     inputs = {os.path.realpath(p) for p in _build._inputs()}
     files = [os.path.join(_build.CSRC, f) for f in os.listdir(_build.CSRC)]
     files = [p for p in files if os.path.isfile(p)]
-    assert len(files) >= 10   # 3 HIP units, their header, 3 host sources, 3 tables
+    assert len(files) >= 13   # 4 HIP units, their 3 headers, 3 host sources, 3 tables
     for p in files:
         assert os.path.realpath(p) in inputs, p
     assert os.path.realpath(HEADER) in inputs
-    assert len(_build.HIP_UNITS) == 3 and _build.HIP_UNITS[0] == _build.SRC
+    assert len(_build.HIP_UNITS) == 4 and _build.HIP_UNITS[0] == _build.SRC
     for p in _build.HIP_UNITS:
         assert os.path.isfile(p) and os.path.realpath(p) in inputs, p
         assert os.path.dirname(_build.obj_path(p)) == _build.OBJDIR
 
 
 def test_last_error_reports_every_unit():
-    """efd_last_error holds one string for the library: an argument error raised in the window
-    unit or in the reduction unit reads back as the mode sum's do (no device call is made)."""
+    """efd_last_error holds one string for the library: an argument error raised in the
+    preparation unit, the window unit or the reduction unit reads back as the mode sum's do (no
+    device call is made)."""
     lib = _lib.load()
     buf = ctypes.create_string_buffer(256)
     assert lib.efd_upload(None, None, 8, None) == -1              # emrifd.hip
     lib.efd_last_error(buf, 256)
     assert b"efd_upload: NULL pointer" in buf.value
+    assert lib.efd_spline_build(None, 0, None, 0, None, None) == -1       # emrifd_prepare.hip
+    lib.efd_last_error(buf, 256)
+    assert b"efd_spline_build: bad arguments" in buf.value
+    assert lib.efd_modesum_prepare_batch(None, None, None, 0, None) == -1
+    lib.efd_last_error(buf, 256)
+    assert b"efd_modesum_prepare_batch: NULL argument" in buf.value
     assert lib.efd_hann_stage(None, 0, 0, 0, None, 0, None, None) == -1   # emrifd_window.hip
     lib.efd_last_error(buf, 256)
     assert b"efd_hann_stage: bad arguments" in buf.value

@@ -80,7 +80,7 @@ def test_short_trajectories(base, nt):
 
 
 # 512 / 513: the last knot count the preparation's parallel-cyclic-reduction splines take and
-# the first that goes back to the Thomas kernel (emrifd.hip PCR_NMAX)
+# the first that goes back to the Thomas kernel (emrifd_prepare.hip PCR_NMAX)
 @pytest.mark.parametrize("nt", [257, 512, 513, 1024])
 def test_long_trajectories(base, nt):
     t = base["t"]

@@ -3,9 +3,10 @@
     python tools/exp_variants.py build NAME[=SRC][:-DFLAG[=V][,-DFLAG2...]] ...   # here, hipcc only
     python tools/exp_variants.py run NAME ...                              # on the GPU box
 
-`build` compiles only the variant's mode-sum unit (csrc/emrifd.hip, or SRC: a copy of it) and
-links it with the in-tree objects of the other units, so every variant exports the whole ABI. It
-writes exp/libemrifd_<NAME>.so (git-ignored, copied to the GPU box with the tree). `run` loads each
+`build` compiles the variant's two units of the mode-sum chain with its flags -- the sum
+(csrc/emrifd.hip, or SRC: a copy of it) and the preparation (csrc/emrifd_prepare.hip, where
+EFD_EXP_EXACT_RCP and EFD_EXP_NO_PCR live) -- and links them with the in-tree objects of the
+other units, so every variant exports the whole ABI. It writes exp/libemrifd_<NAME>.so (git-ignored, copied to the GPU box with the tree). `run` loads each
 variant in its own child process, runs config 2's full device pipeline, and prints one JSON line
 per variant: k_modesum ms (HIP events, mean of 5 launches), the spectrum's max deviation from
 the in-tree library's (relative to max|S|), and the -DEFD_EXP counters when compiled in.
@@ -21,6 +22,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXP = os.path.join(ROOT, "exp")
 SRC = os.path.join(ROOT, "emri_frequencydomainwaveforms_amd", "csrc", "emrifd.hip")
+PREP_SRC = os.path.join(ROOT, "emri_frequencydomainwaveforms_amd", "csrc", "emrifd_prepare.hip")
 sys.path.insert(0, ROOT)
 
 
@@ -35,27 +37,33 @@ def lib_path(name):
 
 def build(specs):
     from emri_frequencydomainwaveforms_amd import _build
-    # a variant is its own compile of the mode-sum unit (csrc/emrifd.hip: every EFD_EXP block is
-    # there), linked with the in-tree objects of everything else -- the host objects (twin,
-    # upstream) and the window and reduction units -- so it exports the whole ABI
-    objs = _build.HOST_OBJS + [_build.obj_path(s) for s in _build.HIP_UNITS[1:]]
+    # a variant is its own compile of the mode-sum chain (csrc/emrifd.hip: every EFD_EXP block
+    # of the sum; csrc/emrifd_prepare.hip: the preparation's switches), linked with the in-tree
+    # objects of everything else -- the host objects (twin, upstream) and the window and
+    # reduction units -- so it exports the whole ABI
+    assert _build.HIP_UNITS[:2] == [SRC, PREP_SRC]
+    objs = _build.HOST_OBJS + [_build.obj_path(s) for s in _build.HIP_UNITS[2:]]
     _build.build(force=not all(map(os.path.exists, objs)))   # (a library can travel without them)
     os.makedirs(EXP, exist_ok=True)
     jobs = []
     for spec in specs:
         name, _, flags = spec.partition(":")
-        # NAME=SOURCE: another mode-sum source (e.g. an earlier revision saved under exp/; it
-        # includes emrifd_common.h and the tables by name, hence -I csrc)
+        # NAME=SOURCE: another source of the sum unit (e.g. an earlier revision saved under
+        # exp/; it includes emrifd_layout.h and the tables by name, hence -I csrc)
         name, _, src = name.partition("=")
-        obj = os.path.join(EXP, f"emrifd_{name}.o")
-        cmd = _build.hip_compile_cmd(src or SRC, obj, ["-I", _build.CSRC,
-                                                       *[f for f in flags.split(",") if f]])
-        print(" ".join(cmd), flush=True)
-        jobs.append((name, obj, subprocess.Popen(cmd)))
-    for name, obj, p in jobs:
-        if p.wait() != 0:
+        flags = ["-I", _build.CSRC, *[f for f in flags.split(",") if f]]
+        units = {os.path.join(EXP, f"emrifd_{name}.o"): src or SRC,
+                 os.path.join(EXP, f"emrifd_prepare_{name}.o"): PREP_SRC}
+        procs = []
+        for obj, unit in units.items():
+            cmd = _build.hip_compile_cmd(unit, obj, flags)
+            print(" ".join(cmd), flush=True)
+            procs.append(subprocess.Popen(cmd))
+        jobs.append((name, list(units), procs))
+    for name, variant_objs, procs in jobs:
+        if any([p.wait() != 0 for p in procs]):
             sys.exit("variant build failed")
-        cmd = _build.link_cmd(objs + [obj], lib_path(name))
+        cmd = _build.link_cmd(objs + variant_objs, lib_path(name))
         print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
