@@ -752,8 +752,25 @@ __device__ void spline_shared(const double* __restrict__ x, int n, YF yf, int co
 // ----------------------------------------------------------------------------------------
 __device__ __forceinline__ double knotF(const double* f_phi, const double* f_r, int m, int n,
                                         int i) {
-    // numpy's m * f_phi + n * f_r, rounded the same way (no FMA contraction)
+    // The abscissae of the inverse splines and the run signs. NOT numpy's rounding: the _rn
+    // builtins are the plain operators in HIP's headers, so the compiler contracts this into one
+    // rounded product and an FMA, an ulp off numpy's m * f_phi + n * f_r at some knots. That is
+    // harmless for t(F) (and kept as it is: another rounding here moves every spectrum's last
+    // digits), but not for a comparison with a grid value: k_items takes its bounds from knotF_rn.
     return __dadd_rn(__dmul_rn((double)m, f_phi[i]), __dmul_rn((double)n, f_r[i]));
+}
+// numpy's m * f_phi + n * f_r bit for bit (product, product, sum, each rounded once: no FMA
+// contraction), as the oracle's supports and the host twin's knotF have it. The lane bounds
+// compare it with the grid: a bin that equals a knot frequency belongs to [F_j, F_{j+1}) of one
+// record, or to none at a run's open end, only if both sides hold the same double. With the
+// contracted value a run's end knot could move an ulp past such a bin, which then gained or lost
+// a whole term.
+__device__ __forceinline__ double knotF_rn(const double* f_phi, const double* f_r, int m, int n,
+                                           int i) {
+#pragma clang fp contract(off)
+    const double a = (double)m * f_phi[i];
+    const double b = (double)n * f_r[i];
+    return a + b;
 }
 
 __device__ void inverse_splines(const double* __restrict__ t, const double* __restrict__ f_phi,
@@ -1405,7 +1422,7 @@ __device__ bool build_item(
         ymin_rec = ymin;
     }
     // g-interval of this record: [x_lo, x_hi), lower end open at the run's first knot
-    const double Fj = knotF(f_phi, f_r, m, n, j), Fj1 = knotF(f_phi, f_r, m, n, j + 1);
+    const double Fj = knotF_rn(f_phi, f_r, m, n, j), Fj1 = knotF_rn(f_phi, f_r, m, n, j + 1);
     const double xlo = sg > 0 ? Fj : Fj1;
     const double xhi = sg > 0 ? Fj1 : Fj;
     const bool strict_lo = sg > 0 ? (j == a) : (j + 1 == rr[4 * run + 1]);
