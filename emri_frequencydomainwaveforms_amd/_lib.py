@@ -20,6 +20,8 @@ EFD_LOGLIKE_SCRATCH = 1024
 EFD_INNER_SCRATCH = 2048
 EFD_FISHER_MAX_PARAMS = 16
 EFD_FISHER_SCRATCH = 139264   # efd_fisher_gram's scratch doubles (1024 workgroups x 136 pairs)
+EFD_OVERLAP_MAX_ROWS = 64
+EFD_OVERLAP_SCRATCH = 197632   # efd_overlap_rows' scratch doubles (1024 workgroups x 193 outputs)
 EFD_BATCH_MAX = 16
 EFD_HANN_ROWS_MAX = 16   # efd_hann_loglike's rows per call (include/emrifd.h)
 EFD_HANN_LOCAL_PARTIALS = 4096   # efd_hann_loglike_local's scratch doubles per row
@@ -71,6 +73,7 @@ EXPORTED_SYMBOLS = (
     "efd_loglike",
     "efd_inner_product",
     "efd_fisher_gram",
+    "efd_overlap_rows",
     "efd_modesum_cpu",
     "efd_modesum_cpu_stats",
     "efd_spline_build_cpu",
@@ -78,6 +81,7 @@ EXPORTED_SYMBOLS = (
     "efd_loglike_cpu",
     "efd_inner_product_cpu",
     "efd_fisher_gram_cpu",
+    "efd_overlap_rows_cpu",
     "efd_td_split_cpu",
     "efd_td_split_loglike_cpu",
     "efd_cpu_threads",
@@ -289,6 +293,9 @@ def load(path=None):
     lib.efd_inner_product.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp]
     lib.efd_fisher_gram.restype = ctypes.c_int
     lib.efd_fisher_gram.argtypes = [vp, i64, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    for name in ("efd_overlap_rows", "efd_overlap_rows_cpu"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp]
     if hasattr(lib, "efd_modesum_cpu"):   # the host twins (csrc/emrifd_cpu.cpp)
         lib.efd_modesum_cpu.restype = ctypes.c_int
         lib.efd_modesum_cpu.argtypes = [ctypes.POINTER(ModesumArgs), vp, sz, vp]

@@ -974,6 +974,53 @@ int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int
     return EFD_OK;
 }
 
+// efd_overlap_rows' arithmetic: r = t - u per element, then the three written fmas per row.
+// Fixed chunks of 4096 elements, their partials added in chunk order: the result does not
+// depend on the thread count, and a row's numbers do not depend on the other rows.
+int efd_overlap_rows_cpu(const double* h, int64_t row_stride, int32_t nrow, const double* t,
+                         const double* u, const double* w, int64_t nelem, double* out,
+                         double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (nrow < 1 || nrow > EFD_OVERLAP_MAX_ROWS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_overlap_rows_cpu: nrow outside 1..64");
+    if (!h || !t || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_overlap_rows_cpu: NULL h, t or out");
+    if (nelem <= 0) return efdcpu::fail(EFD_ERR_ARG, "efd_overlap_rows_cpu: nelem <= 0");
+    if (row_stride < nelem)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_overlap_rows_cpu: row_stride < nelem");
+    const int nout = 3 * nrow + 1;
+    const int64_t chunk = 4096;
+    const int64_t nchunk = (nelem + chunk - 1) / chunk;
+    std::vector<double> part((size_t)nchunk * nout, 0.0);
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+    for (int64_t c = 0; c < nchunk; ++c) {
+        double* acc = part.data() + (size_t)c * nout;
+        const int64_t e1 = std::min(nelem, (c + 1) * chunk);
+        for (int64_t e = c * chunk; e < e1; ++e) {
+            double rr = t[2 * e], ri = t[2 * e + 1];
+            if (u) {
+                rr -= u[2 * e];
+                ri -= u[2 * e + 1];
+            }
+            const double ww = w ? w[e] : 1.0;
+            for (int k = 0; k < nrow; ++k) {
+                const double* r = h + 2 * (row_stride * (int64_t)k + e);
+                const double hr = r[0], hi = r[1];
+                acc[3 * k] = std::fma(ww, std::fma(hr, rr, hi * ri), acc[3 * k]);
+                acc[3 * k + 1] = std::fma(ww, std::fma(hr, ri, -(hi * rr)), acc[3 * k + 1]);
+                acc[3 * k + 2] = std::fma(ww, std::fma(hr, hr, hi * hi), acc[3 * k + 2]);
+            }
+            acc[3 * nrow] = std::fma(ww, std::fma(rr, rr, ri * ri), acc[3 * nrow]);
+        }
+    }
+    for (int o = 0; o < nout; ++o) {
+        double s = 0.0;
+        for (int64_t c = 0; c < nchunk; ++c) s += part[(size_t)c * nout + o];
+        out[o] = 4.0 * s;
+    }
+    return EFD_OK;
+}
+
 // efd_td_split's arithmetic (the translation unit is built with contraction off)
 static inline void td_split_pair(const double* z, int64_t n, int64_t k, double gain, double* hp,
                                  double* hc) {

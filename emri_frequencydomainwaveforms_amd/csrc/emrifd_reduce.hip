@@ -2,7 +2,8 @@
 // channels and numbers, and their C ABI (include/emrifd.h): the h+ / hx split
 // (efd_polarizations), the log-likelihood and inner product (efd_loglike, efd_inner_product),
 // the TD template's half-spectrum split and its fused likelihood (efd_td_split*), and the
-// Fisher matrix's Gram kernel (efd_fisher_gram). Shares only emrifd_common.h with the mode sum
+// Fisher matrix's Gram kernel (efd_fisher_gram), and the overlaps of many rows with one fixed
+// waveform (efd_overlap_rows). Shares only emrifd_common.h with the mode sum
 // (emrifd.hip) and the window path (emrifd_window.hip).
 
 #include "emrifd_common.h"
@@ -360,6 +361,119 @@ void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_str
     }
 }
 
+// ---- overlaps of many rows with one fixed waveform (efd_overlap_rows) ----------------------
+// A streaming reduction with no cross-row products, so the rows are never staged in LDS.
+// Workgroup (b, y) takes the 256-element chunks b, b + G, b + 2 G, ... (G = gridDim.x, a function
+// of nelem alone) of the NR rows of row block y: a thread loads its element of t, u, w once,
+// forms r = t - u, issues the 16-byte loads of its element of the block's NR rows together
+// (8 rows x 256 threads x 16 B = 32 KiB in flight per workgroup) and keeps 3 NR sums in
+// registers across the chunks. The epilogue is a butterfly over the 64 lanes, the four waves'
+// sums added as ((0 + 1) + 2) + 3, and one partial per (output, workgroup) at part[o G + b];
+// k_overlap_final adds each output's G partials in a fixed order and scales by 4.
+// What makes out[3k .. 3k + 2] a function of row k, t, u, w and nelem alone (the subset
+// promise): the element -> (workgroup, thread) map and both reduction orders depend on nelem
+// only, and a row's terms never see another row, the row block's width or its position; the
+// terms are the written fmas (contraction off), so every instantiation rounds alike.
+constexpr int OV_THREADS = 256;
+constexpr int OV_MAXB = 1024;   // workgroups per row block (4 per CU)
+constexpr int OV_RB = 8;        // rows per full block
+typedef double ov_d2 __attribute__((ext_vector_type(2)));
+
+// row0: the first row of block y = 0 of this launch; the |r|^2 sum belongs to row 0's block
+template <int NR>
+__global__ __launch_bounds__(OV_THREADS) void k_overlap_partial(
+    const double2* __restrict__ h, int64_t row_stride, int row0, int nrow,
+    const double2* __restrict__ t, const double2* __restrict__ u, const double* __restrict__ w,
+    int64_t nelem, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int NS = 3 * NR + 1;
+    __shared__ double sm[4][NS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int first = row0 + (int)blockIdx.y * NR;
+    const double2* hb = h + row_stride * (int64_t)first;
+    double re[NR], im[NR], nn[NR], rr2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) re[k] = im[k] = nn[k] = 0.0;
+
+    const int64_t nchunk = (nelem + OV_THREADS - 1) / OV_THREADS;
+    for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
+        const int64_t e = c * OV_THREADS + tid;
+        if (e >= nelem) continue;
+        double2 v[NR];
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {   // read once: streamed past the caches t, u, w stay in
+            const ov_d2 x = __builtin_nontemporal_load((const ov_d2*)(hb + (row_stride * k + e)));
+            v[k] = make_double2(x.x, x.y);
+        }
+        double2 r = t[e];
+        if (u) {
+            const double2 uv = u[e];
+            r.x -= uv.x;
+            r.y -= uv.y;
+        }
+        const double ww = w ? w[e] : 1.0;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            re[k] = fma(ww, fma(v[k].x, r.x, v[k].y * r.y), re[k]);
+            im[k] = fma(ww, fma(v[k].x, r.y, -(v[k].y * r.x)), im[k]);
+            nn[k] = fma(ww, fma(v[k].x, v[k].x, v[k].y * v[k].y), nn[k]);
+        }
+        if (first == 0) rr2 = fma(ww, fma(r.x, r.x, r.y * r.y), rr2);
+    }
+    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        double a = re[k], b = im[k], c = nn[k];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            a += __shfl_xor(a, m, 64);
+            b += __shfl_xor(b, m, 64);
+            c += __shfl_xor(c, m, 64);
+        }
+        if (lane == 0) {
+            sm[wv][3 * k] = a;
+            sm[wv][3 * k + 1] = b;
+            sm[wv][3 * k + 2] = c;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) rr2 += __shfl_xor(rr2, m, 64);
+    if (lane == 0) sm[wv][3 * NR] = rr2;
+    __syncthreads();
+    if (tid < NS) {
+        const double s = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
+        if (tid < 3 * NR)
+            part[(int64_t)(3 * first + tid) * gridDim.x + blockIdx.x] = s;
+        else if (first == 0)
+            part[(int64_t)(3 * nrow) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// one workgroup per output: the workgroups' partials in a fixed order, times 4
+__global__ void k_overlap_final(const double* __restrict__ part, int nb, double* __restrict__ out) {
+    __shared__ double red[256];
+    part += (int64_t)blockIdx.x * nb;
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[b];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = 4.0 * red[0];
+}
+
+template <int NR>
+void ov_launch(int nb, int blocks, hipStream_t st, const double2* h, int64_t row_stride, int row0,
+               int nrow, const double2* t, const double2* u, const double* w, int64_t nelem,
+               double* part) {
+    hipLaunchKernelGGL((k_overlap_partial<NR>), dim3(nb, blocks), dim3(OV_THREADS), 0, st, h,
+                       row_stride, row0, nrow, t, u, w, nelem, part);
+}
+
 }  // namespace
 
 void efdhip::launch_loglike_final(int rows, const double* part, int np, double* out,
@@ -458,6 +572,48 @@ int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_fisher_final, dim3((unsigned)(nparam * (nparam + 1) / 2)), dim3(256), 0,
                        st, scratch, nb, nparam, gram);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+static_assert(EFD_OVERLAP_SCRATCH == OV_MAXB * (3 * EFD_OVERLAP_MAX_ROWS + 1),
+              "EFD_OVERLAP_SCRATCH holds every workgroup's partial of every output");
+static_assert(EFD_OVERLAP_MAX_ROWS % OV_RB == 0 && OV_RB == 8, "ov_launch's instantiations");
+
+int efd_overlap_rows(const double* h, int64_t row_stride, int32_t nrow, const double* t,
+                     const double* u, const double* w, int64_t nelem, double* out,
+                     double* scratch, void* stream) {
+    if (nrow < 1 || nrow > EFD_OVERLAP_MAX_ROWS)
+        return fail(EFD_ERR_ARG, "efd_overlap_rows: nrow outside 1..64");
+    if (!h || !t || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_overlap_rows: NULL h, t, out or scratch");
+    if (nelem <= 0) return fail(EFD_ERR_ARG, "efd_overlap_rows: nelem <= 0");
+    if (row_stride < nelem) return fail(EFD_ERR_ARG, "efd_overlap_rows: row_stride < nelem");
+    // the partition is a function of nelem alone
+    const int nb = (int)std::min<int64_t>(OV_MAXB, (nelem + OV_THREADS - 1) / OV_THREADS);
+    const int full = nrow / OV_RB, rest = nrow % OV_RB;
+    hipStream_t st = (hipStream_t)stream;
+    const double2* h2 = (const double2*)h;
+    const double2* t2 = (const double2*)t;
+    const double2* u2 = (const double2*)u;
+    if (full > 0) {
+        ov_launch<OV_RB>(nb, full, st, h2, row_stride, 0, nrow, t2, u2, w, nelem, scratch);
+        HIP_TRY(hipGetLastError());
+    }
+    const int r0 = full * OV_RB;   // the last, narrower block
+    switch (rest) {
+        case 1: ov_launch<1>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 2: ov_launch<2>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 3: ov_launch<3>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 4: ov_launch<4>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 5: ov_launch<5>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 6: ov_launch<6>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        case 7: ov_launch<7>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
+        default: break;
+    }
+    if (rest > 0) HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(3 * nrow + 1)), dim3(256), 0, st, scratch,
+                       nb, out);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

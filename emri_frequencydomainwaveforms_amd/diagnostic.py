@@ -16,6 +16,9 @@ Same arguments, rules and errors as the reference:
   - right-sum rule: x = diff(f) with the first spacing repeated (:97-100); out = 4 sum
     Re(conj(a) b) / PSD * x, or the complex sum with complex=True (:103-110);
   - normalize: True -> / sqrt(<a,a><b,b>); "sig1"/"sig2" -> / <s,s> (:112-154).
+Further down: fisher / covariance / dh_dlambda / get_eigens (:189-451, 647-683) over
+efd_fisher_gram, and mismatch_criterion / vallisneri_criterion_cdf / cutler_vallisneri_bias /
+scale_snr (:489-644, 686-757, 760-840, 843-855) over efd_overlap_rows; see their section comments.
 The reduction runs in libemrifd.so (efd_inner_product); the weights x/PSD are formed once per
 call on the device. Inputs may be numpy arrays or torch tensors; the result is a Python float
 (complex with complex=True), like the reference's numpy scalar.
@@ -307,6 +310,20 @@ def fisher_weights(nbin, n_td=None, dt=None, df=None, f_arr=None, PSD="lisasens"
     return x / psd
 
 
+def _kernel_rows(rows, inner_product_kwargs, torch):
+    """(rows as the reduction kernels take them, complex128 [B][nchan][nbin]; n_td): with the dt
+    form the rows are time-domain, their real and imaginary parts are the reference's channels,
+    each rfft * dt with the DC bin dropped (diagnostic.py:57-73), and n_td is their length;
+    otherwise the rows as they are and n_td = None."""
+    dt_ = inner_product_kwargs.get("dt")
+    if dt_ is None:
+        return rows.to(torch.complex128), None
+    parts = [rows.real, rows.imag] if rows.is_complex() else [rows]
+    fd = torch.cat([torch.fft.rfft(p.to(torch.float64), dim=-1)[..., 1:] * dt_
+                    for p in parts], dim=1).contiguous()
+    return fd, rows.shape[-1]
+
+
 def fisher(waveform_model, params, eps, use_gpu=False, deriv_inds=None,
            parameter_transforms=None, waveform_kwargs={}, inner_product_kwargs={},
            return_derivs=False, accuracy=True):
@@ -324,17 +341,8 @@ def fisher(waveform_model, params, eps, use_gpu=False, deriv_inds=None,
     coef = stencil_coefficients(steps, accuracy)
     td = None
     if inner_product_kwargs.get("dt") is not None:
-        # time-domain rows: real and imaginary parts are the reference's channels, each
-        # rfft * dt with the DC bin dropped (diagnostic.py:57-73); the kernel takes those
-        n_td = rows.shape[-1]
         td = rows
-        parts = [rows.real, rows.imag] if rows.is_complex() else [rows]
-        dt_ = inner_product_kwargs["dt"]
-        rows = torch.cat([torch.fft.rfft(p.to(torch.float64), dim=-1)[..., 1:] * dt_
-                          for p in parts], dim=1).contiguous()
-    else:
-        n_td = None
-        rows = rows.to(torch.complex128)
+    rows, n_td = _kernel_rows(rows, inner_product_kwargs, torch)
     nchan, nbin = int(rows.shape[1]), int(rows.shape[2])
     w = fisher_weights(nbin, n_td=n_td, **inner_product_kwargs)
     w = w.expand(nchan, nbin).contiguous()
@@ -401,3 +409,272 @@ def covariance(*fisher_args, fish=None, diagonalize=False, return_fisher=False, 
         cov = vecs.T @ cov @ vecs
     out = [cov] + ([fish] if return_fisher else []) + ([dh] if with_derivs else [])
     return cov if len(out) == 1 else out
+
+
+# ---------------------------------------------------------------------------------------------
+# Vallisneri's mismatch criterion, its CDF, the Cutler-Vallisneri bias, scale_snr
+# (diagnostic.py:489-644, 686-757, 760-840, 843-855)
+# ---------------------------------------------------------------------------------------------
+# The reference draws one direction on the Fisher ellipsoid per mismatch_criterion call, makes the
+# perturbed waveform and takes three inner products of it with h_true (:622-638); the CDF loops
+# over num_samples such calls (:731-741). Here all directions are drawn first (one
+# np.random.normal(0, 1, d) per sample, in order: NumPy's global stream is consumed exactly as by
+# the reference's loop, so a seeded run has the same directions), the perturbed waveforms sit in
+# one device buffer (fisher_rows: one batched call where the model allows it), h_true is computed
+# once, and one efd_overlap_rows pass (reductions.Reducer.overlap_rows) gives every sample's
+# <h_k|h_true>, <h_k|h_k> and <h_true|h_true>; one host transfer brings them back. The bias
+# vector <dh_k | h_true - h_approx> (:812-823) is the same pass over fisher's derivatives, the
+# difference formed per element inside the kernel and never stored.
+# Kept from the reference: the signatures and keywords, the polar-angle wrap on indices 7 and 9 of
+# the TRANSFORMED vector with + pi on the azimuth beside it (:597-604; a transformed vector shorter
+# than 11 fails with IndexError, as there), abs(log ratio), np.unique / cumsum / np.interp(0.9).
+# Widened on purpose: a model may return a list of channels; parameter_transforms=None means
+# identity (the reference fails on None); vallisneri_criterion_cdf takes eigens= too (the
+# reference always recomputes them) and hands fisher's arguments given by keyword on to fisher;
+# the rows held at once are bounded by the device memory that
+# is free (_need_memory), larger sample counts go in blocks.
+
+
+def _transformed(params, parameter_transforms):
+    p = np.array(params, dtype=np.float64)
+    if parameter_transforms:
+        p = parameter_transforms.transform_base_parameters(p)
+    return np.asarray(p, dtype=np.float64)
+
+
+def _ellipsoid_offsets(num_samples, fish, eigens):
+    """vec_delta [num_samples][d] of mismatch_criterion (:579-587): x uniform on the unit sphere,
+    delta = sum_l x_l v[:, l] / sqrt(w_l), in the reference's order of operations."""
+    w, v = eigens
+    d = fish.shape[0]
+    us = [np.random.normal(0, 1, d) for _ in range(num_samples)]   # all draws first, in order
+    out = np.zeros((num_samples, d))
+    for k, u in enumerate(us):
+        x = u / np.sum(u ** 2) ** (0.5)
+        for l in range(d):
+            out[k] += x[l] * v[:, l] / np.sqrt(w[l])
+    return out
+
+
+def _perturbed_point(params, delta, deriv_inds, parameter_transforms):
+    """The transformed parameters moved by delta along deriv_inds, polar angles wrapped and
+    reflected (:590-604)."""
+    var = np.array(params, dtype=np.float64)
+    for i, ind in enumerate(deriv_inds):
+        var[ind] = var[ind] + delta[i]
+    var = _transformed(var, parameter_transforms).copy()
+    for val in (7, 9):
+        var[val] = var[val] % (2 * np.pi)
+        if var[val] > np.pi:
+            var[val] = 2 * np.pi - var[val]
+            var[val + 1] += np.pi
+    return var
+
+
+def _free_bytes(torch, dev):
+    return (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev)
+            - torch.cuda.memory_allocated(dev))
+
+
+def _vallisneri(num_samples, waveform_model, params, deriv_inds=None, inner_product_kwargs={},
+                waveform_kwargs={}, parameter_transforms=None, fish=None, eps=None, eigens=None,
+                return_fish=False, fisher_kwargs={}):
+    """mismatch_criterion's work for num_samples directions: (mism [n], ratio [n], fish, info)
+    with info the offsets, perturbed points and overlaps. The signature after num_samples is
+    mismatch_criterion's, so that its callers' arguments bind; return_fish is the caller's."""
+    params = np.asarray(params, dtype=np.float64)
+    if deriv_inds is None:
+        deriv_inds = np.arange(len(params))
+    if fish is None:
+        if eps is None:
+            raise ValueError("No numerical derivative step-sizes (eps) supplied for Fisher "
+                             "matrix generation.")
+        if isinstance(eps, float):
+            eps = np.full_like(params, eps)
+        fish = fisher(waveform_model=waveform_model, params=params, eps=eps,
+                      deriv_inds=deriv_inds, parameter_transforms=parameter_transforms,
+                      waveform_kwargs=waveform_kwargs,
+                      inner_product_kwargs=inner_product_kwargs, **fisher_kwargs)
+    fish = np.asarray(fish.get() if hasattr(fish, "get") else fish)
+    if eigens is None:
+        eigens = np.linalg.eig(fish)
+    deltas = _ellipsoid_offsets(num_samples, fish, eigens)
+    points = [_perturbed_point(params, dl, deriv_inds, parameter_transforms) for dl in deltas]
+    res, info = sample_overlaps(waveform_model, _transformed(params, parameter_transforms),
+                                points, waveform_kwargs, inner_product_kwargs)
+    mism, ratio, over = _criterion(res, deltas, fish)
+    info.update(offsets=deltas, points=np.asarray(points), overlaps=over)
+    return mism, ratio, fish, info
+
+
+def sample_overlaps(waveform_model, true_point, points, waveform_kwargs={},
+                    inner_product_kwargs={}, weights=None):
+    """efd_overlap_rows' numbers (host float64 [3 n + 1]: <h_k|h_true>, its imaginary partner and
+    <h_k|h_k> per point, then <h_true|h_true>) for the model at the n (transformed) points
+    against the model at true_point, and {"h_true", "weights"} (device). The waveforms come from
+    fisher_rows in blocks that fit the free device memory, h_true is computed once, every block
+    is one reduction pass and one host transfer brings all numbers back. weights: the kernel's
+    w as a device tensor [nchan][nbin], or None for inner_product's x / PSD from
+    inner_product_kwargs (fisher_weights)."""
+    torch = require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    red = _reducer(dev)
+    n = len(points)
+    t, _ = fisher_rows(waveform_model, [true_point], waveform_kwargs)   # (its own memory check)
+    row_bytes = 16 * int(t[0].numel())
+    t, n_td = _kernel_rows(t, inner_product_kwargs, torch)
+    nchan, nbin = int(t.shape[1]), int(t.shape[2])
+    if weights is None:
+        w = fisher_weights(nbin, n_td=n_td, **inner_product_kwargs)
+        w = w.expand(nchan, nbin).contiguous()
+    else:
+        w = weights
+    t = t[0].contiguous()
+    # rows held at once: a time-domain block also holds its transform
+    per_row = row_bytes * (1 if n_td is None else 3)
+    block = int(min(n, max(1, _free_bytes(torch, dev) // (2 * per_row))))
+    parts = []
+    for b0 in range(0, n, block):
+        rows, _ = fisher_rows(waveform_model, points[b0:b0 + block], waveform_kwargs)
+        rows, _ = _kernel_rows(rows, inner_product_kwargs, torch)
+        if tuple(rows.shape[1:]) != (nchan, nbin):
+            raise ValueError("the model's output changes shape between points")
+        flat = red.overlap_rows_flat(rows, t, None, w)
+        parts.append(flat if b0 + block >= n else flat[:-1])
+        del rows
+    res = torch.cat(parts).cpu().numpy()   # the one host transfer
+    return res, {"h_true": t, "weights": w}
+
+
+def _criterion(res, deltas, fish):
+    """(mism, ratio, over) per sample from sample_overlaps' numbers (:609-639)."""
+    rr = res[-1]
+    over = res[0:-1:3] / np.sqrt(res[2:-1:3] * rr)
+    prod = np.einsum("kj,ji,ki->k", deltas, fish, deltas)
+    ratio = over / (1 - 0.5 * prod / rr)
+    return (1.0 - over) / 2.0, ratio, over
+
+
+def mismatch_criterion(waveform_model, params, deriv_inds=None, inner_product_kwargs={},
+                       waveform_kwargs={}, parameter_transforms=None, fish=None, eps=None,
+                       eigens=None, return_fish=False, fisher_kwargs={}):
+    """Vallisneri's criterion for one random direction on the Fisher matrix's 1-sigma ellipsoid
+    (diagnostic.py:489-644): (mism, ratio[, fish]) with mism = (1 - over) / 2,
+    ratio = over / (1 - delta^T F delta / (2 <h_true|h_true>)), over the normalised overlap of the
+    perturbed waveform with h_true. fish is computed by fisher(eps=...) unless given; eigens is
+    its (eigenvalues, right eigenvectors) pair, np.linalg.eig's by default. The one-sample case of
+    vallisneri_criterion_cdf's code; see the section comment above."""
+    mism, ratio, fish, _ = _vallisneri(
+        1, waveform_model, params, deriv_inds=deriv_inds,
+        inner_product_kwargs=inner_product_kwargs, waveform_kwargs=waveform_kwargs,
+        parameter_transforms=parameter_transforms, fish=fish, eps=eps, eigens=eigens,
+        fisher_kwargs=fisher_kwargs)
+    if not return_fish:
+        return mism[0], ratio[0]
+    return mism[0], ratio[0], fish
+
+
+def vallisneri_criterion_cdf(*mismatch_args, num_samples=100, return_cdf=True,
+                             return_ratios=False, fish=None, precision=False, fisher_kwargs={},
+                             **mismatch_kwargs):
+    """The CDF of abs(log r) over num_samples directions and its 90th percentile
+    (diagnostic.py:686-757): (r_at_90[, quantiles, cdf][, ratios]). mismatch_args / _kwargs are
+    mismatch_criterion's; fish comes from fisher(*mismatch_args, **fisher_kwargs) unless given,
+    its eigen-pairs from get_eigens(fish, high_precision=precision) unless eigens= is given. All
+    samples' waveforms come from one batched call and one reduction pass."""
+    if fish is None:
+        # the reference's call, plus fisher's own arguments where they were given by keyword
+        # (there they reach mismatch_criterion only, and fisher fails for want of eps)
+        named = {k: mismatch_kwargs[k] for k in ("eps", "deriv_inds", "parameter_transforms",
+                                                 "waveform_kwargs", "inner_product_kwargs")
+                 if k in mismatch_kwargs}
+        fish = fisher(*mismatch_args, **named, **fisher_kwargs)
+    fish = np.asarray(fish.get() if hasattr(fish, "get") else fish)
+    eigens = mismatch_kwargs.pop("eigens", None)
+    if eigens is None:
+        eigens = get_eigens(fish, high_precision=precision)
+    mismatch_kwargs.pop("return_fish", None)
+    _, ratio, _, _ = _vallisneri(num_samples, *mismatch_args, fish=fish, eigens=eigens,
+                                 **mismatch_kwargs)
+    ratios = np.abs(np.log(ratio))
+    quantiles, counts = np.unique(ratios, return_counts=True)
+    cdf = np.cumsum(counts).astype(np.double) / ratios.size
+    r_at_90 = np.interp(0.9, cdf, quantiles)
+    out = (r_at_90,)
+    if return_cdf:
+        out += (quantiles, cdf)
+    if return_ratios:
+        out += (ratios,)
+    return out
+
+
+def cutler_vallisneri_bias(waveform_model_true, waveform_model_approx, params, eps,
+                           in_diagnostics=None, fish=None, deriv_inds=None, return_fisher=False,
+                           return_derivs=False, return_cov=False, parameter_transforms=None,
+                           waveform_true_kwargs={}, waveform_approx_kwargs={},
+                           inner_product_kwargs={}):
+    """Cutler-Vallisneri systematic bias of an approximate template (diagnostic.py:760-840):
+    syst_vec[k] = <dh_k | h_true - h_approx>, bias = cov @ syst_vec; (syst_vec, bias), or the
+    list [syst_vec, bias, fish, cov, dh] with the entries the return_* flags ask for. cov, fish
+    and dh come from covariance(..., return_fisher=True, return_derivs=True) on the true model,
+    or cov, h_true and dh from the in_diagnostics dict. One efd_overlap_rows pass over dh forms
+    the difference per element; h_true - h_approx is never stored."""
+    torch = require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    params = np.asarray(params, dtype=np.float64)
+    if deriv_inds is None:
+        deriv_inds = np.arange(len(params))
+    if isinstance(eps, float):
+        eps = np.full_like(params, eps)
+    params_true = _transformed(params, parameter_transforms)
+    if in_diagnostics is None:
+        h_true, _ = fisher_rows(waveform_model_true, [params_true], waveform_true_kwargs)
+        cov, fish, dh = covariance(waveform_model_true, params, eps, return_fisher=True,
+                                   return_derivs=True, deriv_inds=deriv_inds,
+                                   parameter_transforms=parameter_transforms,
+                                   waveform_kwargs=waveform_true_kwargs,
+                                   inner_product_kwargs=inner_product_kwargs)
+    else:
+        cov = in_diagnostics["cov"]
+        h_true = _stack_channels(in_diagnostics["h_true"], torch, dev)
+        h_true = h_true.reshape((1, 1, -1) if h_true.dim() == 1 else (1,) + tuple(h_true.shape))
+        dh = in_diagnostics["dh"]
+    h_approx, _ = fisher_rows(waveform_model_approx, [params_true], waveform_approx_kwargs)
+    rows = torch.as_tensor(dh, device=dev)
+    if rows.dim() == 2:   # a one-channel model's derivatives [P][n]
+        rows = rows[:, None, :]
+    rows, n_td = _kernel_rows(rows, inner_product_kwargs, torch)
+    t, _ = _kernel_rows(h_true, inner_product_kwargs, torch)
+    u, _ = _kernel_rows(h_approx, inner_product_kwargs, torch)
+    nchan, nbin = int(rows.shape[1]), int(rows.shape[2])
+    if tuple(t.shape[1:]) != (nchan, nbin) or tuple(u.shape[1:]) != (nchan, nbin):
+        raise ValueError("cutler_vallisneri_bias: h_true, h_approx and the derivatives differ "
+                         "in shape")
+    w = fisher_weights(nbin, n_td=n_td, **inner_product_kwargs).expand(nchan, nbin).contiguous()
+    out, _ = _reducer(dev).overlap_rows(rows.contiguous(), t[0].contiguous(), u[0].contiguous(),
+                                        w)
+    syst_vec = out[:, 0].cpu().numpy()
+    bias = np.dot(cov, syst_vec)
+    if True not in [return_fisher, return_cov, return_derivs]:
+        return syst_vec, bias
+    returns = [syst_vec, bias]
+    if return_fisher:
+        returns.append(fish)
+    if return_cov:
+        returns.append(cov)
+    if return_derivs:
+        returns.append(dh)
+    return returns
+
+
+def scale_snr(target_snr, sig, *snr_args, return_orig_snr=False, **snr_kwargs):
+    """The signal's channels scaled to the target SNR (diagnostic.py:843-855): a list of
+    channels, or (list, original snr) with return_orig_snr. Host arithmetic on top of snr()."""
+    snr_out = snr(sig, *snr_args, **snr_kwargs)
+    factor = target_snr / snr_out
+    if isinstance(sig, list) is False:
+        sig = [sig]
+    out = [sig_i * factor for sig_i in sig]
+    if return_orig_snr:
+        return (out, snr_out)
+    return out

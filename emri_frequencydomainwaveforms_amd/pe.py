@@ -224,6 +224,81 @@ def fisher_covariance(s, eps, accuracy=True, waveform_model=None, return_derivs=
     return F, dg.covariance(fish=F), info
 
 
+def vallisneri_check(s, eps, num_samples=100, seed=None, accuracy=True, waveform_model=None):
+    """Vallisneri's test of fisher_covariance's matrix for a PESetup's source (lisatools
+    vallisneri_criterion_cdf, diagnostic.py:686-757, in the six sampled coordinates and with
+    fisher_covariance's weights: the likelihood's grid and PSD, no weight on the bins it drops):
+    (r_at_90, ratios, mismatches, info). num_samples directions on the 1-sigma ellipsoid, each
+    moved point through s.transform to the generator's 14 parameters (polar angles wrapped as the
+    reference does, :597-604), all waveforms from one batched call (diagnostic.fisher_rows) and
+    one efd_overlap_rows pass against the waveform at s.truth6. ratios = |log r| per sample,
+    r_at_90 their CDF's 90th percentile, mismatches = (1 - overlap) / 2. seed: seeds NumPy's
+    global stream for the draws and puts its state back afterwards; None draws from the stream as
+    it stands. info: "fisher", "cov", "offsets" (the drawn parameter offsets [n][6]), "points",
+    "overlaps", "stencil_agreement" (accuracy=True), "h_true" and "weights" (device).
+    eps: fisher_covariance's steps, named as in lisatools."""
+    from . import diagnostic as dg
+    model = s.gen if waveform_model is None else waveform_model
+    F, cov, finfo = fisher_covariance(s, eps, accuracy=accuracy, waveform_model=model)
+    tr = _SampledToWaveform(s.transform)
+    state = np.random.get_state() if seed is not None else None
+    if seed is not None:
+        np.random.seed(seed)
+    try:
+        deltas = dg._ellipsoid_offsets(num_samples, F, np.linalg.eig(F))
+    finally:
+        if state is not None:
+            np.random.set_state(state)
+    points = [dg._perturbed_point(s.truth6, dl, range(6), tr) for dl in deltas]
+    res, info = dg.sample_overlaps(model, tr.transform_base_parameters(s.truth6), points,
+                                   s.kwargs, weights=finfo["weights"])
+    mism, ratio, over = dg._criterion(res, deltas, F)
+    ratios = np.abs(np.log(ratio))
+    quantiles, counts = np.unique(ratios, return_counts=True)
+    r_at_90 = float(np.interp(0.9, np.cumsum(counts).astype(np.double) / ratios.size, quantiles))
+    info.update(fisher=F, cov=cov, offsets=deltas, points=np.asarray(points), overlaps=over)
+    if "stencil_agreement" in finfo:
+        info["stencil_agreement"] = finfo["stencil_agreement"]
+    return r_at_90, ratios, mism, info
+
+
+def systematic_bias(s, eps, approx_kwargs=None, approx_model=None, accuracy=True):
+    """Cutler-Vallisneri bias of an approximate template for a PESetup's source (lisatools
+    cutler_vallisneri_bias, diagnostic.py:760-840, in the six sampled coordinates with
+    fisher_covariance's weights): (syst_vec, bias, info), syst_vec[k] = <dh_k | h_true -
+    h_approx> from one efd_overlap_rows pass over fisher_covariance's derivatives (the difference
+    is formed inside the kernel), bias = cov @ syst_vec, info["bias_sigma"] = bias / sqrt(diag
+    cov); info also holds "fisher", "cov" and "stencil_agreement" (accuracy=True).
+    The approximate template at the true parameters: approx_model (any callable on the same grid,
+    e.g. the generator of a template="td" setup; default s.gen) called with s.kwargs overridden
+    by approx_kwargs (e.g. a coarser mode threshold, or another setting that keeps f_arr).
+    eps is fisher_covariance's step argument, named as in lisatools; the waveform keyword of the
+    same name (the mode-selection threshold) is reachable only through
+    approx_kwargs={"eps": ...}."""
+    from . import diagnostic as dg
+    torch = dg.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    F, cov, finfo = fisher_covariance(s, eps, accuracy=accuracy, return_derivs=True)
+    p14 = _SampledToWaveform(s.transform).transform_base_parameters(s.truth6)
+    t, _ = dg.fisher_rows(s.gen, [p14], s.kwargs)
+    u, _ = dg.fisher_rows(s.gen if approx_model is None else approx_model, [p14],
+                          {**s.kwargs, **(approx_kwargs or {})})
+    dh = finfo["derivs"]
+    if tuple(u.shape) != tuple(t.shape):
+        raise ValueError(f"systematic_bias: the approximate template has shape "
+                         f"{tuple(u.shape[1:])}, the true one {tuple(t.shape[1:])}")
+    out, _ = dg._reducer(dev).overlap_rows(dh, t[0].to(torch.complex128).contiguous(),
+                                           u[0].to(torch.complex128).contiguous(),
+                                           finfo["weights"])
+    syst_vec = out[:, 0].cpu().numpy()
+    bias = cov @ syst_vec
+    info = {"fisher": F, "cov": cov, "bias_sigma": bias / np.sqrt(np.diag(cov)),
+            "weights": finfo["weights"]}
+    if "stencil_agreement" in finfo:
+        info["stencil_agreement"] = finfo["stencil_agreement"]
+    return syst_vec, bias, info
+
+
 class MemoizedUpstream:
     """Memoise a generator's host upstream (trajectory, amplitudes, Ylm, mode selection: the
     stand-ins of trajectory.py / amplitude.py) per parameter set, so repeated likelihood calls on

@@ -1,11 +1,12 @@
 """Device reductions of the likelihood side: thin wrappers of efd_loglike / efd_inner_product /
-efd_fisher_gram.
+efd_fisher_gram / efd_overlap_rows.
 
 All run in libemrifd.so (HIP, gfx950) as fixed-partition two-pass reductions, so results are
 bitwise reproducible. They read the channels in place: h, d complex128 [nchan][nbin], w float64
 [nchan][nbin] (all contiguous, on one device); the result stays on the device until the caller
 asks for it, so a batch of walkers costs one host synchronisation. fisher_gram takes the rows of
-a Fisher matrix's stencil points and returns the whole [nparam][nparam] matrix from one pass.
+a Fisher matrix's stencil points and returns the whole [nparam][nparam] matrix from one pass;
+overlap_rows takes many rows and one fixed waveform and returns every row's products with it.
 """
 
 import ctypes
@@ -121,3 +122,62 @@ class Reducer:
                                             gram.data_ptr(), scr.data_ptr(), self._stream()),
                    "efd_fisher_gram", self.lib)
         return gram
+
+    def overlap_rows(self, rows, t, u=None, w=None):
+        """Every row's overlap with one fixed waveform r = t - u (u None: r = t) in one pass
+        (efd_overlap_rows; the reduction of lisatools' mismatch_criterion, diagnostic.py:622-638,
+        and of cutler_vallisneri_bias, :812-823): (out, rr) with out float64 [nrow][3] =
+        4 sum_e w (Re conj(h_k) r, Im conj(h_k) r, |h_k|^2) and rr = 4 sum_e w |r|^2 a 0-d
+        tensor, both views of one device tensor of 3 nrow + 1 doubles (overlap_rows_flat returns
+        that one: a single host transfer brings everything back).
+
+        rows: complex128 [nrow][...] as fisher_gram's (contiguous rows a fixed stride apart);
+        t, u: contiguous complex128 with a row's nelem elements; w: float64 with nelem elements,
+        or None (w = 1). More than EFD_OVERLAP_MAX_ROWS rows go in several calls; a row's numbers
+        are bitwise what any other split gives (the kernel's subset promise).
+        """
+        res = self.overlap_rows_flat(rows, t, u, w)
+        nrow = int(rows.shape[0])
+        return res[:3 * nrow].view(nrow, 3), res[3 * nrow]
+
+    def overlap_rows_flat(self, rows, t, u=None, w=None):
+        """overlap_rows' numbers as efd_overlap_rows lays them out: float64 [3 nrow + 1] on the
+        device, (re, im, nn) per row and then rr."""
+        torch = self.torch
+        if (rows.dtype != torch.complex128 or rows.device != self.device or rows.dim() < 2
+                or rows.shape[0] < 1 or not rows[0].is_contiguous()):
+            raise ValueError(f"rows: expected complex128 [nrow][...] on {self.device} with "
+                             "contiguous rows")
+        nrow = int(rows.shape[0])
+        nelem = int(rows[0].numel())
+        stride = int(rows.stride(0)) if nrow > 1 else nelem
+        if nelem == 0 or stride < nelem:
+            raise ValueError("rows: empty or overlapping rows")
+        ptrs = []
+        for x, name, dtype in ((t, "t", torch.complex128), (u, "u", torch.complex128),
+                               (w, "w", torch.float64)):
+            if x is None:
+                if name == "t":
+                    raise ValueError("t: a complex128 tensor is required")
+                ptrs.append(None)
+                continue
+            if x.numel() != nelem:
+                raise ValueError(f"{name}: expected {nelem} elements, got {x.numel()}")
+            ptrs.append(self._check(x, name, dtype, tuple(x.shape)))
+        scr = getattr(self, "_scr_ov", None)
+        if scr is None:
+            scr = self._scr_ov = torch.empty(_lib.EFD_OVERLAP_SCRATCH, dtype=torch.float64,
+                                             device=self.device)
+        M = _lib.EFD_OVERLAP_MAX_ROWS
+        ncall = (nrow + M - 1) // M
+        # call c writes its 3 n + 1 doubles at 3 c M: its |r|^2 lands on the next call's first
+        # slot and is overwritten by it, the last call's stays at 3 nrow
+        res = torch.empty(3 * nrow + 1, dtype=torch.float64, device=self.device)
+        base = torch.view_as_real(rows).data_ptr()
+        for c in range(ncall):
+            n = min(M, nrow - c * M)
+            _lib.check(self.lib.efd_overlap_rows(base + 16 * stride * c * M, stride, n, *ptrs,
+                                                 nelem, res.data_ptr() + 8 * 3 * c * M,
+                                                 scr.data_ptr(), self._stream()),
+                       "efd_overlap_rows", self.lib)
+        return res

@@ -488,6 +488,40 @@ int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t
                     double* scratch, void* stream);
 
 /*
+ * Overlaps of many rows with one fixed waveform in one pass: the reduction of lisatools'
+ * mismatch_criterion / vallisneri_criterion_cdf (diagnostic.py:489-757: every perturbed
+ * waveform's normalised overlap with h_true, :622-638) and of cutler_vallisneri_bias
+ * (:812-823: <dh_k | h_true - h_approx>, the difference formed on the fly).
+ *   r[e]        = t[e] - u[e]                       (u == NULL: r = t)
+ *   out[3k + 0] = 4 * sum_e w[e] Re(conj(h_k[e]) r[e])
+ *   out[3k + 1] = 4 * sum_e w[e] Im(conj(h_k[e]) r[e])
+ *   out[3k + 2] = 4 * sum_e w[e] |h_k[e]|^2          k = 0 .. nrow - 1
+ *   out[3 nrow] = 4 * sum_e w[e] |r[e]|^2
+ * h: nrow complex rows of nelem elements (efd_fisher_gram's conventions: row r at
+ * h + 2 r row_stride doubles, row_stride >= nelem, 16-byte aligned; a slice of a wider buffer is
+ * fine), 1 <= nrow <= EFD_OVERLAP_MAX_ROWS; t, u: contiguous complex [nelem]; w: real [nelem] or
+ * NULL (w = 1); out: 3 nrow + 1 device doubles; scratch: EFD_OVERLAP_SCRATCH device doubles.
+ * Every element of h is read once; t, u, w once per block of 8 rows. Terms, as written (no
+ * contraction): fma(w, fma(hr, rr, hi ri), .), fma(w, fma(hr, ri, -(hi rr)), .),
+ * fma(w, fma(hr, hr, hi hi), .). Promises:
+ *   - no atomics, a fixed partition that depends on nelem only and fixed reduction orders:
+ *     bitwise reproducible;
+ *   - out[3k .. 3k + 2] is a function of row k, t, u, w and nelem alone: the same row gives the
+ *     same bits alone, at another position, in another row block or beside other rows (so a
+ *     caller may split more rows than EFD_OVERLAP_MAX_ROWS over several calls without changing
+ *     any number);
+ *   - the cross terms out[3k], out[3k + 1] are exactly 0 when u equals t bit for bit, and when
+ *     row k's support is disjoint from r's.
+ * EFD_ERR_ARG before any launch: nrow out of range, NULL h, t, out or scratch, nelem <= 0,
+ * row_stride < nelem.
+ */
+#define EFD_OVERLAP_MAX_ROWS 64
+#define EFD_OVERLAP_SCRATCH 197632
+int efd_overlap_rows(const double* h, int64_t row_stride, int32_t nrow, const double* t,
+                     const double* u, const double* w, int64_t nelem, double* out,
+                     double* scratch, void* stream);
+
+/*
  * CPU twins: the same algorithm on HOST pointers, C++17 + OpenMP
  * (csrc/emrifd_cpu.cpp, linked into libemrifd.so). Signatures are those of the HIP entry points;
  * `stream`, `workspace` and `scratch` are accepted for parity and ignored (pass NULL / 0). The
@@ -512,6 +546,9 @@ int efd_inner_product_cpu(const double* a, const double* b, const double* w, int
 int efd_fisher_gram_cpu(const double* h, int64_t row_stride, int32_t nparam, int32_t npoint,
                         const double* coef, const double* w, int64_t nelem, double* dh,
                         double* gram, double* scratch, void* stream);
+int efd_overlap_rows_cpu(const double* h, int64_t row_stride, int32_t nrow, const double* t,
+                         const double* u, const double* w, int64_t nelem, double* out,
+                         double* scratch, void* stream);
 int efd_td_split_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
                      const uint8_t* keep, double* out, int64_t out_stride, void* stream);
 int efd_td_split_loglike_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,

@@ -1,0 +1,457 @@
+"""efd_overlap_rows on the device: the C ABI against its CPU twin over the shapes at which the
+kernel changes path (one element, around a wave, around the 256-element chunk, several
+workgroups, more chunks than workgroups; one row, around the row block of 8, the maximum of 64),
+its exact zeros and its reproducibility and subset promises; the Python surface
+(diagnostic.mismatch_criterion / vallisneri_criterion_cdf / cutler_vallisneri_bias / scale_snr)
+against lisatools' own results (tests/golden/overlap_golden.npz); and the EMRI level
+(pe.vallisneri_check, pe.systematic_bias).
+
+Tolerance of device against twin: 1e-12 sqrt(nn_k rr) on the cross terms and 1e-12 relative on
+the norms, the inner-product tolerance of tests/test_gpu_likelihood.py and test_gpu_fisher.py
+(both sides form the same float64 terms; only the summation order differs). Against the fixture:
+over / mism 1e-11 absolute, ratio / r_at_90 1e-11 relative, syst_vec[k] 1e-11 sqrt(F_kk |dh|^2),
+bias 1e-9 sqrt(cov_kk); a plain numpy evaluation of the same sums lies 3e-15, 6e-15, 1e-14, 1e-15
+and 3e-17 from the reference (tests/golden/make_golden_overlap.py's print)."""
+
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import overlap_ref as orf
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-12
+random_case = orf.random_case
+RB = 8   # the kernel's row block
+
+
+def _dev(a):
+    return None if a is None else torch.as_tensor(a, device="cuda")
+
+
+def _p(t):
+    if t is None:
+        return None
+    return ctypes.c_void_p((torch.view_as_real(t) if t.is_complex() else t).data_ptr())
+
+
+def overlap_gpu(rows, t, u, w, nelem=None, row_stride=None):
+    """efd_overlap_rows through ctypes on device copies of host arrays (as orf.overlap_cpu)."""
+    from emri_frequencydomainwaveforms_amd import _lib
+    lib = _lib.load()
+    rows = np.ascontiguousarray(rows, dtype=np.complex128)
+    nrow = rows.shape[0]
+    row_stride = rows.shape[1] if row_stride is None else row_stride
+    nelem = rows.shape[1] if nelem is None else nelem
+    d_rows, d_t, d_u, d_w = _dev(rows), _dev(t), _dev(u), _dev(w)
+    out = torch.full((3 * nrow + 1,), float("nan"), dtype=torch.float64, device="cuda")
+    scr = torch.empty(_lib.EFD_OVERLAP_SCRATCH, dtype=torch.float64, device="cuda")
+    rc = lib.efd_overlap_rows(_p(d_rows), row_stride, nrow, _p(d_t), _p(d_u), _p(d_w), nelem,
+                              _p(out), _p(scr), None)
+    torch.cuda.synchronize()
+    return rc, out.cpu().numpy()
+
+
+def _close(out, ref):
+    return orf.cross_err(out, ref) <= RTOL and orf.norm_err(out, ref) <= RTOL
+
+
+@pytest.mark.parametrize("nrow", [1, RB - 1, RB, RB + 1, 64])
+@pytest.mark.parametrize("nelem", [1, 63, 64, 65, 255, 256, 257, 8194])
+def test_matches_cpu_twin(nelem, nrow):
+    rows, t, u, w = random_case(nelem, nrow)
+    rc, out = overlap_gpu(rows, t, u, w)
+    rc2, ref = orf.overlap_cpu(rows, t, u, w)
+    assert rc == 0 and rc2 == 0
+    assert _close(out, ref)
+
+
+def test_more_chunks_than_workgroups():
+    """524,293 elements are 2049 chunks for 1024 workgroups: the grid-stride loop wraps."""
+    rows, t, u, w = random_case(524293, 2)
+    rc, out = overlap_gpu(rows, t, u, w)
+    rc2, ref = orf.overlap_cpu(rows, t, u, w)
+    assert rc == 0 and rc2 == 0
+    assert _close(out, ref)
+
+
+@pytest.mark.parametrize("nelem,nrow", [(257, 9), (8194, 5)])
+def test_variants_match_cpu_twin(nelem, nrow):
+    rows, t, u, w = random_case(nelem, nrow, seed=1, pad=3)
+    tight = np.ascontiguousarray(rows[:, :nelem])
+    # rows three elements apart from contiguous
+    rc, out = overlap_gpu(rows, t, u, w, nelem=nelem, row_stride=nelem + 3)
+    _, ref = orf.overlap_cpu(rows, t, u, w, nelem=nelem, row_stride=nelem + 3)
+    assert rc == 0 and _close(out, ref)
+    assert np.array_equal(overlap_gpu(tight, t, u, w)[1], out)   # the stride changes nothing
+    for uu, ww in ((None, w), (u, None), (None, None)):         # u = NULL, w = NULL
+        rc, o = overlap_gpu(tight, t, uu, ww)
+        _, r = orf.overlap_cpu(tight, t, uu, ww)
+        assert rc == 0 and _close(o, r)
+    wz = w.copy()                                                # masked bins
+    wz[::3] = 0.0
+    wz[nelem // 2:nelem // 2 + 70] = 0.0
+    rc, o = overlap_gpu(tight, t, u, wz)
+    _, r = orf.overlap_cpu(tight, t, u, wz)
+    assert rc == 0 and _close(o, r)
+
+
+def test_exact_zeros():
+    nelem, nrow = 8194, 9
+    rows, t, u, w = random_case(nelem, nrow, seed=2)
+    rc, out = overlap_gpu(rows, t, t.copy(), w)     # u == t bit for bit: r = 0
+    assert rc == 0
+    assert np.all(out[0:-1:3] == 0.0) and np.all(out[1:-1:3] == 0.0) and out[-1] == 0.0
+    assert np.all(out[2:-1:3] > 0.0)
+    dis = rows.copy()                               # rows on the first half, r on the second
+    dis[:, nelem // 2:] = 0.0
+    t2, u2 = t.copy(), u.copy()
+    t2[:nelem // 2] = u2[:nelem // 2] = 0.0
+    for uu in (u2, None):
+        rc, out = overlap_gpu(dis, t2, uu, w)
+        assert rc == 0
+        assert np.all(out[0:-1:3] == 0.0) and np.all(out[1:-1:3] == 0.0)
+        assert np.all(out[2:-1:3] > 0.0) and out[-1] > 0.0
+
+
+def test_bitwise_reproducible_and_subset_invariant():
+    from emri_frequencydomainwaveforms_amd.reductions import Reducer
+    nelem = 8194
+    rows, t, u, w = random_case(nelem, 100, seed=3)
+    rc, A = overlap_gpu(rows[:64], t, u, w)
+    rc2, B = overlap_gpu(rows[:64], t, u, w)
+    assert rc == 0 and rc2 == 0 and np.array_equal(A, B)
+    # row k alone, moved to position 0, and among 64: the same bits (k in a full block, k the
+    # block's last row, k in the first block)
+    for k in (0, 13, 23, 63):
+        rc, one = overlap_gpu(rows[k:k + 1], t, u, w)
+        assert rc == 0 and np.array_equal(one[:3], A[3 * k:3 * k + 3]) and one[3] == A[-1]
+        moved = np.concatenate([rows[k:k + 1], rows[:5]])
+        rc, m = overlap_gpu(moved, t, u, w)
+        assert rc == 0 and np.array_equal(m[:3], A[3 * k:3 * k + 3])
+        assert np.array_equal(m[3:6], A[0:3])      # and row 0 in a narrower block, at position 1
+    # 100 rows through the Reducer are two calls: every row as in a single call
+    red = Reducer()
+    d_rows, d_t, d_u, d_w = _dev(rows), _dev(t), _dev(u), _dev(w)
+    out, rr = red.overlap_rows(d_rows, d_t, d_u, d_w)
+    assert tuple(out.shape) == (100, 3) and rr.dim() == 0 and out.is_cuda
+    out = out.cpu().numpy()
+    assert np.array_equal(out[:64].reshape(-1), A[:-1]) and float(rr) == A[-1]
+    rc, C = overlap_gpu(rows[64:], t, u, w)
+    assert rc == 0 and np.array_equal(out[64:].reshape(-1), C[:-1]) and float(rr) == C[-1]
+    o1, r1 = red.overlap_rows(d_rows[77:78], d_t, d_u, d_w)
+    assert np.array_equal(o1.cpu().numpy()[0], out[77]) and float(r1) == float(rr)
+    flat = red.overlap_rows_flat(d_rows, d_t, d_u, d_w).cpu().numpy()
+    assert np.array_equal(flat[:-1], out.reshape(-1)) and flat[-1] == float(rr)
+
+
+def test_reducer_checks_its_arguments():
+    from emri_frequencydomainwaveforms_amd.reductions import Reducer
+    red = Reducer()
+    rows = torch.zeros((3, 2, 10), dtype=torch.complex128, device="cuda")
+    t = torch.zeros((2, 10), dtype=torch.complex128, device="cuda")
+    w = torch.ones((2, 10), dtype=torch.float64, device="cuda")
+    red.overlap_rows(rows, t, None, w)
+    wide = torch.zeros((3, 12), dtype=torch.complex128, device="cuda")
+    red.overlap_rows(wide[:, :7], t.reshape(-1)[:7])   # a slice of a wider buffer is fine
+    for bad in (dict(rows=rows.to(torch.complex64)), dict(rows=rows.cpu()),
+                dict(rows=rows[:, :, ::2]), dict(t=t[:, :9]), dict(t=None),
+                dict(u=t.to(torch.complex64)), dict(w=w[:1]), dict(w=w.to(torch.float32)),
+                dict(t=t.t())):
+        kw = dict(rows=rows, t=t, u=None, w=w)
+        kw.update(bad)
+        with pytest.raises(ValueError):
+            red.overlap_rows(kw["rows"], kw["t"], kw["u"], kw["w"])
+
+
+def test_argument_errors_are_host_side():
+    from emri_frequencydomainwaveforms_amd import _lib
+    lib = _lib.load()
+    fake = ctypes.c_void_p(16)   # never dereferenced: validation fails first
+    buf = ctypes.create_string_buffer(256)
+
+    def call(h=fake, stride=8, nrow=2, t=fake, nelem=8, out=fake, scr=fake):
+        rc = lib.efd_overlap_rows(h, stride, nrow, t, None, None, nelem, out, scr, None)
+        lib.efd_last_error(buf, 256)
+        return rc, buf.value
+
+    for kw in (dict(nrow=0), dict(nrow=65), dict(nrow=-1), dict(h=None), dict(t=None),
+               dict(out=None), dict(scr=None), dict(nelem=0), dict(nelem=-5), dict(stride=7)):
+        rc, msg = call(**kw)
+        assert rc == _lib.EFD_ERR_ARG and b"efd_overlap_rows" in msg, (kw, msg)
+
+
+# ---- the lisatools surface on the fixture's toy model -------------------------------------
+@pytest.fixture(scope="module")
+def gold():
+    g = orf.golden()
+    ipk = dict(f_arr=g["f"], PSD=g["psd"])
+    return g, orf.toy_model(g["f"]), orf.ToyTransform(), ipk
+
+
+def test_mismatch_criterion_seeded_loop(gold):
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    eig = (g["evals"], g["evecs"])
+    n = len(g["mism"])
+    np.random.seed(int(g["seed"]))
+    got = np.array([diagnostic.mismatch_criterion(model, g["params"], parameter_transforms=T,
+                                                  fish=g["fisher"], eigens=eig,
+                                                  inner_product_kwargs=ipk) for _ in range(n)])
+    assert g["reflected"].any()   # reflected samples are among those compared
+    assert np.abs(got[:, 0] - g["mism"]).max() <= 1e-11
+    assert np.abs(got[:, 1] / g["ratio"] - 1).max() <= 1e-11
+    # its own Fisher matrix from eps, returned on request; a list-returning model: the same bits
+    np.random.seed(int(g["seed"]))
+    m0, r0, F = diagnostic.mismatch_criterion(model, g["params"], parameter_transforms=T,
+                                              eps=g["eps"], eigens=eig, return_fish=True,
+                                              inner_product_kwargs=ipk)
+    d = np.sqrt(np.diag(g["fisher"]))
+    assert np.max(np.abs(F - g["fisher"]) / np.outer(d, d)) <= 1e-12
+    assert m0 == got[0, 0]   # the overlap does not involve the matrix (the eigen-pairs are given)
+    np.random.seed(int(g["seed"]))
+    ml, rl = diagnostic.mismatch_criterion(lambda *p: list(model(*p)), g["params"],
+                                           parameter_transforms=T, fish=g["fisher"], eigens=eig,
+                                           inner_product_kwargs=ipk)
+    assert ml == got[0, 0] and rl == got[0, 1]
+    with pytest.raises(ValueError, match="step-sizes"):
+        diagnostic.mismatch_criterion(model, g["params"], parameter_transforms=T,
+                                      inner_product_kwargs=ipk)
+
+
+def test_vallisneri_criterion_cdf(gold):
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    n = len(g["mism"])
+    np.random.seed(int(g["seed"]))
+    r90, quant, cdf, ratios = diagnostic.vallisneri_criterion_cdf(
+        model, g["params"], num_samples=n, return_ratios=True, fish=g["fisher"],
+        eigens=(g["evals"], g["evecs"]), parameter_transforms=T, inner_product_kwargs=ipk)
+    # |log ratio| inherits ratio's relative 1e-11 as an absolute error (ratio is within 0.2 of 1)
+    assert np.abs(ratios - g["cdf_ratios"]).max() <= 1e-11
+    assert abs(r90 / g["r_at_90"] - 1) <= 1e-11
+    assert np.array_equal(cdf, g["cdf"]) and np.abs(quant - g["quantiles"]).max() <= 1e-11
+    np.random.seed(int(g["seed"]))
+    only = diagnostic.vallisneri_criterion_cdf(
+        lambda *p: list(model(*p)), g["params"], num_samples=n, return_cdf=False,
+        fish=g["fisher"], eigens=(g["evals"], g["evecs"]), parameter_transforms=T,
+        inner_product_kwargs=ipk)
+    assert only == (r90,)
+
+
+def test_cutler_vallisneri_bias(gold):
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    approx = orf.toy_model(g["f"], orf.APPROX_SCALE)
+    p, eps = g["params"], g["eps"]
+    tp = T.transform_base_parameters(p)
+    dn = 4.0 * np.sum(orf.weights(g["f"], g["psd"], 2)
+                      * np.abs(model(*tp) - approx(*tp)).ravel() ** 2)
+    tol_s = 1e-11 * np.sqrt(np.diag(g["fisher"]) * dn)
+    tol_b = 1e-9 * np.sqrt(np.diag(g["cov"]))
+
+    syst, bias = diagnostic.cutler_vallisneri_bias(model, approx, p, eps,
+                                                   parameter_transforms=T,
+                                                   inner_product_kwargs=ipk)
+    assert np.all(np.abs(syst - g["syst_vec"]) <= tol_s)
+    assert np.all(np.abs(bias - g["bias"]) <= tol_b)
+    # the list form, with a list-returning pair of models
+    lst = lambda m: (lambda *q: list(m(*q)))
+    s2, b2, F, cov, dh = diagnostic.cutler_vallisneri_bias(
+        lst(model), lst(approx), p, eps, parameter_transforms=T, inner_product_kwargs=ipk,
+        return_fisher=True, return_cov=True, return_derivs=True)
+    assert np.array_equal(s2, syst) and np.array_equal(b2, bias)
+    assert dh.is_cuda and tuple(dh.shape) == (5, 2, len(g["f"]))
+    d = np.sqrt(np.diag(g["fisher"]))
+    assert np.max(np.abs(F - g["fisher"]) / np.outer(d, d)) <= 1e-12
+    # the in_diagnostics route: the caller's cov, h_true and derivatives
+    s3, b3 = diagnostic.cutler_vallisneri_bias(
+        model, approx, p, eps, parameter_transforms=T, inner_product_kwargs=ipk,
+        in_diagnostics=dict(cov=g["cov"], h_true=model(*tp), dh=dh))
+    assert np.array_equal(s3, syst)
+    assert np.all(np.abs(b3 - g["bias"]) <= tol_b)
+    # an approximate model equal to the true one: exactly no bias
+    s0, b0 = diagnostic.cutler_vallisneri_bias(model, model, p, eps, parameter_transforms=T,
+                                               inner_product_kwargs=ipk)
+    assert np.all(s0 == 0.0) and np.all(b0 == 0.0)
+
+
+def test_scale_snr(gold):
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    h = model(*T.transform_base_parameters(g["params"]))
+    sig = [h[0], h[1]]
+    out, orig = diagnostic.scale_snr(30.0, sig, return_orig_snr=True, **ipk)
+    assert abs(orig / g["scale_snr_orig"] - 1) <= 1e-12
+    assert abs(diagnostic.snr(diagnostic.scale_snr(30.0, sig, **ipk), **ipk) - 30.0) <= 1e-12 * 30
+    ref = g["scale_snr_sample"]
+    assert np.abs(np.array(out)[:, ::64] - ref).max() <= 1e-12 * np.abs(ref).max()
+    one = diagnostic.scale_snr(30.0, h[0], **ipk)   # a bare channel comes back as a list
+    assert isinstance(one, list) and len(one) == 1
+
+
+def _right_sum(f):
+    x = np.empty_like(f)
+    x[1:] = np.diff(f)
+    x[0] = x[1]
+    return x
+
+
+def test_dt_form_against_numpy():
+    """Time-domain rows (inner_product's dt form, diagnostic.py:57-73) with
+    test_diagnostic_fisher_dt_form's signal: rfft * dt with the DC bin dropped feeds the kernel.
+    Tolerance by that test's reasoning (the transforms round at ~1e-15 of |h|, the differences
+    keep >= 1e-3 of it): 1e-12, asserted at 1e-10, here of sqrt(F_kk |dh|^2) for the bias vector
+    and absolute for the overlaps."""
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    n, dt = 4096, 5.0
+    t = np.arange(n) * dt
+
+    def make(scale):
+        return lambda A, f0: scale * A * np.sin(2 * np.pi * f0 * t) \
+            * np.exp(-0.5 * ((t - 1e4) / 4e3) ** 2)
+
+    model, approx = make(1.0), make(1.01)
+    p, eps = np.array([1.0, 0.01]), np.array([1e-3, 1e-6])
+    f = np.fft.rfftfreq(n, dt)[1:]
+    psd = 1.0 + (1e-2 / f) ** 2
+    ipk = dict(dt=dt, PSD=psd)
+    w = _right_sum(f) / psd
+    fd = lambda x: np.fft.rfft(x, axis=-1)[..., 1:] * dt
+
+    syst, bias, F, dh = diagnostic.cutler_vallisneri_bias(
+        model, approx, p, eps, inner_product_kwargs=ipk, return_fisher=True, return_derivs=True)
+    assert tuple(dh.shape) == (2, n)
+    D = fd(dh.cpu().numpy())
+    diff = fd(model(*p)) - fd(approx(*p))
+    ref = 4.0 * np.real(np.einsum("ke,e,e->k", D.conj(), diff, w))
+    dn = 4.0 * np.sum(w * np.abs(diff) ** 2)
+    assert np.all(np.abs(syst - ref) <= 1e-10 * np.sqrt(np.diag(F) * dn))
+
+    # the criterion needs an 11-vector for its polar wrap (as the reference)
+    class Pad:
+        def transform_base_parameters(self, q):
+            return np.concatenate([q, np.zeros(9)])
+
+    wide = lambda A, f0, *rest: model(A, f0)
+    evals, evecs = np.linalg.eig(F)
+    np.random.seed(5)
+    mism, ratio = diagnostic.mismatch_criterion(wide, p, parameter_transforms=Pad(), fish=F,
+                                                eigens=(evals, evecs), inner_product_kwargs=ipk)
+    np.random.seed(5)
+    u = np.random.normal(0, 1, 2)
+    x = u / np.sum(u ** 2) ** 0.5
+    delta = sum(x[l] * evecs[:, l] / np.sqrt(evals[l]) for l in range(2))
+    a, b = fd(model(*(p + delta))), fd(model(*p))
+    ip = lambda y, z: 4.0 * np.real(np.sum(y.conj() * z * w))
+    over = ip(a, b) / np.sqrt(ip(a, a) * ip(b, b))
+    assert abs(mism - (1 - over) / 2) <= 1e-10
+    want = over / (1 - 0.5 * delta @ F @ delta / ip(b, b))
+    assert abs(ratio / want - 1) <= 1e-10
+
+
+def test_checks_device_memory(gold, monkeypatch):
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    total = torch.cuda.mem_get_info()[1]
+    monkeypatch.setattr(torch.cuda, "mem_get_info", lambda *a, **k: (0, total))
+    monkeypatch.setattr(torch.cuda, "memory_reserved", lambda *a, **k: 0)
+    monkeypatch.setattr(torch.cuda, "memory_allocated", lambda *a, **k: 0)
+    need = 16 * 2 * len(g["f"])   # h_true's row is the first thing held
+    with pytest.raises(ValueError, match=str(need)):
+        diagnostic.vallisneri_criterion_cdf(
+            model, g["params"], num_samples=4, fish=g["fisher"], parameter_transforms=T,
+            inner_product_kwargs=ipk)
+
+
+def test_samples_go_in_blocks_when_memory_is_short(gold, monkeypatch):
+    """Free memory for two rows at a time: 7 samples take four passes and give the bits of one."""
+    from emri_frequencydomainwaveforms_amd import diagnostic
+    g, model, T, ipk = gold
+    pts, _ = orf.perturbed_points(g["params"], g["offsets"][:7], T)
+    tp = T.transform_base_parameters(g["params"])
+    whole, _ = diagnostic.sample_overlaps(model, tp, pts, inner_product_kwargs=ipk)
+    row = 16 * 2 * len(g["f"])
+    monkeypatch.setattr(diagnostic, "_free_bytes", lambda *a: 4 * row)
+    calls = []
+    real = diagnostic.fisher_rows
+    monkeypatch.setattr(diagnostic, "fisher_rows",
+                        lambda m, p, *a, **k: (calls.append(len(p)), real(m, p, *a, **k))[1])
+    parts, _ = diagnostic.sample_overlaps(model, tp, pts, inner_product_kwargs=ipk)
+    assert calls == [1, 2, 2, 2, 1]
+    assert np.array_equal(parts, whole)
+
+
+# ---- EMRI level -----------------------------------------------------------------------------
+SETUP = dict(Tobs=0.05, dt=20.0, eps=1e-2, M=3e5, mu=10.0, e0=0.3, nwalkers=4, ntemps=1)
+
+
+@pytest.fixture(scope="module")
+def emri():
+    from emri_frequencydomainwaveforms_amd import pe
+    s = pe.setup(**SETUP)
+    steps = np.where(s.truth6 != 0.0, 1e-6 * np.abs(s.truth6), 1e-6)
+    F, cov, info = pe.fisher_covariance(s, steps, return_derivs=True)
+    return s, steps, F, cov, info
+
+
+def test_emri_vallisneri_check(emri):
+    from emri_frequencydomainwaveforms_amd import diagnostic, pe
+    s, steps, F, cov, finfo = emri
+    r90, ratios, mism, info = pe.vallisneri_check(s, steps, num_samples=6, seed=11)
+    assert np.array_equal(info["fisher"], F) and info["offsets"].shape == (6, 6)
+    assert info["stencil_agreement"] == finfo["stencil_agreement"]
+    assert ratios.shape == (6,) and mism.shape == (6,) and np.isfinite(r90)
+    # the same seed gives the same bits, and leaves NumPy's global stream where it was
+    np.random.seed(3)
+    r90b, ratios_b, mism_b, info_b = pe.vallisneri_check(s, steps, num_samples=6, seed=11)
+    assert np.random.normal() == np.random.RandomState(3).normal()
+    assert r90b == r90 and np.array_equal(ratios_b, ratios) and np.array_equal(mism_b, mism)
+    assert np.array_equal(info_b["offsets"], info["offsets"])
+    # batched rows against the generic one-call-per-sample route
+    _, ratios_g, mism_g, info_g = pe.vallisneri_check(
+        s, steps, num_samples=6, seed=11, waveform_model=lambda *a, **k: s.gen(*a, **k))
+    assert np.array_equal(ratios_g, ratios) and np.array_equal(mism_g, mism)
+    assert np.array_equal(info_g["overlaps"], info["overlaps"])
+    # each overlap against inner_product(normalize=True) on the same weights (zero weight = an
+    # infinite PSD on the bins the likelihood drops; both channels share the PSD)
+    w = finfo["weights"]
+    assert torch.equal(w[0], w[1])
+    psd = torch.as_tensor(np.asarray(s.like.psd[0]), device=w.device).clone()
+    psd[w[0] == 0.0] = float("inf")
+    h_true = s.gen(*s.truth14, **s.kwargs)
+    for k in range(6):
+        h = s.gen(*info["points"][k], **s.kwargs)
+        want = diagnostic.inner_product([h[0], h[1]], [h_true[0], h_true[1]],
+                                        f_arr=s.like.freqs, PSD=psd, normalize=True)
+        assert abs(info["overlaps"][k] - want) <= 1e-12
+
+
+def test_emri_systematic_bias_zero_and_linear_identity(emri):
+    """approx_model = the template itself: exactly no bias. approx_model = h_true - sum_i
+    delta_i D_i with D fisher_covariance's derivatives and delta_i = 1 / sqrt(F_ii): syst_vec =
+    F delta within 1e-10 sqrt(F_kk delta^T F delta) (the difference h_true - h_approx loses
+    SNR / sqrt(delta^T F delta) times 1e-16, test_emri_cross_kernel_identity_with_loglike's
+    reasoning)."""
+    from emri_frequencydomainwaveforms_amd import pe
+    s, steps, F, cov, finfo = emri
+    syst, bias, info = pe.systematic_bias(s, steps, approx_model=s.gen)
+    assert np.all(syst == 0.0) and np.all(bias == 0.0) and np.all(info["bias_sigma"] == 0.0)
+    assert np.array_equal(info["fisher"], F)
+    delta = 1.0 / np.sqrt(np.diag(F))
+    D = finfo["derivs"]
+    dd = (torch.as_tensor(delta, device=D.device)[:, None, None] * D).sum(0)
+
+    def approx(*a, **k):
+        return torch.stack(s.gen(*a, **k)) - dd
+
+    syst, bias, info = pe.systematic_bias(s, steps, approx_model=approx)
+    want = F @ delta
+    assert np.all(np.abs(syst - want) <= 1e-10 * np.sqrt(np.diag(F) * (delta @ F @ delta)))
+    assert np.array_equal(info["bias_sigma"], bias / np.sqrt(np.diag(cov)))
+    # approx_kwargs reach the template: a coarser mode threshold moves it
+    syst_c, _, _ = pe.systematic_bias(s, steps, approx_kwargs={"eps": 1e-1})
+    assert np.all(np.isfinite(syst_c)) and np.any(syst_c != 0.0)
