@@ -26,6 +26,9 @@ EFD_BATCH_MAX = 16
 EFD_HANN_ROWS_MAX = 16   # efd_hann_loglike's rows per call (include/emrifd.h)
 EFD_HANN_LOCAL_PARTIALS = 4096   # efd_hann_loglike_local's scratch doubles per row
 EFD_TD_SPLIT_SCRATCH = 1024   # efd_td_split_loglike's scratch doubles per row
+EFD_PAIR_MAX_ROWS = 64
+EFD_PAIR_SCRATCH = 655360   # the pair statistics' scratch doubles (1024 chunks x 64 rows x 10)
+EFD_WINDOW_MAX_ROWS = 16   # efd_window_rows' windows per call
 
 # every symbol include/emrifd.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -74,6 +77,9 @@ EXPORTED_SYMBOLS = (
     "efd_inner_product",
     "efd_fisher_gram",
     "efd_overlap_rows",
+    "efd_pair_stats",
+    "efd_td_split_pair_stats",
+    "efd_window_rows",
     "efd_modesum_cpu",
     "efd_modesum_cpu_stats",
     "efd_spline_build_cpu",
@@ -84,6 +90,9 @@ EXPORTED_SYMBOLS = (
     "efd_overlap_rows_cpu",
     "efd_td_split_cpu",
     "efd_td_split_loglike_cpu",
+    "efd_pair_stats_cpu",
+    "efd_td_split_pair_stats_cpu",
+    "efd_window_rows_cpu",
     "efd_cpu_threads",
     "efd_cpu_last_error",
     "efd_host_trajectory",
@@ -296,6 +305,15 @@ def load(path=None):
     for name in ("efd_overlap_rows", "efd_overlap_rows_cpu"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp]
+    for name in ("efd_pair_stats", "efd_pair_stats_cpu"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, i64, vp, i64, i32, i32, i64, vp, vp, vp, vp]
+    for name in ("efd_td_split_pair_stats", "efd_td_split_pair_stats_cpu"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, i64, i64, i32, dbl, vp, i64, vp, vp, vp, vp, vp]
+    for name in ("efd_window_rows", "efd_window_rows_cpu"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, i64, ctypes.POINTER(vp), i32, vp, i64, vp]
     if hasattr(lib, "efd_modesum_cpu"):   # the host twins (csrc/emrifd_cpu.cpp)
         lib.efd_modesum_cpu.restype = ctypes.c_int
         lib.efd_modesum_cpu.argtypes = [ctypes.POINTER(ModesumArgs), vp, sz, vp]

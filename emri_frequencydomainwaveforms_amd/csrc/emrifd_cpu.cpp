@@ -1093,4 +1093,116 @@ int efd_td_split_loglike_cpu(const double* Z, int64_t stride, int64_t n, int32_t
     return EFD_OK;
 }
 
+// efd_pair_stats' terms, the same nesting (include/emrifd.h): abi's term is the difference of
+// two rounded products, so it is exactly 0 when b == a
+static inline void pair_term(double w, double ar, double ai, double br, double bi, double* s) {
+    const double dr = ar - br, di = ai - bi;
+    s[0] = std::fma(w, std::fma(ar, ar, ai * ai), s[0]);
+    s[1] = std::fma(w, std::fma(br, br, bi * bi), s[1]);
+    s[2] = std::fma(w, std::fma(ar, br, ai * bi), s[2]);
+    s[3] = std::fma(w, ar * bi - ai * br, s[3]);
+    s[4] = std::fma(w, std::fma(dr, dr, di * di), s[4]);
+}
+
+// Both pair statistics: fixed chunks of 4096 bins, their partials added in chunk order, so the
+// result does not depend on the thread count, and a row's numbers do not depend on other rows.
+// zsplit: b is the split of row r of Z (efd_td_split's arithmetic and keep rule), nchan = 2.
+static void pair_stats_rows(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
+                            bool zsplit, int64_t n, double gain, const uint8_t* keep,
+                            int32_t nrow, int32_t nchan, int64_t nbin, const double* w,
+                            double* out) {
+    const int ns = 5 * nchan;
+    const int64_t chunk = 4096;
+    const int64_t nchunk = (nbin + chunk - 1) / chunk;
+    std::vector<double> part((size_t)nchunk * ns);
+    for (int32_t r = 0; r < nrow; ++r) {
+        const double* ar = a + 2 * (int64_t)r * a_stride;
+        const double* br = b + 2 * (int64_t)r * b_stride;
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+        for (int64_t c = 0; c < nchunk; ++c) {
+            double* s = part.data() + (size_t)c * ns;
+            for (int i = 0; i < ns; ++i) s[i] = 0.0;
+            const int64_t k1 = std::min(nbin, (c + 1) * chunk);
+            for (int64_t k = c * chunk; k < k1; ++k) {
+                const double ww = w ? w[k] : 1.0;
+                if (zsplit) {
+                    double hp[2] = {0.0, 0.0}, hc[2] = {0.0, 0.0};
+                    if (!keep || keep[k]) td_split_pair(br, n, k, gain, hp, hc);
+                    pair_term(ww, ar[2 * k], ar[2 * k + 1], hp[0], hp[1], s);
+                    pair_term(ww, ar[2 * (nbin + k)], ar[2 * (nbin + k) + 1], hc[0], hc[1], s + 5);
+                } else {
+                    for (int ch = 0; ch < nchan; ++ch) {
+                        const int64_t e = 2 * (ch * nbin + k);
+                        pair_term(ww, ar[e], ar[e + 1], br[e], br[e + 1], s + 5 * ch);
+                    }
+                }
+            }
+        }
+        for (int i = 0; i < ns; ++i) {
+            double s = 0.0;
+            for (int64_t c = 0; c < nchunk; ++c) s += part[(size_t)c * ns + i];
+            out[(int64_t)r * ns + i] = 4.0 * s;
+        }
+        if (zsplit && (n & 1) == 0) {   // the Nyquist bin: in no channel, but a NaN there counts
+            const double vr = br[n], vi = br[n + 1];
+            if (vr != vr || vi != vi)
+                for (int ch = 0; ch < 2; ++ch)
+                    for (int i = 1; i < 5; ++i) out[(int64_t)r * ns + 5 * ch + i] = vr + vi;
+        }
+    }
+}
+
+int efd_pair_stats_cpu(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
+                       int32_t nrow, int32_t nchan, int64_t nbin, const double* w, double* out,
+                       double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (nrow < 1 || nrow > EFD_PAIR_MAX_ROWS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_pair_stats_cpu: nrow outside 1..64");
+    if (nchan != 1 && nchan != 2)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_pair_stats_cpu: nchan must be 1 or 2");
+    if (!a || !b || !out) return efdcpu::fail(EFD_ERR_ARG, "efd_pair_stats_cpu: NULL a, b or out");
+    if (nbin <= 0) return efdcpu::fail(EFD_ERR_ARG, "efd_pair_stats_cpu: nbin <= 0");
+    if (a_stride < nchan * nbin || b_stride < nchan * nbin)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_pair_stats_cpu: stride < nchan nbin");
+    pair_stats_rows(a, a_stride, b, b_stride, false, 0, 1.0, nullptr, nrow, nchan, nbin, w, out);
+    return EFD_OK;
+}
+
+int efd_td_split_pair_stats_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
+                                double gain, const double* a, int64_t a_stride, const double* w,
+                                const uint8_t* keep, double* out, double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (!Z || !a || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_pair_stats_cpu: NULL Z, a or out");
+    if (n < 1) return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_pair_stats_cpu: n < 1");
+    if (rows < 1 || rows > EFD_PAIR_MAX_ROWS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_td_split_pair_stats_cpu: rows outside 1..64");
+    const int64_t nb = (n + 1) / 2;
+    if (stride < n || a_stride < 2 * nb)
+        return efdcpu::fail(EFD_ERR_ARG,
+                            "efd_td_split_pair_stats_cpu: stride < n or a_stride < 2 nb");
+    pair_stats_rows(a, a_stride, Z, stride, true, n, gain, keep, rows, 2, nb, w, out);
+    return EFD_OK;
+}
+
+int efd_window_rows_cpu(const double* h, int64_t n, const double* const* win, int32_t nwin,
+                        double* out, int64_t out_stride, void* stream) {
+    (void)stream;
+    if (!h || !win || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_window_rows_cpu: NULL h, win or out");
+    if (n < 1 || nwin < 1 || nwin > EFD_WINDOW_MAX_ROWS || out_stride < n)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_window_rows_cpu: n, nwin or out_stride");
+    for (int32_t j = 0; j < nwin; ++j) {
+        const double* wj = win[j];
+        double* o = out + 2 * (int64_t)j * out_stride;
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+        for (int64_t k = 0; k < n; ++k) {
+            const double x = wj ? wj[k] : 1.0;
+            o[2 * k] = wj ? x * h[2 * k] : h[2 * k];
+            o[2 * k + 1] = wj ? x * h[2 * k + 1] : h[2 * k + 1];
+        }
+    }
+    return EFD_OK;
+}
+
 }  // extern "C"

@@ -3,8 +3,9 @@
 // (efd_polarizations), the log-likelihood and inner product (efd_loglike, efd_inner_product),
 // the TD template's half-spectrum split and its fused likelihood (efd_td_split*), and the
 // Fisher matrix's Gram kernel (efd_fisher_gram), and the overlaps of many rows with one fixed
-// waveform (efd_overlap_rows). Shares only emrifd_common.h with the mode sum
-// (emrifd.hip) and the window path (emrifd_window.hip).
+// waveform (efd_overlap_rows), and the statistics of many row pairs of the mode-by-mode study
+// (efd_pair_stats, efd_td_split_pair_stats, efd_window_rows). Shares only emrifd_common.h with
+// the mode sum (emrifd.hip) and the window path (emrifd_window.hip).
 
 #include "emrifd_common.h"
 
@@ -474,6 +475,148 @@ void ov_launch(int nb, int blocks, hipStream_t st, const double2* h, int64_t row
                        row_stride, row0, nrow, t, u, w, nelem, part);
 }
 
+// ---- statistics of many (a, b) row pairs (efd_pair_stats, efd_td_split_pair_stats) ----------
+// A streaming reduction again: workgroup (c, r) takes bins [c chunk, (c + 1) chunk) of row pair
+// r, both channels, so a thread loads w[k] (and keep[k]) once for its bin and keeps five sums per
+// channel in registers. The row is the slow grid dimension: the workgroups of one chunk follow
+// each other on one XCD (the chunk count is a multiple of 8 once there are that many) and find w
+// and keep in its cache, while a and b (or Z) are read once and streamed past it. The epilogue
+// is k_overlap_partial's: a butterfly over the 64 lanes, the four waves' sums added as
+// ((0 + 1) + 2) + 3, one partial per (output, workgroup) at part[o gridDim.x + c]; then
+// k_overlap_final adds each output's partials in a fixed order and scales by 4.
+// What makes a row's numbers a function of that row pair, w and the sizes alone: the bin ->
+// (workgroup, thread) map and both reduction orders depend on nbin (n) only, a row's terms never
+// see another row or its own position, and the terms are the written ones (contraction off).
+constexpr int PS_THREADS = 256;
+constexpr int PS_MAXB = 1024;   // chunks per row (4 workgroups per CU for a single row)
+
+// one bin of one channel into its five sums. abi's term is the difference of two rounded
+// products, not an fma: ar bi and ai br are then the same number when b == a, so it is exactly 0
+__device__ __forceinline__ void ps_term(double w, const double2 a, const double2 b, double* s) {
+#pragma clang fp contract(off)
+    const double dr = a.x - b.x, di = a.y - b.y;
+    s[0] = fma(w, fma(a.x, a.x, a.y * a.y), s[0]);
+    s[1] = fma(w, fma(b.x, b.x, b.y * b.y), s[1]);
+    s[2] = fma(w, fma(a.x, b.x, a.y * b.y), s[2]);
+    s[3] = fma(w, a.x * b.y - a.y * b.x, s[3]);
+    s[4] = fma(w, fma(dr, dr, di * di), s[4]);
+}
+
+__device__ __forceinline__ double2 ps_stream(const double2* p) {
+    const ov_d2 x = __builtin_nontemporal_load((const ov_d2*)p);
+    return make_double2(x.x, x.y);
+}
+
+// the workgroup's 5 NCHAN sums to part[((r NCHAN + c) 5 + i) gridDim.x + blockIdx.x]
+template <int NCHAN>
+__device__ __forceinline__ void ps_store(double (&s)[NCHAN][5], double* __restrict__ part) {
+    constexpr int NS = 5 * NCHAN;
+    __shared__ double sm[4][NS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (int c = 0; c < NCHAN; ++c)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            double v = s[c][i];
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+            if (lane == 0) sm[wv][5 * c + i] = v;
+        }
+    __syncthreads();
+    if (tid < NS) {
+        const double v = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
+        part[((int64_t)blockIdx.y * NS + tid) * gridDim.x + blockIdx.x] = v;
+    }
+}
+
+template <int NCHAN>
+__global__ __launch_bounds__(PS_THREADS) void k_pair_stats(
+    const double2* __restrict__ a, int64_t a_stride, const double2* __restrict__ b,
+    int64_t b_stride, const double* __restrict__ w, int64_t nbin, int64_t chunk,
+    double* __restrict__ part) {
+    const double2* ar = a + (int64_t)blockIdx.y * a_stride;
+    const double2* br = b + (int64_t)blockIdx.y * b_stride;
+    const int64_t k0 = (int64_t)blockIdx.x * chunk;
+    const int64_t k1 = min(nbin, k0 + chunk);
+    double s[NCHAN][5];
+#pragma unroll
+    for (int c = 0; c < NCHAN; ++c)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s[c][i] = 0.0;
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += PS_THREADS) {
+        double2 av[NCHAN], bv[NCHAN];
+#pragma unroll
+        for (int c = 0; c < NCHAN; ++c) {
+            av[c] = ps_stream(ar + (c * nbin + k));
+            bv[c] = ps_stream(br + (c * nbin + k));
+        }
+        const double ww = w ? w[k] : 1.0;
+#pragma unroll
+        for (int c = 0; c < NCHAN; ++c) ps_term(ww, av[c], bv[c], s[c]);
+    }
+    ps_store<NCHAN>(s, part);
+}
+
+// the same with b = the split of row r of Z (k_td_split's arithmetic and keep rule), kept in
+// registers: an ascending stream Z[k] and a descending one Z[n - k], as k_td_split_loglike
+__global__ __launch_bounds__(PS_THREADS) void k_td_split_pair_stats(
+    const double2* __restrict__ Z, int64_t stride, int64_t n, int64_t nb, int64_t chunk,
+    double gain, const double2* __restrict__ a, int64_t a_stride, const double* __restrict__ w,
+    const uint8_t* __restrict__ keep, double* __restrict__ part) {
+    const double2* z = Z + (int64_t)blockIdx.y * stride;
+    const double2* ar = a + (int64_t)blockIdx.y * a_stride;
+    const int64_t k0 = (int64_t)blockIdx.x * chunk;
+    const int64_t k1 = min(nb, k0 + chunk);
+    double s[2][5];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s[c][i] = 0.0;
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += PS_THREADS) {
+        const double2 a0 = ps_stream(ar + k), a1 = ps_stream(ar + (nb + k));
+        double2 hp = make_double2(0.0, 0.0), hc = hp;
+        if (keep == nullptr || keep[k] != 0)
+            td_split_pair(ps_stream(z + k), ps_stream(z + (k == 0 ? 0 : n - k)), gain, hp, hc);
+        const double ww = w ? w[k] : 1.0;
+        ps_term(ww, a0, hp, s[0]);
+        ps_term(ww, a1, hc, s[1]);
+    }
+    // even n: the Nyquist bin belongs to neither channel (k_td_split_loglike's rule); a NaN
+    // there still poisons every number of the row that depends on b
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
+        const double2 v = z[n / 2];
+        if (v.x != v.x || v.y != v.y)
+            for (int c = 0; c < 2; ++c)
+                for (int i = 1; i < 5; ++i) s[c][i] = v.x + v.y;
+    }
+    ps_store<2>(s, part);
+}
+
+// out[j][k] = win[j][k] h[k]: every window of one series from one read of it
+struct wr_ptrs {
+    const double* p[EFD_WINDOW_MAX_ROWS];
+};
+
+__global__ __launch_bounds__(256) void k_window_rows(const double2* __restrict__ h, int64_t n,
+                                                     wr_ptrs win, int nwin,
+                                                     double2* __restrict__ out,
+                                                     int64_t out_stride) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const double2 v = h[k];
+    for (int j = 0; j < nwin; ++j) {
+        const double* wj = win.p[j];
+        double2 o = v;
+        if (wj) {
+            const double x = wj[k];
+            o = make_double2(x * v.x, x * v.y);
+        }
+        out[(int64_t)j * out_stride + k] = o;
+    }
+}
+
 }  // namespace
 
 void efdhip::launch_loglike_final(int rows, const double* part, int np, double* out,
@@ -664,6 +807,93 @@ int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t row
                        (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)d, w, scratch);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+static_assert(EFD_PAIR_SCRATCH == PS_MAXB * EFD_PAIR_MAX_ROWS * 2 * 5,
+              "EFD_PAIR_SCRATCH holds every workgroup's partial of every output");
+
+// the chunks of the pair statistics for nbin bins: a function of nbin alone (whole rounds of the
+// 8 XCDs once there are that many), each a multiple of 256 bins and at least 1024 where nbin
+// allows (four 16-byte loads per operand and thread)
+static int pair_chunks(int64_t nbin, int64_t* chunk) {
+    int64_t np = std::min<int64_t>(PS_MAXB, (nbin + 1023) / 1024);
+    if (np > 8) np -= np % 8;
+    int64_t c = (nbin + np - 1) / np;
+    c = (c + PS_THREADS - 1) / PS_THREADS * PS_THREADS;
+    *chunk = c;
+    return (int)((nbin + c - 1) / c);
+}
+
+int efd_pair_stats(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
+                   int32_t nrow, int32_t nchan, int64_t nbin, const double* w, double* out,
+                   double* scratch, void* stream) {
+    if (nrow < 1 || nrow > EFD_PAIR_MAX_ROWS)
+        return fail(EFD_ERR_ARG, "efd_pair_stats: nrow outside 1..64");
+    if (nchan != 1 && nchan != 2) return fail(EFD_ERR_ARG, "efd_pair_stats: nchan must be 1 or 2");
+    if (!a || !b || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_pair_stats: NULL a, b, out or scratch");
+    if (nbin <= 0 || nbin > ((int64_t)1 << 40))
+        return fail(EFD_ERR_ARG, "efd_pair_stats: nbin out of range");
+    if (a_stride < nchan * nbin || b_stride < nchan * nbin)
+        return fail(EFD_ERR_ARG, "efd_pair_stats: stride < nchan nbin");
+    int64_t chunk = 0;
+    const int np = pair_chunks(nbin, &chunk);
+    hipStream_t st = (hipStream_t)stream;
+    if (nchan == 1)
+        hipLaunchKernelGGL((k_pair_stats<1>), dim3((unsigned)np, (unsigned)nrow), dim3(PS_THREADS),
+                           0, st, (const double2*)a, a_stride, (const double2*)b, b_stride, w, nbin,
+                           chunk, scratch);
+    else
+        hipLaunchKernelGGL((k_pair_stats<2>), dim3((unsigned)np, (unsigned)nrow), dim3(PS_THREADS),
+                           0, st, (const double2*)a, a_stride, (const double2*)b, b_stride, w, nbin,
+                           chunk, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(nrow * nchan * 5)), dim3(256), 0, st,
+                       scratch, np, out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_td_split_pair_stats(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                            const double* a, int64_t a_stride, const double* w,
+                            const uint8_t* keep, double* out, double* scratch, void* stream) {
+    if (!Z || !a || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: NULL Z, a, out or scratch");
+    if (n < 1 || n > ((int64_t)1 << 40))
+        return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: n out of range");
+    if (rows < 1 || rows > EFD_PAIR_MAX_ROWS)
+        return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: rows outside 1..64");
+    if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: stride < n");
+    const int64_t nb = (n + 1) / 2;
+    if (a_stride < 2 * nb) return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: a_stride < 2 nb");
+    int64_t chunk = 0;
+    const int np = pair_chunks(nb, &chunk);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_td_split_pair_stats, dim3((unsigned)np, (unsigned)rows), dim3(PS_THREADS),
+                       0, st, (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)a,
+                       a_stride, w, keep, scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(rows * 10)), dim3(256), 0, st, scratch, np,
+                       out);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+int efd_window_rows(const double* h, int64_t n, const double* const* win, int32_t nwin,
+                    double* out, int64_t out_stride, void* stream) {
+    if (!h || !win || !out) return fail(EFD_ERR_ARG, "efd_window_rows: NULL h, win or out");
+    if (n < 1 || n > ((int64_t)1 << 38))
+        return fail(EFD_ERR_ARG, "efd_window_rows: n out of range");
+    if (nwin < 1 || nwin > EFD_WINDOW_MAX_ROWS)
+        return fail(EFD_ERR_ARG, "efd_window_rows: nwin outside 1..16");
+    if (out_stride < n) return fail(EFD_ERR_ARG, "efd_window_rows: out_stride < n");
+    wr_ptrs p;
+    for (int j = 0; j < EFD_WINDOW_MAX_ROWS; ++j) p.p[j] = j < nwin ? win[j] : nullptr;
+    hipLaunchKernelGGL(k_window_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const double2*)h, n, p, (int)nwin, (double2*)out,
+                       out_stride);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

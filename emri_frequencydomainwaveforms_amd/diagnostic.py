@@ -3,6 +3,9 @@
     inner_product(sig1, sig2, dt=None, df=None, f_arr=None, PSD="lisasens", PSD_args=(),
                   PSD_kwargs={}, normalize=False, use_gpu=False, complex=False)   :14-157
     snr(sig1, *args, data=None, use_gpu=False, **kwargs)                         :160-171
+    pair_statistics(sig1_rows, sig2_rows, dt=None, df=None, f_arr=None, PSD="lisasens",
+                    PSD_args=(), PSD_kwargs={})     many pairs' SNR, overlap, mismatch and logL of
+                    the difference from one pass (efd_pair_stats; check_mode_by_mode.py:292-326)
 
 Same arguments, rules and errors as the reference:
   - signals are one channel or a list of channels (equal counts, else ValueError);
@@ -65,6 +68,16 @@ def _psd_array(PSD, freqs, PSD_args, PSD_kwargs, torch, device):
                      "if noise weighting is included in a signal.")
 
 
+def _power_weight(freqs, nbin, PSD, PSD_args, PSD_kwargs, torch, dev):
+    """x / PSD over one channel's nbin bins, x = diff(f) with the first spacing repeated
+    (diagnostic.py:93-98): the weight of inner_product and pair_statistics."""
+    psd = _psd_array(PSD, freqs, PSD_args, PSD_kwargs, torch, dev)
+    x = torch.empty(nbin, dtype=torch.float64, device=dev)
+    x[1:] = torch.diff(freqs)
+    x[0] = x[1]
+    return x / psd
+
+
 def inner_product(sig1, sig2, dt=None, df=None, f_arr=None, PSD="lisasens", PSD_args=(),
                   PSD_kwargs={}, normalize=False, use_gpu=False, complex=False):
     torch = require_gpu()
@@ -90,12 +103,9 @@ def inner_product(sig1, sig2, dt=None, df=None, f_arr=None, PSD="lisasens", PSD_
             freqs = (torch.arange(len(f1[0]), dtype=torch.float64, device=dev) + 1) * df
         else:
             freqs = torch.as_tensor(f_arr, dtype=torch.float64, device=dev)
-    psd = _psd_array(PSD, freqs, PSD_args, PSD_kwargs, torch, dev)
     nbin = len(f1[0])
-    x = torch.empty(nbin, dtype=torch.float64, device=dev)
-    x[1:] = torch.diff(freqs)
-    x[0] = x[1]
-    w = (x / psd).expand(len(f1), nbin).contiguous()
+    w = _power_weight(freqs, nbin, PSD, PSD_args, PSD_kwargs, torch, dev)
+    w = w.expand(len(f1), nbin).contiguous()
     a = torch.stack(f1).contiguous()
     b = torch.stack(f2).contiguous()
     val = _reducer(dev).inner(a, b, w).item()
@@ -119,6 +129,87 @@ def inner_product(sig1, sig2, dt=None, df=None, f_arr=None, PSD="lisasens", PSD_
     elif normalize is not False:
         raise ValueError("Normalize must be True, False, 'sig1', or 'sig2'.")
     return out / norm
+
+
+class PairStatistics:
+    """What the mode-by-mode driver derives for each (template 1, template 2) pair
+    (check_mode_by_mode.py:292-326), as numpy arrays over the R pairs, from efd_pair_stats'
+    numbers raw [R][nchan][5] = (aa, bb, abr, abi, dd):
+      aa, bb, dd [R][nchan] and ab complex [R][nchan]: <1|1>, <2|2>, <1-2|1-2> and <1|2> per
+        channel; aa_sum, bb_sum, dd_sum [R] and ab_sum complex [R]: summed over the channels;
+      snr1 = sqrt(aa_sum), snr2 = sqrt(bb_sum)                              (:292)
+      overlap = Re ab_sum / sqrt(aa_sum bb_sum), mismatch = |1 - overlap|   (:299-301)
+      loglike = -1/2 dd_sum                                                 (:315-317)
+    dd is the difference's own sum (formed per element), not aa + bb - 2 Re ab."""
+
+    def __init__(self, raw):
+        raw = np.asarray(raw, dtype=np.float64)
+        self.raw = raw
+        self.aa, self.bb, self.dd = raw[..., 0], raw[..., 1], raw[..., 4]
+        self.ab = raw[..., 2] + 1j * raw[..., 3]
+        self.aa_sum, self.bb_sum = self.aa.sum(axis=-1), self.bb.sum(axis=-1)
+        self.ab_sum, self.dd_sum = self.ab.sum(axis=-1), self.dd.sum(axis=-1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.snr1, self.snr2 = np.sqrt(self.aa_sum), np.sqrt(self.bb_sum)
+            self.overlap = self.ab_sum.real / np.sqrt(self.aa_sum * self.bb_sum)
+        self.mismatch = np.abs(1.0 - self.overlap)
+        self.loglike = -0.5 * self.dd_sum
+
+
+def _as_rows(sig, torch, dev):
+    """Rows of channels as one tensor [R][nchan][n]: a tensor as it is, a list of channel lists
+    (or of single channels) stacked."""
+    def row(r):
+        if isinstance(r, (list, tuple)):
+            return torch.stack(_as_channels(list(r), torch, dev))
+        t = torch.as_tensor(r, device=dev)
+        return t[None, :] if t.dim() == 1 else t
+
+    if isinstance(sig, (list, tuple)):
+        return torch.stack([row(r) for r in sig])
+    t = torch.as_tensor(sig, device=dev)
+    return t[:, None, :] if t.dim() == 2 else t
+
+
+def pair_statistics(sig1_rows, sig2_rows, dt=None, df=None, f_arr=None, PSD="lisasens",
+                    PSD_args=(), PSD_kwargs={}):
+    """SNRs, normalised overlap, mismatch and the log-likelihood of the difference of R
+    (signal 1, signal 2) pairs in one pass over each (efd_pair_stats): what the mode-by-mode
+    driver takes from six to eight inner_product calls per pair (check_mode_by_mode.py:292-326).
+    The rows are lists of channel lists, or tensors [R][nchan][nbin] (one or two channels); the
+    frequency and PSD rules and errors are inner_product's, with one weight for all rows. Rows go
+    in blocks of EFD_PAIR_MAX_ROWS and one host transfer brings everything back. Returns a
+    PairStatistics."""
+    torch = require_gpu()
+    if df is None and dt is None and f_arr is None:
+        raise ValueError("Must provide either df, dt or f_arr keyword arguments.")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    a = _as_rows(sig1_rows, torch, dev)
+    b = _as_rows(sig2_rows, torch, dev)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
+        raise ValueError("pair_statistics: expected the same number of rows [R][nchan][n] on "
+                         "both sides, got {} and {}".format(tuple(a.shape), tuple(b.shape)))
+    if a.shape[1] != b.shape[1]:
+        raise ValueError("Signal 1 has {} channels. Signal 2 has {} channels. Must be "
+                         "equal.".format(a.shape[1], b.shape[1]))
+    if dt is not None:
+        n = max(a.shape[-1], b.shape[-1])
+        a = torch.nn.functional.pad(a, (0, n - a.shape[-1]))
+        b = torch.nn.functional.pad(b, (0, n - b.shape[-1]))
+        freqs = torch.fft.rfftfreq(n, dt, dtype=torch.float64, device=dev)[1:]
+        a = torch.fft.rfft(a.to(torch.float64))[..., 1:] * dt
+        b = torch.fft.rfft(b.to(torch.float64))[..., 1:] * dt
+    elif df is not None:
+        freqs = (torch.arange(a.shape[-1], dtype=torch.float64, device=dev) + 1) * df
+    else:
+        freqs = torch.as_tensor(f_arr, dtype=torch.float64, device=dev)
+    a = a.to(torch.complex128).contiguous()
+    b = b.to(torch.complex128).contiguous()
+    if a.shape != b.shape:
+        raise ValueError("pair_statistics: the two sides' rows differ in length")
+    w = _power_weight(freqs, int(a.shape[-1]), PSD, PSD_args, PSD_kwargs, torch, dev).contiguous()
+    raw = _reducer(dev).pair_stats(a, b, w)
+    return PairStatistics(raw.cpu().numpy())
 
 
 def snr(sig1, *args, data=None, use_gpu=False, **kwargs):

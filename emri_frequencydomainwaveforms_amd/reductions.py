@@ -1,5 +1,5 @@
 """Device reductions of the likelihood side: thin wrappers of efd_loglike / efd_inner_product /
-efd_fisher_gram / efd_overlap_rows.
+efd_fisher_gram / efd_overlap_rows / efd_pair_stats / efd_td_split_pair_stats.
 
 All run in libemrifd.so (HIP, gfx950) as fixed-partition two-pass reductions, so results are
 bitwise reproducible. They read the channels in place: h, d complex128 [nchan][nbin], w float64
@@ -181,3 +181,123 @@ class Reducer:
                                                  scr.data_ptr(), self._stream()),
                        "efd_overlap_rows", self.lib)
         return res
+
+    def _pair_rows(self, x, name, nchan=None):
+        """(pointer, stride in complex elements, nrow, nchan, nbin) of rows complex128
+        [nrow][nchan][nbin]: every row contiguous, rows a fixed stride apart."""
+        torch = self.torch
+        if (x.dtype != torch.complex128 or x.device != self.device or x.dim() != 3
+                or x.shape[0] < 1 or not x[0].is_contiguous()):
+            raise ValueError(f"{name}: expected complex128 [nrow][nchan][nbin] on {self.device} "
+                             "with contiguous rows")
+        nrow, nch, nbin = (int(v) for v in x.shape)
+        if nch not in (1, 2) or (nchan is not None and nch != nchan):
+            raise ValueError(f"{name}: expected {nchan or '1 or 2'} channels, got {nch}")
+        stride = int(x.stride(0)) if nrow > 1 else nch * nbin
+        if nbin == 0 or stride < nch * nbin:
+            raise ValueError(f"{name}: empty or overlapping rows")
+        return torch.view_as_real(x).data_ptr(), stride, nrow, nch, nbin
+
+    def _pair_scratch(self):
+        scr = getattr(self, "_scr_ps", None)
+        if scr is None:
+            scr = self._scr_ps = self.torch.empty(_lib.EFD_PAIR_SCRATCH, dtype=self.torch.float64,
+                                                  device=self.device)
+        return scr
+
+    def _pair_out(self, out, nrow, nchan):
+        torch = self.torch
+        if out is None:
+            return torch.empty((nrow, nchan, 5), dtype=torch.float64, device=self.device)
+        self._check(out, "out", torch.float64, (nrow, nchan, 5))
+        return out
+
+    def pair_stats(self, a, b, w, out=None):
+        """(aa, bb, abr, abi, dd) of every (a_r, b_r) pair and channel in one pass over each
+        (efd_pair_stats; the mode-by-mode driver's inner products, check_mode_by_mode.py:292-326)
+        as a float64 [nrow][nchan][5] device tensor: 4 sum_k w (|a|^2, |b|^2, Re conj(a) b,
+        Im conj(a) b, |a - b|^2), the difference formed per element.
+
+        a, b: complex128 [nrow][nchan][nbin], nchan 1 or 2, contiguous rows a fixed stride
+        apart; w: float64 [nbin] shared by the channels and rows, or None (w = 1). More than
+        EFD_PAIR_MAX_ROWS rows go in several calls; a row's numbers are bitwise what any other
+        split gives."""
+        torch = self.torch
+        pa, sa, nrow, nchan, nbin = self._pair_rows(a, "a")
+        pb, sb, nrb, _, nbb = self._pair_rows(b, "b", nchan)
+        if (nrb, nbb) != (nrow, nbin):
+            raise ValueError(f"b: expected shape {tuple(a.shape)}, got {tuple(b.shape)}")
+        pw = None if w is None else self._check(w, "w", torch.float64, (nbin,))
+        out = self._pair_out(out, nrow, nchan)
+        scr = self._pair_scratch()
+        M = _lib.EFD_PAIR_MAX_ROWS
+        for r0 in range(0, nrow, M):
+            n = min(M, nrow - r0)
+            _lib.check(self.lib.efd_pair_stats(pa + 16 * sa * r0, sa, pb + 16 * sb * r0, sb, n,
+                                               nchan, nbin, pw,
+                                               out.data_ptr() + 8 * 5 * nchan * r0,
+                                               scr.data_ptr(), self._stream()),
+                       "efd_pair_stats", self.lib)
+        return out
+
+    def td_split_pair_stats(self, Z, n, gain, a, w, keep=None, out=None):
+        """pair_stats with b_r = the two channels of row r of Z (efd_td_split's gain H+, gain Hx
+        over the nb = (n + 1) // 2 positive-frequency bins), never stored
+        (efd_td_split_pair_stats): float64 [rows][2][5] on the device.
+
+        Z: complex128 [rows][>= n], natural-order transforms of w (h+ - i hx), rows a fixed
+        stride apart; a: complex128 [rows][2][nb]; w: float64 [nb] or None; keep: uint8 [nb] or
+        None (a dropped bin has b = 0)."""
+        torch = self.torch
+        n = int(n)
+        if (Z.dtype != torch.complex128 or Z.device != self.device or Z.dim() != 2
+                or Z.shape[0] < 1 or Z.stride(1) != 1 or n < 1 or Z.shape[1] < n):
+            raise ValueError(f"Z: expected complex128 [rows][>= {n}] on {self.device} with "
+                             "contiguous rows")
+        rows = int(Z.shape[0])
+        zs = int(Z.stride(0)) if rows > 1 else n
+        if zs < n:
+            raise ValueError("Z: overlapping rows")
+        nb = (n + 1) // 2
+        pa, sa, nra, _, nba = self._pair_rows(a, "a", 2)
+        if (nra, nba) != (rows, nb):
+            raise ValueError(f"a: expected shape {(rows, 2, nb)}, got {tuple(a.shape)}")
+        pw = None if w is None else self._check(w, "w", torch.float64, (nb,))
+        pk = None if keep is None else self._check(keep, "keep", torch.uint8, (nb,))
+        out = self._pair_out(out, rows, 2)
+        scr = self._pair_scratch()
+        pz = torch.view_as_real(Z).data_ptr()
+        M = _lib.EFD_PAIR_MAX_ROWS
+        for r0 in range(0, rows, M):
+            m = min(M, rows - r0)
+            _lib.check(self.lib.efd_td_split_pair_stats(pz + 16 * zs * r0, zs, n, m, float(gain),
+                                                        pa + 16 * sa * r0, sa, pw, pk,
+                                                        out.data_ptr() + 8 * 10 * r0,
+                                                        scr.data_ptr(), self._stream()),
+                       "efd_td_split_pair_stats", self.lib)
+        return out
+
+    def window_rows(self, h, windows, out):
+        """out[j] = windows[j] * h for every window of one series (efd_window_rows): h
+        complex128 [n]; windows: float64 [n] tensors, or None for the unwindowed copy; out:
+        complex128 [len(windows)][>= n] with contiguous rows a fixed stride apart."""
+        torch = self.torch
+        n = int(h.numel())
+        ph = self._check(h, "h", torch.complex128, (n,))
+        nwin = len(windows)
+        if not 1 <= nwin <= _lib.EFD_WINDOW_MAX_ROWS:
+            raise ValueError(f"windows: expected 1..{_lib.EFD_WINDOW_MAX_ROWS}, got {nwin}")
+        if (out.dtype != torch.complex128 or out.device != self.device or out.dim() != 2
+                or out.shape[0] != nwin or out.shape[1] < n or out.stride(1) != 1):
+            raise ValueError(f"out: expected complex128 [{nwin}][>= {n}] on {self.device}")
+        stride = int(out.stride(0)) if nwin > 1 else n
+        if stride < n:
+            raise ValueError("out: overlapping rows")
+        ptrs = (ctypes.c_void_p * nwin)(*[
+            None if x is None else self._check(x, "window", torch.float64, (n,))
+            for x in windows])
+        _lib.check(self.lib.efd_window_rows(ph, n, ptrs, nwin,
+                                            torch.view_as_real(out).data_ptr(), stride,
+                                            self._stream()),
+                   "efd_window_rows", self.lib)
+        return out

@@ -522,6 +522,68 @@ int efd_overlap_rows(const double* h, int64_t row_stride, int32_t nrow, const do
                      double* scratch, void* stream);
 
 /*
+ * Statistics of many (template a, template b) pairs in one pass over each operand: everything
+ * the reference's mode-by-mode driver derives per (source, window) from six to eight
+ * inner_product calls (check_mode_by_mode.py:292 SNR, :299-301 normalised overlap, :315-317 the
+ * log-likelihood of the difference). For row pair r and channel c, out[(r nchan + c) 5 + i]:
+ *   0: aa  = 4 sum_k w |a|^2
+ *   1: bb  = 4 sum_k w |b|^2
+ *   2: abr = 4 sum_k w Re(conj(a) b)
+ *   3: abi = 4 sum_k w Im(conj(a) b)
+ *   4: dd  = 4 sum_k w |a - b|^2        (a - b formed per element, then squared: a pair at
+ *                                        mismatch 1e-6 does not get dd from aa + bb - 2 abr)
+ * a_r, b_r: complex [nchan][nbin] at a + 2 r a_stride and b + 2 r b_stride doubles (strides >=
+ * nchan nbin, rows 16-byte aligned; slices of wider buffers are fine), 1 <= nrow <=
+ * EFD_PAIR_MAX_ROWS, nchan 1 or 2; w: real [nbin] shared by the channels and rows, or NULL
+ * (w = 1): diff(f) / PSD with the first spacing repeated (lisatools diagnostic.py:93-98); out:
+ * 5 nchan nrow device doubles; scratch: EFD_PAIR_SCRATCH device doubles. Every element of a and
+ * b is read once; w once per row (from the XCD's cache after the first: the row is the slow
+ * grid dimension). Terms, as written (no contraction), with dr = ar - br, di = ai - bi:
+ *   fma(w, fma(ar, ar, ai ai), .), fma(w, fma(br, br, bi bi), .), fma(w, fma(ar, br, ai bi), .),
+ *   fma(w, ar bi - ai br, .)   (two rounded products and their difference, no inner fma),
+ *   fma(w, fma(dr, dr, di di), .).
+ * efd_td_split_pair_stats: the same ten numbers per row (nchan = 2) with b_r never stored: b_r
+ * is what efd_td_split writes for row r of Z (the same arithmetic, gain, and keep rule: a bin
+ * with keep[k] == 0 has b = 0 and its Z is not read; a is taken as given), a_r complex [2][nb] at
+ * a + 2 r a_stride doubles (a_stride >= 2 nb), w real [nb] or NULL, nb = (n + 1) / 2. Bin 0 pairs
+ * with itself; for even n the Nyquist bin is in neither channel. Every element of Z and a is
+ * read once.
+ * Promises of both:
+ *   - no atomics, a partition that depends on nbin (n) only and fixed reduction orders: bitwise
+ *     reproducible;
+ *   - a row's numbers are a function of that row pair, w (keep, gain) and the sizes alone: the
+ *     same alone, at another position or beside other rows (so more than EFD_PAIR_MAX_ROWS
+ *     pairs go in several calls without changing any number);
+ *   - efd_pair_stats: dd and abi are exactly 0 and aa == bb == abr when b equals a bit for bit;
+ *   - a NaN in a row makes only that row's outputs NaN. efd_td_split_pair_stats, even n: a NaN
+ *     in the Nyquist bin of a row of Z makes that row's bb, abr, abi and dd NaN
+ *     (efd_td_split_loglike's rule).
+ * EFD_ERR_ARG before any launch: NULL a, b, Z, out or scratch, rows outside
+ * 1..EFD_PAIR_MAX_ROWS, nbin <= 0, n < 1, a stride too small, nchan not 1 or 2.
+ */
+#define EFD_PAIR_MAX_ROWS 64
+#define EFD_PAIR_SCRATCH 655360
+int efd_pair_stats(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
+                   int32_t nrow, int32_t nchan, int64_t nbin, const double* w, double* out,
+                   double* scratch, void* stream);
+int efd_td_split_pair_stats(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
+                            const double* a, int64_t a_stride, const double* w,
+                            const uint8_t* keep, double* out, double* scratch, void* stream);
+
+/*
+ * Every windowing of one series from one read of it: out[j][k] = win[j][k] h[k] (real times
+ * complex, each part one product), h complex [n], win: HOST array of nwin device pointers to
+ * real windows [n], 1 <= nwin <= EFD_WINDOW_MAX_ROWS; a NULL entry copies the series bit for bit
+ * (the unwindowed row); row j at out + 2 j out_stride doubles, out_stride >= n. One TD mode sum
+ * then serves every window of a source (the driver windows and transforms the same series four
+ * times, check_mode_by_mode.py:263-264, :271-272). EFD_ERR_ARG before any launch: NULL h, win
+ * or out, n < 1, nwin out of range, out_stride < n.
+ */
+#define EFD_WINDOW_MAX_ROWS 16
+int efd_window_rows(const double* h, int64_t n, const double* const* win, int32_t nwin,
+                    double* out, int64_t out_stride, void* stream);
+
+/*
  * CPU twins: the same algorithm on HOST pointers, C++17 + OpenMP
  * (csrc/emrifd_cpu.cpp, linked into libemrifd.so). Signatures are those of the HIP entry points;
  * `stream`, `workspace` and `scratch` are accepted for parity and ignored (pass NULL / 0). The
@@ -554,6 +616,14 @@ int efd_td_split_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows, d
 int efd_td_split_loglike_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
                              double gain, const double* d, const double* w, double* out,
                              double* scratch, void* stream);
+int efd_pair_stats_cpu(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
+                       int32_t nrow, int32_t nchan, int64_t nbin, const double* w, double* out,
+                       double* scratch, void* stream);
+int efd_td_split_pair_stats_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
+                                double gain, const double* a, int64_t a_stride, const double* w,
+                                const uint8_t* keep, double* out, double* scratch, void* stream);
+int efd_window_rows_cpu(const double* h, int64_t n, const double* const* win, int32_t nwin,
+                        double* out, int64_t out_stride, void* stream);
 /* OpenMP threads of the twins (n <= 0: all available); returns the previous setting. */
 int efd_cpu_threads(int n);
 /* Last error message of the calling thread's CPU-twin call. */
