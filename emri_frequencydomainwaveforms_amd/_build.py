@@ -1,8 +1,10 @@
 """Build libemrifd.so in-tree (no JIT cache, so the .so travels with the repo snapshot). Every
 source is compiled to an object under build/, all of them at once, and one link step follows:
 
-  csrc/emrifd_cpu.cpp -> g++ -O3 -march=x86-64-v4 -fopenmp (the host twin, efd_*_cpu; AVX-512 is
-                         on both this container's Sapphire Rapids and the GPU box's EPYC 9575F)
+  csrc/emrifd_cpu.cpp, emrifd_reduce_cpu.cpp -> g++ -O3 -march=x86-64-v4 -fopenmp
+                         -ffp-contract=off each (the host twins, efd_*_cpu: the mode sum's and the
+                         reductions'; AVX-512 is on both this container's Sapphire Rapids and the
+                         GPU box's EPYC 9575F)
   csrc/emrifd_host.cpp -> g++ -O3 -fopenmp: the host upstream stand-ins (trajectory, p0 solve) in C++
   and the walker batches' staging
   csrc/emrifd_modes.cpp -> g++ -O3 -ffast-math -fopenmp (libmvec; knots over threads for one-at-a-time
@@ -11,7 +13,7 @@ source is compiled to an object under build/, all of them at once, and one link 
                          sum, its preparation, the window path, the channel split and reductions)
                          -> hipcc --offload-arch=gfx950 -c each; all share csrc/emrifd_common.h,
                          the first two also csrc/emrifd_layout.h (no relocatable device code)
-  link                -> hipcc -shared over the seven objects, with libgomp and libmvec
+  link                -> hipcc -shared over the eight objects, with libgomp and libmvec
 """
 
 import glob
@@ -25,6 +27,7 @@ SRC = os.path.join(CSRC, "emrifd.hip")
 HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_prepare.hip"), os.path.join(CSRC, "emrifd_window.hip"),
              os.path.join(CSRC, "emrifd_reduce.hip")]
 CPU_SRC = os.path.join(CSRC, "emrifd_cpu.cpp")
+REDUCE_CPU_SRC = os.path.join(CSRC, "emrifd_reduce_cpu.cpp")
 HOST_SRC = os.path.join(CSRC, "emrifd_host.cpp")
 MODES_SRC = os.path.join(CSRC, "emrifd_modes.cpp")
 OUT = os.path.join(HERE, "libemrifd.so")
@@ -39,7 +42,7 @@ def obj_path(src):
     return os.path.join(OBJDIR, os.path.splitext(os.path.basename(src))[0] + ".o")
 
 
-HOST_OBJS = [obj_path(s) for s in (CPU_SRC, HOST_SRC, MODES_SRC)]
+HOST_OBJS = [obj_path(s) for s in (CPU_SRC, REDUCE_CPU_SRC, HOST_SRC, MODES_SRC)]
 
 
 def hip_compile_cmd(src, obj, flags=()):
@@ -95,11 +98,11 @@ def build(force=False, verbose=False, extra=()):
     os.makedirs(OBJDIR, exist_ok=True)
     gxx = ["g++", "-O3", f"-march={CPU_ARCH}", "-fPIC", "-std=c++17", "-fopenmp"]
     bid = [f'-DEFD_BUILD_ID="{sid}"'] if not extra else []
-    # the longest compile (the mode sum) first; seven compilers at once, one per source
+    # the longest compile (the mode sum) first; eight compilers at once, one per source
     cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in HIP_UNITS]
-    cmds += [[*gxx, "-ffp-contract=off", "-c", CPU_SRC, "-o", obj_path(CPU_SRC)],
-             [*gxx, "-ffp-contract=off", "-c", HOST_SRC, "-o", obj_path(HOST_SRC)],
-             [*gxx, "-ffast-math", "-c", MODES_SRC, "-o", obj_path(MODES_SRC)]]
+    cmds += [[*gxx, "-ffp-contract=off", "-c", s, "-o", obj_path(s)]
+             for s in (CPU_SRC, REDUCE_CPU_SRC, HOST_SRC)]
+    cmds += [[*gxx, "-ffast-math", "-c", MODES_SRC, "-o", obj_path(MODES_SRC)]]
     procs = []
     for cmd in cmds:
         if verbose:

@@ -314,7 +314,7 @@ def load(path=None):
     for name in ("efd_window_rows", "efd_window_rows_cpu"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, i64, ctypes.POINTER(vp), i32, vp, i64, vp]
-    if hasattr(lib, "efd_modesum_cpu"):   # the host twins (csrc/emrifd_cpu.cpp)
+    if hasattr(lib, "efd_modesum_cpu"):   # the host twins (csrc/emrifd_cpu.cpp, emrifd_reduce_cpu.cpp)
         lib.efd_modesum_cpu.restype = ctypes.c_int
         lib.efd_modesum_cpu.argtypes = [ctypes.POINTER(ModesumArgs), vp, sz, vp]
         lib.efd_modesum_cpu_stats.restype = ctypes.c_int

@@ -1,4 +1,5 @@
-"""Host twin of the FD mode sum (efd_modesum_cpu in libemrifd.so, csrc/emrifd_cpu.cpp).
+"""Host twin of the FD mode sum (efd_modesum_cpu in libemrifd.so, csrc/emrifd_cpu.cpp) and of
+the likelihood reduction (efd_loglike_cpu, csrc/emrifd_reduce_cpu.cpp).
 
 The same algorithm as the HIP path (grouping, splines, interval records, tile-wise
 output-stationary sum with the uniform K_{1/3} fast path) on the CPU with OpenMP: the CPU

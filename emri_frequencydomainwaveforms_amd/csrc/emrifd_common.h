@@ -27,9 +27,9 @@ namespace efdhip {
 // sets the calling thread's last-error string (efd_last_error) and returns code; defined once,
 // beside the string, in emrifd.hip
 EFD_INTERNAL int fail(int code, const std::string& msg);
-// k_loglike_final (emrifd_reduce.hip) on one workgroup per row: out[r] from row r's np partials
-// at part[r np ...]. The window path's likelihoods end in the same kernel, so they launch it
-// through this instead of holding a copy; the caller checks hipGetLastError()
+// k_final (emrifd_reduce.hip) with the likelihood's scale -2, one workgroup per row: out[r] from
+// row r's np partials at part[r np ...]. The window path's likelihoods end in the same kernel,
+// so they launch it through this instead of holding a copy; the caller checks hipGetLastError()
 EFD_INTERNAL void launch_loglike_final(int rows, const double* part, int np, double* out,
                                        hipStream_t st);
 }  // namespace efdhip

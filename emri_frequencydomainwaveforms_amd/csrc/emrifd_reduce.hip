@@ -23,14 +23,98 @@ __global__ void k_polarizations(const double2* __restrict__ S, int64_t nf, int64
     hc[i] = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
 }
 
-// fused log-likelihood partials: one workgroup per chunk, then a second pass
+// ---- the reductions' shared steps. Every reduction here promises bitwise reproducibility and
+// that a row's numbers do not depend on the call's other rows; both rest on the orders written
+// in this section and nowhere else. Every launch of this unit has RED_THREADS threads.
+constexpr int RED_THREADS = 256;
+
+// the workgroup's sum of each of v[0 .. N - 1] through LDS, all N behind one barrier sequence:
+// the tree s = 128, 64, ..., 1. Every thread returns with the sums in v (thread 0 uses them).
+template <int N>
+__device__ __forceinline__ void block_sum(double* v) {
+    __shared__ double red[N][RED_THREADS];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int n = 0; n < N; ++n) red[n][tid] = v[n];
+    __syncthreads();
+    for (int s = RED_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int n = 0; n < N; ++n) red[n][tid] += red[n][tid + s];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = red[n][0];
+}
+
+// a wave's 64 lanes' sum by a butterfly: every lane ends with the same value
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// The streaming reductions' workgroup epilogue: each of the thread's NS sums over its wave
+// (wave_sum), the four waves' sums added as ((0 + 1) + 2) + 3, and sum i stored as this
+// workgroup's partial of output o = out_of(i) at part[o gridDim.x + blockIdx.x] (o < 0: dropped).
+template <int NS, class OutOf>
+__device__ __forceinline__ void wg_store(const double (&v)[NS], double* __restrict__ part,
+                                         OutOf out_of) {
+    __shared__ double sm[4][NS];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const double x = wave_sum(v[i]);
+        if (lane == 0) sm[wv][i] = x;
+    }
+    __syncthreads();
+    if (tid < NS) {
+        const double s = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
+        const int64_t o = out_of(tid);
+        if (o >= 0) part[o * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// The one second pass: workgroup o adds output o's np partials part[o np ...] (thread t takes
+// t, t + 256, ... in that order, then block_sum's tree) and writes out[o] = scale * sum.
+__global__ __launch_bounds__(RED_THREADS) void k_final(const double* __restrict__ part, int np,
+                                                       double scale, double* __restrict__ out) {
+    part += (int64_t)blockIdx.x * np;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += RED_THREADS) acc += part[i];
+    block_sum<1>(&acc);
+    if (threadIdx.x == 0) out[blockIdx.x] = scale * acc;
+}
+
+void launch_final(int nout, const double* part, int np, double scale, double* out,
+                  hipStream_t st) {
+    hipLaunchKernelGGL(k_final, dim3((unsigned)nout), dim3(RED_THREADS), 0, st, part, np, scale,
+                       out);
+}
+
+// bins [k0, k1) of workgroup blockIdx.x of a row cut into chunks of `chunk` bins (row_chunks)
+__device__ __forceinline__ void chunk_bounds(int64_t chunk, int64_t nb, int64_t& k0, int64_t& k1) {
+    k0 = (int64_t)blockIdx.x * chunk;
+    k1 = min(nb, k0 + chunk);
+}
+
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals v (for none: nothing), so that
+// a kernel's template arguments can follow run-time values
+template <int... Vs, class F>
+void for_value(int v, F f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// fused log-likelihood partials: one workgroup per chunk, then the second pass (k_final, -2)
 __global__ void k_loglike_partial(const double2* __restrict__ h, const double2* __restrict__ d,
                                   const double* __restrict__ w, int64_t total,
                                   double* __restrict__ part) {
     // d - h*w rounded like the reference's numpy (product rounded, then difference): no FMA
     // contraction here, so a template equal to the injection gives exactly 0
 #pragma clang fp contract(off)
-    __shared__ double red[256];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -44,29 +128,8 @@ __global__ void k_loglike_partial(const double2* __restrict__ h, const double2* 
         }
         acc = fma(rr, rr, fma(ri, ri, acc));
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-
-// (one row per workgroup: partials part[row * np ...], out[row])
-__global__ void k_loglike_final(const double* __restrict__ part, int np, double* __restrict__ out) {
-    part += (int64_t)blockIdx.x * np;
-    out += blockIdx.x;
-    __shared__ double red[256];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) acc += part[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = -0.5 * 4.0 * red[0];
+    block_sum<1>(&acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // ---- DFT of a TD template h = h+ - i hx into its two channels (efd_td_split*). Z = fft(w h)
@@ -79,6 +142,17 @@ __device__ __forceinline__ void td_split_pair(const double2 a, const double2 b, 
 #pragma clang fp contract(off)
     hp = make_double2(gain * (0.5 * (a.x + b.x)), gain * (0.5 * (a.y - b.y)));
     hc = make_double2(gain * (-0.5 * (a.y + b.y)), gain * (0.5 * (a.x - b.x)));
+}
+
+// The even-n rule of the split's reductions: the Nyquist bin Z[n / 2] belongs to neither
+// channel's kept bins, but a NaN there still poisons the row, as one anywhere else does through
+// the terms. True in the one thread of the row (thread 0 of chunk 0) that finds such a NaN, with
+// the NaN its sums take in *poison.
+__device__ __forceinline__ bool nyquist_nan(const double2* z, int64_t n, double* poison) {
+    if (blockIdx.x != 0 || threadIdx.x != 0 || (n & 1) != 0) return false;
+    const double2 v = z[n / 2];
+    *poison = v.x + v.y;
+    return v.x != v.x || v.y != v.y;
 }
 
 __global__ __launch_bounds__(256) void k_td_split(const double2* __restrict__ Z, int64_t stride,
@@ -99,18 +173,17 @@ __global__ __launch_bounds__(256) void k_td_split(const double2* __restrict__ Z,
 // in registers: workgroup (c, r) takes bins [c chunk, (c + 1) chunk) of row r, an ascending
 // stream Z[k] and a descending one Z[n - k]; the row is the slow grid dimension, so the rows'
 // workgroups of one chunk follow each other on one XCD and find d and w in its cache. Partials
-// at part[r gridDim.x + c] (k_loglike_final's layout).
+// at part[r gridDim.x + c] (k_final's layout).
 __global__ __launch_bounds__(256) void k_td_split_loglike(
     const double2* __restrict__ Z, int64_t stride, int64_t n, int64_t nb, int64_t chunk,
     double gain, const double2* __restrict__ d, const double* __restrict__ w,
     double* __restrict__ part) {
     // d - h w rounded as k_loglike_partial does (product, then difference)
 #pragma clang fp contract(off)
-    __shared__ double red[256];
     const double2* z = Z + (int64_t)blockIdx.y * stride;
-    const int64_t k0 = (int64_t)blockIdx.x * chunk;
-    const int64_t k1 = min(nb, k0 + chunk);
-    double acc = 0.0;
+    int64_t k0, k1;
+    chunk_bounds(chunk, nb, k0, k1);
+    double acc = 0.0, poison;
     for (int64_t k = k0 + threadIdx.x; k < k1; k += 256) {
         double2 hp, hc;
         td_split_pair(z[k], z[k == 0 ? 0 : n - k], gain, hp, hc);
@@ -121,67 +194,31 @@ __global__ __launch_bounds__(256) void k_td_split_loglike(
         acc = fma(ar, ar, fma(ai, ai, acc));
         acc = fma(br, br, fma(bi, bi, acc));
     }
-    // even n: the Nyquist bin belongs to neither channel's kept bins; a NaN there still
-    // poisons the row, as one anywhere else does through the terms above
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
-        const double2 v = z[n / 2];
-        if (v.x != v.x || v.y != v.y) acc = v.x + v.y;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+    if (nyquist_nan(z, n, &poison)) acc = poison;
+    block_sum<1>(&acc);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
-// noise-weighted inner product partials: sum conj(a) b w (complex), one pair per workgroup
+// noise-weighted inner product partials: sum conj(a) b w (complex), one pair per workgroup; the
+// real parts at part[blockIdx.x], the imaginary ones at part[gridDim.x + blockIdx.x] (k_final's
+// layout for the two outputs re, im)
 __global__ void k_inner_partial(const double2* __restrict__ a, const double2* __restrict__ b,
                                 const double* __restrict__ w, int64_t total,
-                                double2* __restrict__ part) {
-    __shared__ double rre[256], rim[256];
-    double accr = 0.0, acci = 0.0;
+                                double* __restrict__ part) {
+    double acc[2] = {0.0, 0.0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
         const double2 av = a[i], bv = b[i];
         const double ww = w ? w[i] : 1.0;
         // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
-        accr = fma(ww, fma(av.x, bv.x, av.y * bv.y), accr);
-        acci = fma(ww, fma(av.x, bv.y, -av.y * bv.x), acci);
+        acc[0] = fma(ww, fma(av.x, bv.x, av.y * bv.y), acc[0]);
+        acc[1] = fma(ww, fma(av.x, bv.y, -av.y * bv.x), acc[1]);
     }
-    rre[threadIdx.x] = accr;
-    rim[threadIdx.x] = acci;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            rre[threadIdx.x] += rre[threadIdx.x + s];
-            rim[threadIdx.x] += rim[threadIdx.x + s];
-        }
-        __syncthreads();
+    block_sum<2>(acc);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = acc[0];
+        part[gridDim.x + blockIdx.x] = acc[1];
     }
-    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(rre[0], rim[0]);
-}
-
-__global__ void k_inner_final(const double2* __restrict__ part, int np, double scale,
-                              double2* __restrict__ out) {
-    __shared__ double rre[256], rim[256];
-    double accr = 0.0, acci = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) {
-        accr += part[i].x;
-        acci += part[i].y;
-    }
-    rre[threadIdx.x] = accr;
-    rim[threadIdx.x] = acci;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            rre[threadIdx.x] += rre[threadIdx.x + s];
-            rim[threadIdx.x] += rim[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = make_double2(scale * rre[0], scale * rim[0]);
 }
 
 // ---- weighted Gram matrix of stencil-combined rows (efd_fisher_gram) ----------------------
@@ -295,16 +332,14 @@ __global__ __launch_bounds__(FG_THREADS) void k_fisher_partial(
         }
         __syncthreads();
     }
-    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
+    // the 64 lanes' sums (wave_sum), lane 0 stores
     const int npair = nparam * (nparam + 1) / 2;
 #pragma unroll
     for (int k = 0; k < MAXT; ++k) {
         if (tj[k] >= TP) continue;
 #pragma unroll
         for (int p = 0; p < 16; ++p) {
-            double v = acc[k][p];
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+            const double v = wave_sum(acc[k][p]);
             const int gi = 4 * ti[k] + (p >> 2), gj = 4 * tj[k] + (p & 3);
             if (lane == 0 && gi <= gj && gj < nparam)
                 part[(int64_t)blockIdx.x * npair + fg_pair_index(gi, gj, nparam)] = v;
@@ -315,17 +350,11 @@ __global__ __launch_bounds__(FG_THREADS) void k_fisher_partial(
 // one workgroup per pair: the workgroups' partials in a fixed order, mirrored into both halves
 __global__ void k_fisher_final(const double* __restrict__ part, int nb, int nparam,
                                double* __restrict__ gram) {
-    __shared__ double red[256];
     const int npair = nparam * (nparam + 1) / 2;
     const int p = blockIdx.x;
     double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[(int64_t)b * npair + p];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
+    for (int b = threadIdx.x; b < nb; b += RED_THREADS) acc += part[(int64_t)b * npair + p];
+    block_sum<1>(&acc);
     if (threadIdx.x == 0) {
         int i = 0, q = p;
         while (q >= nparam - i) {
@@ -333,32 +362,9 @@ __global__ void k_fisher_final(const double* __restrict__ part, int nb, int npar
             ++i;
         }
         const int j = i + q;
-        const double g = 4.0 * red[0];
+        const double g = 4.0 * acc;
         gram[i * nparam + j] = g;
         gram[j * nparam + i] = g;
-    }
-}
-
-template <int NPOINT>
-void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_stride, int nparam,
-               const fg_coef& cf, const double* w, int64_t nelem, double2* dh, double* part) {
-    switch (tp) {
-        case 1:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 1>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        case 2:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 2>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        case 3:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 3>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
-        default:
-            hipLaunchKernelGGL((k_fisher_partial<NPOINT, 4>), dim3(nb), dim3(FG_THREADS), 0, st, h,
-                               row_stride, nparam, cf, w, nelem, dh, part);
-            break;
     }
 }
 
@@ -368,9 +374,9 @@ void fg_launch(int tp, int nb, hipStream_t st, const double2* h, int64_t row_str
 // of nelem alone) of the NR rows of row block y: a thread loads its element of t, u, w once,
 // forms r = t - u, issues the 16-byte loads of its element of the block's NR rows together
 // (8 rows x 256 threads x 16 B = 32 KiB in flight per workgroup) and keeps 3 NR sums in
-// registers across the chunks. The epilogue is a butterfly over the 64 lanes, the four waves'
-// sums added as ((0 + 1) + 2) + 3, and one partial per (output, workgroup) at part[o G + b];
-// k_overlap_final adds each output's G partials in a fixed order and scales by 4.
+// registers across the chunks. The epilogue is wg_store: a butterfly over the 64 lanes, the four
+// waves' sums added as ((0 + 1) + 2) + 3, and one partial per (output, workgroup) at
+// part[o G + b]; k_final adds each output's G partials in a fixed order and scales by 4.
 // What makes out[3k .. 3k + 2] a function of row k, t, u, w and nelem alone (the subset
 // promise): the element -> (workgroup, thread) map and both reduction orders depend on nelem
 // only, and a row's terms never see another row, the row block's width or its position; the
@@ -380,7 +386,8 @@ constexpr int OV_MAXB = 1024;   // workgroups per row block (4 per CU)
 constexpr int OV_RB = 8;        // rows per full block
 typedef double ov_d2 __attribute__((ext_vector_type(2)));
 
-// row0: the first row of block y = 0 of this launch; the |r|^2 sum belongs to row 0's block
+// row0: the first row of block y = 0 of this launch; the |r|^2 sum belongs to row 0's block.
+// Row k's sums (re, im, nn) are acc[3 k .. 3 k + 2], the |r|^2 sum is acc[3 NR]
 template <int NR>
 __global__ __launch_bounds__(OV_THREADS) void k_overlap_partial(
     const double2* __restrict__ h, int64_t row_stride, int row0, int nrow,
@@ -388,15 +395,12 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_partial(
     int64_t nelem, double* __restrict__ part) {
 #pragma clang fp contract(off)
     constexpr int NS = 3 * NR + 1;
-    __shared__ double sm[4][NS];
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int first = row0 + (int)blockIdx.y * NR;
     const double2* hb = h + row_stride * (int64_t)first;
-    double re[NR], im[NR], nn[NR], rr2 = 0.0;
+    double acc[NS];
 #pragma unroll
-    for (int k = 0; k < NR; ++k) re[k] = im[k] = nn[k] = 0.0;
+    for (int i = 0; i < NS; ++i) acc[i] = 0.0;
 
     const int64_t nchunk = (nelem + OV_THREADS - 1) / OV_THREADS;
     for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
@@ -417,54 +421,15 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlap_partial(
         const double ww = w ? w[e] : 1.0;
 #pragma unroll
         for (int k = 0; k < NR; ++k) {
-            re[k] = fma(ww, fma(v[k].x, r.x, v[k].y * r.y), re[k]);
-            im[k] = fma(ww, fma(v[k].x, r.y, -(v[k].y * r.x)), im[k]);
-            nn[k] = fma(ww, fma(v[k].x, v[k].x, v[k].y * v[k].y), nn[k]);
+            acc[3 * k] = fma(ww, fma(v[k].x, r.x, v[k].y * r.y), acc[3 * k]);
+            acc[3 * k + 1] = fma(ww, fma(v[k].x, r.y, -(v[k].y * r.x)), acc[3 * k + 1]);
+            acc[3 * k + 2] = fma(ww, fma(v[k].x, v[k].x, v[k].y * v[k].y), acc[3 * k + 2]);
         }
-        if (first == 0) rr2 = fma(ww, fma(r.x, r.x, r.y * r.y), rr2);
+        if (first == 0) acc[3 * NR] = fma(ww, fma(r.x, r.x, r.y * r.y), acc[3 * NR]);
     }
-    // the 64 lanes' sums by a butterfly (every lane ends with the same value), lane 0 stores
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        double a = re[k], b = im[k], c = nn[k];
-#pragma unroll
-        for (int m = 32; m > 0; m >>= 1) {
-            a += __shfl_xor(a, m, 64);
-            b += __shfl_xor(b, m, 64);
-            c += __shfl_xor(c, m, 64);
-        }
-        if (lane == 0) {
-            sm[wv][3 * k] = a;
-            sm[wv][3 * k + 1] = b;
-            sm[wv][3 * k + 2] = c;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) rr2 += __shfl_xor(rr2, m, 64);
-    if (lane == 0) sm[wv][3 * NR] = rr2;
-    __syncthreads();
-    if (tid < NS) {
-        const double s = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
-        if (tid < 3 * NR)
-            part[(int64_t)(3 * first + tid) * gridDim.x + blockIdx.x] = s;
-        else if (first == 0)
-            part[(int64_t)(3 * nrow) * gridDim.x + blockIdx.x] = s;
-    }
-}
-
-// one workgroup per output: the workgroups' partials in a fixed order, times 4
-__global__ void k_overlap_final(const double* __restrict__ part, int nb, double* __restrict__ out) {
-    __shared__ double red[256];
-    part += (int64_t)blockIdx.x * nb;
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) acc += part[b];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = 4.0 * red[0];
+    wg_store(acc, part, [=](int i) {
+        return i < 3 * NR ? (int64_t)(3 * first + i) : first == 0 ? (int64_t)(3 * nrow) : -1;
+    });
 }
 
 template <int NR>
@@ -481,9 +446,9 @@ void ov_launch(int nb, int blocks, hipStream_t st, const double2* h, int64_t row
 // channel in registers. The row is the slow grid dimension: the workgroups of one chunk follow
 // each other on one XCD (the chunk count is a multiple of 8 once there are that many) and find w
 // and keep in its cache, while a and b (or Z) are read once and streamed past it. The epilogue
-// is k_overlap_partial's: a butterfly over the 64 lanes, the four waves' sums added as
-// ((0 + 1) + 2) + 3, one partial per (output, workgroup) at part[o gridDim.x + c]; then
-// k_overlap_final adds each output's partials in a fixed order and scales by 4.
+// is k_overlap_partial's (wg_store): a butterfly over the 64 lanes, the four waves' sums added
+// as ((0 + 1) + 2) + 3, one partial per (output, workgroup) at part[o gridDim.x + c]; then
+// k_final adds each output's partials in a fixed order and scales by 4.
 // What makes a row's numbers a function of that row pair, w and the sizes alone: the bin ->
 // (workgroup, thread) map and both reduction orders depend on nbin (n) only, a row's terms never
 // see another row or its own position, and the terms are the written ones (contraction off).
@@ -507,28 +472,11 @@ __device__ __forceinline__ double2 ps_stream(const double2* p) {
     return make_double2(x.x, x.y);
 }
 
-// the workgroup's 5 NCHAN sums to part[((r NCHAN + c) 5 + i) gridDim.x + blockIdx.x]
-template <int NCHAN>
-__device__ __forceinline__ void ps_store(double (&s)[NCHAN][5], double* __restrict__ part) {
-    constexpr int NS = 5 * NCHAN;
-    __shared__ double sm[4][NS];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll
-    for (int c = 0; c < NCHAN; ++c)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            double v = s[c][i];
-#pragma unroll
-            for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-            if (lane == 0) sm[wv][5 * c + i] = v;
-        }
-    __syncthreads();
-    if (tid < NS) {
-        const double v = ((sm[0][tid] + sm[1][tid]) + sm[2][tid]) + sm[3][tid];
-        part[((int64_t)blockIdx.y * NS + tid) * gridDim.x + blockIdx.x] = v;
-    }
+// the workgroup's NS = 5 NCHAN sums (s[5 c + i]: sum i of channel c) as the partials of row
+// blockIdx.y's outputs: part[((r NCHAN + c) 5 + i) gridDim.x + blockIdx.x]
+template <int NS>
+__device__ __forceinline__ void ps_store(const double (&s)[NS], double* __restrict__ part) {
+    wg_store(s, part, [](int i) { return (int64_t)blockIdx.y * NS + i; });
 }
 
 template <int NCHAN>
@@ -538,13 +486,11 @@ __global__ __launch_bounds__(PS_THREADS) void k_pair_stats(
     double* __restrict__ part) {
     const double2* ar = a + (int64_t)blockIdx.y * a_stride;
     const double2* br = b + (int64_t)blockIdx.y * b_stride;
-    const int64_t k0 = (int64_t)blockIdx.x * chunk;
-    const int64_t k1 = min(nbin, k0 + chunk);
-    double s[NCHAN][5];
+    int64_t k0, k1;
+    chunk_bounds(chunk, nbin, k0, k1);
+    double s[5 * NCHAN];
 #pragma unroll
-    for (int c = 0; c < NCHAN; ++c)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) s[c][i] = 0.0;
+    for (int i = 0; i < 5 * NCHAN; ++i) s[i] = 0.0;
     for (int64_t k = k0 + threadIdx.x; k < k1; k += PS_THREADS) {
         double2 av[NCHAN], bv[NCHAN];
 #pragma unroll
@@ -554,9 +500,9 @@ __global__ __launch_bounds__(PS_THREADS) void k_pair_stats(
         }
         const double ww = w ? w[k] : 1.0;
 #pragma unroll
-        for (int c = 0; c < NCHAN; ++c) ps_term(ww, av[c], bv[c], s[c]);
+        for (int c = 0; c < NCHAN; ++c) ps_term(ww, av[c], bv[c], s + 5 * c);
     }
-    ps_store<NCHAN>(s, part);
+    ps_store(s, part);
 }
 
 // the same with b = the split of row r of Z (k_td_split's arithmetic and keep rule), kept in
@@ -567,31 +513,25 @@ __global__ __launch_bounds__(PS_THREADS) void k_td_split_pair_stats(
     const uint8_t* __restrict__ keep, double* __restrict__ part) {
     const double2* z = Z + (int64_t)blockIdx.y * stride;
     const double2* ar = a + (int64_t)blockIdx.y * a_stride;
-    const int64_t k0 = (int64_t)blockIdx.x * chunk;
-    const int64_t k1 = min(nb, k0 + chunk);
-    double s[2][5];
+    int64_t k0, k1;
+    chunk_bounds(chunk, nb, k0, k1);
+    double s[10], poison;
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) s[c][i] = 0.0;
+    for (int i = 0; i < 10; ++i) s[i] = 0.0;
     for (int64_t k = k0 + threadIdx.x; k < k1; k += PS_THREADS) {
         const double2 a0 = ps_stream(ar + k), a1 = ps_stream(ar + (nb + k));
         double2 hp = make_double2(0.0, 0.0), hc = hp;
         if (keep == nullptr || keep[k] != 0)
             td_split_pair(ps_stream(z + k), ps_stream(z + (k == 0 ? 0 : n - k)), gain, hp, hc);
         const double ww = w ? w[k] : 1.0;
-        ps_term(ww, a0, hp, s[0]);
-        ps_term(ww, a1, hc, s[1]);
+        ps_term(ww, a0, hp, s);
+        ps_term(ww, a1, hc, s + 5);
     }
-    // even n: the Nyquist bin belongs to neither channel (k_td_split_loglike's rule); a NaN
-    // there still poisons every number of the row that depends on b
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1) == 0) {
-        const double2 v = z[n / 2];
-        if (v.x != v.x || v.y != v.y)
-            for (int c = 0; c < 2; ++c)
-                for (int i = 1; i < 5; ++i) s[c][i] = v.x + v.y;
-    }
-    ps_store<2>(s, part);
+    // a NaN in the Nyquist bin poisons every number of the row that depends on b
+    if (nyquist_nan(z, n, &poison))
+        for (int c = 0; c < 2; ++c)
+            for (int i = 1; i < 5; ++i) s[5 * c + i] = poison;
+    ps_store(s, part);
 }
 
 // out[j][k] = win[j][k] h[k]: every window of one series from one read of it
@@ -621,7 +561,7 @@ __global__ __launch_bounds__(256) void k_window_rows(const double2* __restrict__
 
 void efdhip::launch_loglike_final(int rows, const double* part, int np, double* out,
                                   hipStream_t st) {
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, part, np, out);
+    launch_final(rows, part, np, -2.0, out, st);
 }
 
 // ========================================================================================
@@ -655,7 +595,7 @@ int efd_loglike(const double* h, const double* d, const double* w, int32_t nchan
     hipLaunchKernelGGL(k_loglike_partial, dim3(np), dim3(threads), 0, st, (const double2*)h,
                        (const double2*)d, w, total, scratch);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3(1), dim3(256), 0, st, scratch, np, out);
+    launch_final(1, scratch, np, -2.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
@@ -669,10 +609,9 @@ int efd_inner_product(const double* a, const double* b, const double* w, int32_t
     const int np = (int)std::min<int64_t>(EFD_INNER_SCRATCH / 2, (total + threads - 1) / threads);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_inner_partial, dim3(np), dim3(threads), 0, st, (const double2*)a,
-                       (const double2*)b, w, total, (double2*)scratch);
+                       (const double2*)b, w, total, scratch);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_inner_final, dim3(1), dim3(256), 0, st, (const double2*)scratch, np,
-                       4.0, (double2*)out);
+    launch_final(2, scratch, np, 4.0, out, st);   // re, im
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
@@ -698,20 +637,13 @@ int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t
     const int nb = (int)std::min<int64_t>(FG_MAXB, (nelem + FG_CHUNK - 1) / FG_CHUNK);
     const int tp = (nparam + 3) / 4;
     hipStream_t st = (hipStream_t)stream;
-    switch (npoint) {
-        case 1:
-            fg_launch<1>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-        case 2:
-            fg_launch<2>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-        default:
-            fg_launch<4>(tp, nb, st, (const double2*)h, row_stride, nparam, cf, w, nelem,
-                         (double2*)dh, scratch);
-            break;
-    }
+    for_value<1, 2, 4>(npoint, [&](auto NP) {
+        for_value<1, 2, 3, 4>(tp, [&](auto TP) {
+            hipLaunchKernelGGL((k_fisher_partial<decltype(NP)::value, decltype(TP)::value>),
+                               dim3(nb), dim3(FG_THREADS), 0, st, (const double2*)h, row_stride,
+                               nparam, cf, w, nelem, (double2*)dh, scratch);
+        });
+    });
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_fisher_final, dim3((unsigned)(nparam * (nparam + 1) / 2)), dim3(256), 0,
                        st, scratch, nb, nparam, gram);
@@ -722,6 +654,7 @@ int efd_fisher_gram(const double* h, int64_t row_stride, int32_t nparam, int32_t
 static_assert(EFD_OVERLAP_SCRATCH == OV_MAXB * (3 * EFD_OVERLAP_MAX_ROWS + 1),
               "EFD_OVERLAP_SCRATCH holds every workgroup's partial of every output");
 static_assert(EFD_OVERLAP_MAX_ROWS % OV_RB == 0 && OV_RB == 8, "ov_launch's instantiations");
+static_assert(OV_THREADS == RED_THREADS && PS_THREADS == RED_THREADS, "wg_store's four waves");
 
 int efd_overlap_rows(const double* h, int64_t row_stride, int32_t nrow, const double* t,
                      const double* u, const double* w, int64_t nelem, double* out,
@@ -744,32 +677,31 @@ int efd_overlap_rows(const double* h, int64_t row_stride, int32_t nrow, const do
         HIP_TRY(hipGetLastError());
     }
     const int r0 = full * OV_RB;   // the last, narrower block
-    switch (rest) {
-        case 1: ov_launch<1>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 2: ov_launch<2>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 3: ov_launch<3>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 4: ov_launch<4>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 5: ov_launch<5>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 6: ov_launch<6>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        case 7: ov_launch<7>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem, scratch); break;
-        default: break;
-    }
+    for_value<1, 2, 3, 4, 5, 6, 7>(rest, [&](auto NR) {
+        ov_launch<decltype(NR)::value>(nb, 1, st, h2, row_stride, r0, nrow, t2, u2, w, nelem,
+                                       scratch);
+    });
     if (rest > 0) HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(3 * nrow + 1)), dim3(256), 0, st, scratch,
-                       nb, out);
+    launch_final(3 * nrow + 1, scratch, nb, 4.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
 
-// the chunks of efd_td_split_loglike for n points: a function of n alone (whole rounds of the
-// 8 XCDs once there are that many), each a multiple of 256 bins
-static int td_split_chunks(int64_t nb, int64_t* chunk) {
-    int64_t np = std::min<int64_t>(EFD_TD_SPLIT_SCRATCH, (nb + 1023) / 1024);
+static_assert(EFD_PAIR_SCRATCH == PS_MAXB * EFD_PAIR_MAX_ROWS * 2 * 5,
+              "EFD_PAIR_SCRATCH holds every workgroup's partial of every output");
+static_assert(EFD_TD_SPLIT_SCRATCH == PS_MAXB,
+              "row_chunks' one cap is the most chunks a row of either reduction has");
+
+// the chunks of a row of the TD split's likelihood (nbin = its nb) and of the pair statistics: a
+// function of nbin alone (whole rounds of the 8 XCDs once there are that many), each a multiple
+// of 256 bins and at least 1024 where nbin allows (four 16-byte loads per operand and thread)
+static int row_chunks(int64_t nbin, int64_t* chunk) {
+    int64_t np = std::min<int64_t>(PS_MAXB, (nbin + 1023) / 1024);
     if (np > 8) np -= np % 8;
-    int64_t c = (nb + np - 1) / np;
-    c = (c + 255) / 256 * 256;
+    int64_t c = (nbin + np - 1) / np;
+    c = (c + PS_THREADS - 1) / PS_THREADS * PS_THREADS;
     *chunk = c;
-    return (int)((nb + c - 1) / c);
+    return (int)((nbin + c - 1) / c);
 }
 
 int efd_td_split(const double* Z, int64_t stride, int64_t n, int32_t rows, double gain,
@@ -801,29 +733,14 @@ int efd_td_split_loglike(const double* Z, int64_t stride, int64_t n, int32_t row
     if (stride < n) return fail(EFD_ERR_ARG, "efd_td_split_loglike: stride < n");
     const int64_t nb = (n + 1) / 2;
     int64_t chunk = 0;
-    const int np = td_split_chunks(nb, &chunk);
+    const int np = row_chunks(nb, &chunk);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_td_split_loglike, dim3((unsigned)np, (unsigned)rows), dim3(256), 0, st,
                        (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)d, w, scratch);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_loglike_final, dim3((unsigned)rows), dim3(256), 0, st, scratch, np, out);
+    launch_final(rows, scratch, np, -2.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
-}
-
-static_assert(EFD_PAIR_SCRATCH == PS_MAXB * EFD_PAIR_MAX_ROWS * 2 * 5,
-              "EFD_PAIR_SCRATCH holds every workgroup's partial of every output");
-
-// the chunks of the pair statistics for nbin bins: a function of nbin alone (whole rounds of the
-// 8 XCDs once there are that many), each a multiple of 256 bins and at least 1024 where nbin
-// allows (four 16-byte loads per operand and thread)
-static int pair_chunks(int64_t nbin, int64_t* chunk) {
-    int64_t np = std::min<int64_t>(PS_MAXB, (nbin + 1023) / 1024);
-    if (np > 8) np -= np % 8;
-    int64_t c = (nbin + np - 1) / np;
-    c = (c + PS_THREADS - 1) / PS_THREADS * PS_THREADS;
-    *chunk = c;
-    return (int)((nbin + c - 1) / c);
 }
 
 int efd_pair_stats(const double* a, int64_t a_stride, const double* b, int64_t b_stride,
@@ -839,19 +756,15 @@ int efd_pair_stats(const double* a, int64_t a_stride, const double* b, int64_t b
     if (a_stride < nchan * nbin || b_stride < nchan * nbin)
         return fail(EFD_ERR_ARG, "efd_pair_stats: stride < nchan nbin");
     int64_t chunk = 0;
-    const int np = pair_chunks(nbin, &chunk);
+    const int np = row_chunks(nbin, &chunk);
     hipStream_t st = (hipStream_t)stream;
-    if (nchan == 1)
-        hipLaunchKernelGGL((k_pair_stats<1>), dim3((unsigned)np, (unsigned)nrow), dim3(PS_THREADS),
-                           0, st, (const double2*)a, a_stride, (const double2*)b, b_stride, w, nbin,
-                           chunk, scratch);
-    else
-        hipLaunchKernelGGL((k_pair_stats<2>), dim3((unsigned)np, (unsigned)nrow), dim3(PS_THREADS),
-                           0, st, (const double2*)a, a_stride, (const double2*)b, b_stride, w, nbin,
-                           chunk, scratch);
+    for_value<1, 2>(nchan, [&](auto NC) {
+        hipLaunchKernelGGL((k_pair_stats<decltype(NC)::value>), dim3((unsigned)np, (unsigned)nrow),
+                           dim3(PS_THREADS), 0, st, (const double2*)a, a_stride, (const double2*)b,
+                           b_stride, w, nbin, chunk, scratch);
+    });
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(nrow * nchan * 5)), dim3(256), 0, st,
-                       scratch, np, out);
+    launch_final(nrow * nchan * 5, scratch, np, 4.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
@@ -869,14 +782,13 @@ int efd_td_split_pair_stats(const double* Z, int64_t stride, int64_t n, int32_t 
     const int64_t nb = (n + 1) / 2;
     if (a_stride < 2 * nb) return fail(EFD_ERR_ARG, "efd_td_split_pair_stats: a_stride < 2 nb");
     int64_t chunk = 0;
-    const int np = pair_chunks(nb, &chunk);
+    const int np = row_chunks(nb, &chunk);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_td_split_pair_stats, dim3((unsigned)np, (unsigned)rows), dim3(PS_THREADS),
                        0, st, (const double2*)Z, stride, n, nb, chunk, gain, (const double2*)a,
                        a_stride, w, keep, scratch);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_overlap_final, dim3((unsigned)(rows * 10)), dim3(256), 0, st, scratch, np,
-                       out);
+    launch_final(rows * 10, scratch, np, 4.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

@@ -42,6 +42,35 @@ class Reducer:
             raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(x.shape)}")
         return torch.view_as_real(x).data_ptr() if x.is_complex() else x.data_ptr()
 
+    def _rows(self, x, msg, dim=None, nrow=None, nelem=None):
+        """(pointer, stride in complex elements, row count, elements per row) of the rows of a
+        complex128 matrix on this device: each row contiguous, the rows a fixed stride apart and
+        not overlapping. A row is x[r] whole, or with nelem given the first nelem elements of a
+        2-D x's row. dim, nrow: x's dimensions and row count where the caller fixes them.
+        ValueError(msg) where x is no such matrix, "<name>: ... overlapping rows" (the name is
+        msg's) where its rows overlap."""
+        torch = self.torch
+        if (x.dtype != torch.complex128 or x.device != self.device
+                or (x.dim() < 2 if dim is None else x.dim() != dim)
+                or (x.shape[0] < 1 if nrow is None else x.shape[0] != nrow)
+                or (not x[0].is_contiguous() if nelem is None
+                    else x.shape[1] < nelem or x.stride(1) != 1)):
+            raise ValueError(msg)
+        whole = nelem is None
+        nelem = int(x[0].numel()) if whole else nelem
+        stride = int(x.stride(0)) if x.shape[0] > 1 else nelem
+        if stride < nelem or (whole and nelem == 0):
+            raise ValueError(f"{msg.split(':')[0]}: {'empty or ' if whole else ''}overlapping rows")
+        return torch.view_as_real(x).data_ptr(), stride, int(x.shape[0]), nelem
+
+    def _scratch(self, name, size):
+        """The float64 scratch tensor `name` of `size` doubles, allocated at its first use."""
+        scr = getattr(self, name, None)
+        if scr is None:
+            scr = self.torch.empty(size, dtype=self.torch.float64, device=self.device)
+            setattr(self, name, scr)
+        return scr
+
     def loglike(self, h, d, w, out=None):
         """-1/2 * 4 * sum |d - h w|^2 over all channels and bins (likelihood.py:257-274).
 
@@ -94,14 +123,9 @@ class Reducer:
         nparam = int(coef.shape[0])
         if not 1 <= nparam <= _lib.EFD_FISHER_MAX_PARAMS:
             raise ValueError(f"nparam must be in 1..{_lib.EFD_FISHER_MAX_PARAMS}")
-        if (rows.dtype != torch.complex128 or rows.device != self.device or rows.dim() < 2
-                or rows.shape[0] != nparam * npoint or not rows[0].is_contiguous()):
-            raise ValueError(f"rows: expected complex128 [{nparam * npoint}][...] on "
-                             f"{self.device} with contiguous rows")
-        nelem = int(rows[0].numel())
-        stride = int(rows.stride(0)) if rows.shape[0] > 1 else nelem
-        if nelem == 0 or stride < nelem:
-            raise ValueError("rows: empty or overlapping rows")
+        prows, stride, _, nelem = self._rows(
+            rows, f"rows: expected complex128 [{nparam * npoint}][...] on {self.device} with "
+            "contiguous rows", nrow=nparam * npoint)
         pw = None
         if w is not None:
             if w.numel() != nelem:
@@ -112,14 +136,11 @@ class Reducer:
             if dh.numel() != nparam * nelem or dh.shape[0] != nparam:
                 raise ValueError(f"dh: expected [{nparam}][...] with {nelem} elements a row")
             pdh = self._check(dh, "dh", torch.complex128, tuple(dh.shape))
-        scr = getattr(self, "_scr_fg", None)
-        if scr is None:
-            scr = self._scr_fg = torch.empty(_lib.EFD_FISHER_SCRATCH, dtype=torch.float64,
-                                             device=self.device)
+        scr = self._scratch("_scr_fg", _lib.EFD_FISHER_SCRATCH)
         gram = torch.empty((nparam, nparam), dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.efd_fisher_gram(torch.view_as_real(rows).data_ptr(), stride, nparam,
-                                            npoint, coef.ctypes.data, pw, nelem, pdh,
-                                            gram.data_ptr(), scr.data_ptr(), self._stream()),
+        _lib.check(self.lib.efd_fisher_gram(prows, stride, nparam, npoint, coef.ctypes.data, pw,
+                                            nelem, pdh, gram.data_ptr(), scr.data_ptr(),
+                                            self._stream()),
                    "efd_fisher_gram", self.lib)
         return gram
 
@@ -144,15 +165,8 @@ class Reducer:
         """overlap_rows' numbers as efd_overlap_rows lays them out: float64 [3 nrow + 1] on the
         device, (re, im, nn) per row and then rr."""
         torch = self.torch
-        if (rows.dtype != torch.complex128 or rows.device != self.device or rows.dim() < 2
-                or rows.shape[0] < 1 or not rows[0].is_contiguous()):
-            raise ValueError(f"rows: expected complex128 [nrow][...] on {self.device} with "
-                             "contiguous rows")
-        nrow = int(rows.shape[0])
-        nelem = int(rows[0].numel())
-        stride = int(rows.stride(0)) if nrow > 1 else nelem
-        if nelem == 0 or stride < nelem:
-            raise ValueError("rows: empty or overlapping rows")
+        base, stride, nrow, nelem = self._rows(
+            rows, f"rows: expected complex128 [nrow][...] on {self.device} with contiguous rows")
         ptrs = []
         for x, name, dtype in ((t, "t", torch.complex128), (u, "u", torch.complex128),
                                (w, "w", torch.float64)):
@@ -164,16 +178,12 @@ class Reducer:
             if x.numel() != nelem:
                 raise ValueError(f"{name}: expected {nelem} elements, got {x.numel()}")
             ptrs.append(self._check(x, name, dtype, tuple(x.shape)))
-        scr = getattr(self, "_scr_ov", None)
-        if scr is None:
-            scr = self._scr_ov = torch.empty(_lib.EFD_OVERLAP_SCRATCH, dtype=torch.float64,
-                                             device=self.device)
+        scr = self._scratch("_scr_ov", _lib.EFD_OVERLAP_SCRATCH)
         M = _lib.EFD_OVERLAP_MAX_ROWS
         ncall = (nrow + M - 1) // M
         # call c writes its 3 n + 1 doubles at 3 c M: its |r|^2 lands on the next call's first
         # slot and is overwritten by it, the last call's stays at 3 nrow
         res = torch.empty(3 * nrow + 1, dtype=torch.float64, device=self.device)
-        base = torch.view_as_real(rows).data_ptr()
         for c in range(ncall):
             n = min(M, nrow - c * M)
             _lib.check(self.lib.efd_overlap_rows(base + 16 * stride * c * M, stride, n, *ptrs,
@@ -185,25 +195,16 @@ class Reducer:
     def _pair_rows(self, x, name, nchan=None):
         """(pointer, stride in complex elements, nrow, nchan, nbin) of rows complex128
         [nrow][nchan][nbin]: every row contiguous, rows a fixed stride apart."""
-        torch = self.torch
-        if (x.dtype != torch.complex128 or x.device != self.device or x.dim() != 3
-                or x.shape[0] < 1 or not x[0].is_contiguous()):
-            raise ValueError(f"{name}: expected complex128 [nrow][nchan][nbin] on {self.device} "
-                             "with contiguous rows")
-        nrow, nch, nbin = (int(v) for v in x.shape)
+        ptr, stride, nrow, _ = self._rows(
+            x, f"{name}: expected complex128 [nrow][nchan][nbin] on {self.device} with "
+            "contiguous rows", dim=3)
+        nch, nbin = int(x.shape[1]), int(x.shape[2])
         if nch not in (1, 2) or (nchan is not None and nch != nchan):
             raise ValueError(f"{name}: expected {nchan or '1 or 2'} channels, got {nch}")
-        stride = int(x.stride(0)) if nrow > 1 else nch * nbin
-        if nbin == 0 or stride < nch * nbin:
-            raise ValueError(f"{name}: empty or overlapping rows")
-        return torch.view_as_real(x).data_ptr(), stride, nrow, nch, nbin
+        return ptr, stride, nrow, nch, nbin
 
     def _pair_scratch(self):
-        scr = getattr(self, "_scr_ps", None)
-        if scr is None:
-            scr = self._scr_ps = self.torch.empty(_lib.EFD_PAIR_SCRATCH, dtype=self.torch.float64,
-                                                  device=self.device)
-        return scr
+        return self._scratch("_scr_ps", _lib.EFD_PAIR_SCRATCH)
 
     def _pair_out(self, out, nrow, nchan):
         torch = self.torch
@@ -250,14 +251,10 @@ class Reducer:
         None (a dropped bin has b = 0)."""
         torch = self.torch
         n = int(n)
-        if (Z.dtype != torch.complex128 or Z.device != self.device or Z.dim() != 2
-                or Z.shape[0] < 1 or Z.stride(1) != 1 or n < 1 or Z.shape[1] < n):
-            raise ValueError(f"Z: expected complex128 [rows][>= {n}] on {self.device} with "
-                             "contiguous rows")
-        rows = int(Z.shape[0])
-        zs = int(Z.stride(0)) if rows > 1 else n
-        if zs < n:
-            raise ValueError("Z: overlapping rows")
+        msg = f"Z: expected complex128 [rows][>= {n}] on {self.device} with contiguous rows"
+        if n < 1:
+            raise ValueError(msg)
+        pz, zs, rows, _ = self._rows(Z, msg, dim=2, nelem=n)
         nb = (n + 1) // 2
         pa, sa, nra, _, nba = self._pair_rows(a, "a", 2)
         if (nra, nba) != (rows, nb):
@@ -266,7 +263,6 @@ class Reducer:
         pk = None if keep is None else self._check(keep, "keep", torch.uint8, (nb,))
         out = self._pair_out(out, rows, 2)
         scr = self._pair_scratch()
-        pz = torch.view_as_real(Z).data_ptr()
         M = _lib.EFD_PAIR_MAX_ROWS
         for r0 in range(0, rows, M):
             m = min(M, rows - r0)
@@ -287,17 +283,12 @@ class Reducer:
         nwin = len(windows)
         if not 1 <= nwin <= _lib.EFD_WINDOW_MAX_ROWS:
             raise ValueError(f"windows: expected 1..{_lib.EFD_WINDOW_MAX_ROWS}, got {nwin}")
-        if (out.dtype != torch.complex128 or out.device != self.device or out.dim() != 2
-                or out.shape[0] != nwin or out.shape[1] < n or out.stride(1) != 1):
-            raise ValueError(f"out: expected complex128 [{nwin}][>= {n}] on {self.device}")
-        stride = int(out.stride(0)) if nwin > 1 else n
-        if stride < n:
-            raise ValueError("out: overlapping rows")
+        pout, stride, _, _ = self._rows(
+            out, f"out: expected complex128 [{nwin}][>= {n}] on {self.device}", dim=2, nrow=nwin,
+            nelem=n)
         ptrs = (ctypes.c_void_p * nwin)(*[
             None if x is None else self._check(x, "window", torch.float64, (n,))
             for x in windows])
-        _lib.check(self.lib.efd_window_rows(ph, n, ptrs, nwin,
-                                            torch.view_as_real(out).data_ptr(), stride,
-                                            self._stream()),
+        _lib.check(self.lib.efd_window_rows(ph, n, ptrs, nwin, pout, stride, self._stream()),
                    "efd_window_rows", self.lib)
         return out

@@ -585,7 +585,8 @@ int efd_window_rows(const double* h, int64_t n, const double* const* win, int32_
 
 /*
  * CPU twins: the same algorithm on HOST pointers, C++17 + OpenMP
- * (csrc/emrifd_cpu.cpp, linked into libemrifd.so). Signatures are those of the HIP entry points;
+ * (csrc/emrifd_cpu.cpp: the mode sum's and the spline build's; csrc/emrifd_reduce_cpu.cpp: the
+ * reductions', splits' and window rows'; both linked into libemrifd.so). Signatures are those of the HIP entry points;
  * `stream`, `workspace` and `scratch` are accepted for parity and ignored (pass NULL / 0). The
  * reference's CPU path is the numpy branch of the same FEW generator (check_mode_by_mode.py:50-60,
  * emri_pe.py:68-80); these twins are the CPU baseline bench.py times at 1 thread and all cores.

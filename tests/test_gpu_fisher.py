@@ -75,6 +75,14 @@ def test_matches_cpu_twin(nelem, nparam, npoint):
     assert rc == 0 and np.array_equal(G0, G)
 
 
+@pytest.mark.parametrize("nelem,nparam,npoint", [(262401, 5, 2)])
+def test_second_chunk_and_final_rounds(nelem, nparam, npoint):
+    """262,401 = 1024 * 256 + 257 elements are 1026 chunks for 1024 workgroups: workgroups 0 and
+    1 take a second chunk, the last chunk is partial, and the final pass adds 1024 partials, four
+    rounds per thread."""
+    test_matches_cpu_twin(nelem, nparam, npoint)
+
+
 @pytest.mark.parametrize("nelem,nparam,npoint", [(257, 5, 2), (8194, 6, 4)])
 def test_variants_match_cpu_twin(nelem, nparam, npoint):
     rows, coef, w = _random_case(nelem, nparam, npoint, seed=1, pad=3)

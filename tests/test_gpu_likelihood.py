@@ -96,6 +96,25 @@ def test_likelihood_matches_lisatools(g):
     np.testing.assert_array_equal(like.get_ll(g["ll_params"]), ll)
 
 
+def test_capped_workgroups_and_second_round():
+    """2 x 131,329 = 262,658 elements are more than the 1024 workgroups of efd_loglike and
+    efd_inner_product hold at one element a thread: the grid is capped, 514 threads take a second
+    element, and the final pass adds 1024 partials, four rounds per thread."""
+    from emri_frequencydomainwaveforms_amd.reductions import Reducer
+    nbin = 131329
+    rng = np.random.default_rng(7)
+    h = rng.normal(size=(2, nbin)) + 1j * rng.normal(size=(2, nbin))
+    d = (0.8 + 0.3j) * h + 0.1 * (rng.normal(size=(2, nbin)) + 1j * rng.normal(size=(2, nbin)))
+    w = rng.uniform(0.5, 2.0, size=(2, nbin))
+    red = Reducer()
+    hd, dd, wd = (torch.as_tensor(x, device="cuda") for x in (h, d, w))
+    assert _close(red.loglike(hd, dd, wd).cpu().numpy(), lo.loglike(h, d, w))
+    assert _close(red.loglike(None, dd, wd).cpu().numpy(), lo.loglike(0.0 * h, d, w))
+    for wdev, whost in ((wd, w), (None, np.ones_like(w))):
+        ref = 4.0 * np.sum(np.conj(h) * d * whost)
+        assert _close(red.inner(hd, dd, wdev).cpu().numpy(), ref)
+
+
 def test_likelihood_nan_first_bin_is_skipped(g):
     f = g["ll_f"]
     rng = np.random.default_rng(5)

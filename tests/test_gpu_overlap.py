@@ -69,6 +69,14 @@ def test_matches_cpu_twin(nelem, nrow):
     assert _close(out, ref)
 
 
+@pytest.mark.parametrize("nelem,nrow", [(262401, RB + 1)])
+def test_second_chunk_and_final_rounds(nelem, nrow):
+    """262,401 = 1024 * 256 + 257 elements are 1026 chunks for 1024 workgroups: workgroups 0 and
+    1 take a second chunk, the last chunk is partial, and the final pass adds 1024 partials, four
+    rounds per thread; 9 rows are a full row block and a narrower one."""
+    test_matches_cpu_twin(nelem, nrow)
+
+
 def test_more_chunks_than_workgroups():
     """524,293 elements are 2049 chunks for 1024 workgroups: the grid-stride loop wraps."""
     rows, t, u, w = random_case(524293, 2)

@@ -2,6 +2,7 @@
 //
 //   g++ -O1 -g -std=c++17 -fopenmp -ffp-contract=off -fsanitize=address,undefined \
 //       -fno-sanitize-recover=all -I include tools/overlap_cpu_check.cpp \
+//       emri_frequencydomainwaveforms_amd/csrc/emrifd_reduce_cpu.cpp \
 //       emri_frequencydomainwaveforms_amd/csrc/emrifd_cpu.cpp -o overlap_cpu_check
 //   ./overlap_cpu_check
 //
