@@ -316,37 +316,40 @@ int efd_stage_batch(void* pin, size_t pin_bytes, uint64_t dev_base, int32_t coun
                     const efd_modesum_args* tmpl, efd_modesum_args* args, size_t* total) {
     if (!src || !shape || !scale || !tmpl || !args || !total || count < 1) return EFD_ERR_ARG;
     auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    size_t off = 0;
-    for (int i = 0; i < count; ++i) {
+    // walker i's ten byte counts, in the order of src
+    auto sizes = [shape](int i, size_t* bytes) {
         const size_t nt = (size_t)shape[2 * i], K = (size_t)shape[2 * i + 1];
+        const size_t b[10] = {8 * nt, 8 * nt, 8 * nt, 8 * nt, 8 * nt, 16 * nt * K,
+                              4 * K, 4 * K, 16 * K, 16 * K};
+        std::copy(b, b + 10, bytes);
+    };
+    // one pass: each walker's offset, and whether every source pointer is there (reported
+    // only once the buffer is known to fit, after *total is set)
+    std::vector<size_t> woff((size_t)count + 1, 0);
+    bool null_src = false;
+    size_t bytes[10];
+    for (int i = 0; i < count; ++i) {
         if (shape[2 * i] < 2 || shape[2 * i + 1] < 1) return EFD_ERR_ARG;
-        const size_t bytes[10] = {8 * nt, 8 * nt, 8 * nt, 8 * nt, 8 * nt, 16 * nt * K,
-                                  4 * K, 4 * K, 16 * K, 16 * K};
-        for (int f = 0; f < 10; ++f) off = al(off + bytes[f]);
+        sizes(i, bytes);
+        size_t o = woff[i];
+        for (int f = 0; f < 10; ++f) {
+            o = al(o + bytes[f]);
+            null_src |= !src[10 * (size_t)i + f];
+        }
+        woff[i + 1] = o;
     }
+    const size_t off = woff[count];
     *total = off;
     if (!pin || off > pin_bytes) return EFD_ERR_WORKSPACE;
+    if (null_src) return EFD_ERR_ARG;
     char* dst = (char*)pin;
-    // each walker's offset (the sizes pass above, again), then the copies: walkers over OpenMP
-    // threads when the batch is large (config 5's groups of 16: ~2-4 MB, one thread's memcpy
-    // bandwidth made the copy most of the group's flush)
-    std::vector<size_t> woff((size_t)count + 1, 0);
-    for (int i = 0; i < count; ++i) {
-        const size_t nt = (size_t)shape[2 * i], K = (size_t)shape[2 * i + 1];
-        const size_t bytes[10] = {8 * nt, 8 * nt, 8 * nt, 8 * nt, 8 * nt, 16 * nt * K,
-                                  4 * K, 4 * K, 16 * K, 16 * K};
-        size_t o = woff[i];
-        for (int f = 0; f < 10; ++f) o = al(o + bytes[f]);
-        woff[i + 1] = o;
-        for (int f = 0; f < 10; ++f)
-            if (!src[10 * (size_t)i + f]) return EFD_ERR_ARG;
-    }
+    // the copies: walkers over OpenMP threads when the batch is large (config 5's groups of
+    // 16: ~2-4 MB, one thread's memcpy bandwidth made the copy most of the group's flush)
     const int nth = off >= ((size_t)1 << 20) ? std::min(count, 8) : 1;
 #pragma omp parallel for num_threads(nth) schedule(static) if (nth > 1)
     for (int i = 0; i < count; ++i) {
-        const size_t nt = (size_t)shape[2 * i], K = (size_t)shape[2 * i + 1];
-        const size_t bytes[10] = {8 * nt, 8 * nt, 8 * nt, 8 * nt, 8 * nt, 16 * nt * K,
-                                  4 * K, 4 * K, 16 * K, 16 * K};
+        size_t bytes[10];
+        sizes(i, bytes);
         uint64_t dp[10];
         size_t o = woff[i];
         for (int f = 0; f < 10; ++f) {
@@ -367,8 +370,8 @@ int efd_stage_batch(void* pin, size_t pin_bytes, uint64_t dev_base, int32_t coun
         a.n = (const int32_t*)(uintptr_t)dp[7];
         a.ylm_p = (const double*)(uintptr_t)dp[8];
         a.ylm_m = (const double*)(uintptr_t)dp[9];
-        a.nt = (int32_t)nt;
-        a.K = (int32_t)K;
+        a.nt = shape[2 * i];
+        a.K = shape[2 * i + 1];
         a.scale_re = scale[2 * i];
         a.scale_im = scale[2 * i + 1];
     }

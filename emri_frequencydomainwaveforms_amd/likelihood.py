@@ -299,11 +299,6 @@ class Likelihood:
     # config 4's 8 walkers are one group either way (groups of 4 or 3: -5 to -10%)
     FUSED_GROUP = min(max(1, int(os.environ.get("EFD_FUSED_GROUP", "16"))), 64)
     FUSED_DEPTH = max(1, int(os.environ.get("EFD_FUSED_DEPTH", "2")))
-    # each group's sum on the group's own stream, right behind its preparation: no
-    # cross-stream wait between the two (~12 us of idle device per group on config 4's chain,
-    # tools/chain_timeline.py), and the groups' sums need no common stream (each writes its own
-    # slice of out); the streams join once, before the copy out. False: round 3's sum stream.
-    FUSED_SUM_OWN_STREAM = os.environ.get("EFD_SUM_STREAM", "0") != "1"
     # a group's staging, upload, preparation and fused sum in one native call
     # (BatchPreparer.flush_loglike, efd_fused_group); False: the Python steps of round 5
     FUSED_NATIVE_GROUP = True
@@ -312,14 +307,16 @@ class Likelihood:
         """The pipelined path with the likelihood fused into the mode sum: per group of
         FUSED_GROUP walkers, the template chain collects each walker's host inputs
         (BatchPreparer), one upload and one efd_modesum_prepare_batch prepare the group on its
-        stream, and one efd_modesum_sum_loglike on a sum stream writes the group's
-        log-likelihoods into out (the templates never reach HBM). A group's workspaces are reused
-        only after the sum that read them (an event per group). Returns the log-likelihoods on
-        the host (copied out in the sum stream's order: one synchronisation per batch), or None,
-        before queueing anything, when the template's grid is not symmetric (the caller takes the
-        per-walker path). A walker whose preparation or sum raised a device-side error comes
-        back NaN from the kernel (efd_modesum_sum_loglike), and only then are the groups'
-        status flags read, which raises."""
+        stream, and one efd_modesum_sum_loglike right behind them on the same stream writes the
+        group's log-likelihoods into its slice of out (the templates never reach HBM; a
+        cross-stream wait between preparation and sum cost ~12 us of idle device per group on
+        config 4's chain, tools/chain_timeline.py). A group's next flush is behind its sum in
+        stream order; the streams join once, before the copy out. Returns the log-likelihoods
+        on the host (one synchronisation per batch), or None, before queueing anything, when
+        the template's grid is not symmetric (the caller takes the per-walker path). A walker
+        whose preparation or sum raised a device-side error comes back NaN from the kernel
+        (efd_modesum_sum_loglike), and only then are the groups' status flags read, which
+        raises."""
         torch = self.torch
         from .summation import BatchPreparer
         if not self._fused_grid_ok(tm, kwargs):
@@ -334,39 +331,26 @@ class Likelihood:
                                   "create_waveform", None), "caustic", "uniform")
         F = self._fused
         if F is None or F["prep"].caustic != caustic or F["prep"].group < G:
-            F = self._fused = dict(prep=BatchPreparer(max(G, self.FUSED_GROUP), self.FUSED_DEPTH,
-                                                      caustic=caustic, device=self.device),
-                                   stream=torch.cuda.Stream(self.device))
-        B, s_sum = F["prep"], F["stream"]
-        if "order" not in F:
-            # the stream handles the orderings below take (efd_stream_order: one event record
-            # and one stream wait each, in C), and one reused release event per group
-            vp = ctypes.c_void_p
-            F["order"] = (vp * (len(B.groups) + 1))(*[g["stream"].cuda_stream for g in B.groups],
-                                                     s_sum.cuda_stream)
-            F["gst"] = [g["stream"].cuda_stream for g in B.groups]
-            F["sum1"] = (vp * 1)(s_sum.cuda_stream)
-            F["ev"] = [torch.cuda.Event() for _ in B.groups]
+            B = BatchPreparer(max(G, self.FUSED_GROUP), self.FUSED_DEPTH, caustic=caustic,
+                              device=self.device)
+            # the group streams' handles, for the orderings below (efd_stream_order: one event
+            # record and one stream wait each, in C)
+            gst = [B.stream(gi).cuda_stream for gi in range(len(B.groups))]
+            F = self._fused = dict(prep=B, gst=gst, order=(ctypes.c_void_p * len(gst))(*gst))
+        B, gst = F["prep"], F["gst"]
         lib = B.lib
-        cur = torch.cuda.current_stream(self.device)
-        curh = cur.cuda_stream
-        # the streams this batch uses after the work queued so far on the current one: with the
-        # sums on the groups' own streams, only the groups' streams the batch's flushes take
-        # (B's rotation from its next group; one stream wait each)
-        if self.FUSED_SUM_OWN_STREAM:
-            key = ("ord", B._next, min(ngroups, len(B.groups)))
-            arr = F.get(key)
-            if arr is None:
-                gis = [(key[1] + k) % len(B.groups) for k in range(key[2])]
-                arr = F[key] = (ctypes.c_void_p * len(gis))(*[F["gst"][g] for g in gis])
-            _lib.check(lib.efd_stream_order(curh, arr, len(arr)), "efd_stream_order", lib)
-        else:
-            _lib.check(lib.efd_stream_order(curh, F["order"], len(F["order"])),
-                       "efd_stream_order", lib)
+        # the group streams this batch's flushes take (B's rotation from its next group), after
+        # the work queued so far on the current stream: one stream wait each
+        key = ("ord", gst.index(B.next_flush()[0].cuda_stream), min(ngroups, len(gst)))
+        arr = F.get(key)
+        if arr is None:
+            arr = F[key] = (ctypes.c_void_p * key[2])(
+                *[gst[(key[1] + k) % len(gst)] for k in range(key[2])])
+        _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
+                                        arr, len(arr)), "efd_stream_order", lib)
         pin = F.get("pin")
         if pin is None or pin.numel() < n:
             pin = F["pin"] = torch.empty(max(n, 64), dtype=torch.float64, pin_memory=True)
-        own = self.FUSED_SUM_OWN_STREAM
         native = self.FUSED_NATIVE_GROUP and hasattr(lib, "efd_fused_group")
         used = []
         try:
@@ -378,60 +362,38 @@ class Likelihood:
                     for i in range(g0, min(n, g0 + G)):
                         tm.submit(B, None, *params[i], *args, order=False, prepare_only=True,
                                   **kwargs)
-                if own and native:
-                    # the group's staging, upload, preparation and fused sum in one native call
-                    # on the group's stream (efd_fused_group), the tile constants made on it
-                    # first (once per grid)
-                    p0 = B._pending[0]
-                    sst = B.groups[B._next]["stream"]
-                    tc = self._tile_constants({"freq": p0[1], "k0": p0[4]}, sst, F)
+                # the tile constants are made on the group's stream (once per grid), before the
+                # sum that reads them
+                sst, freq, k0 = B.next_flush()
+                if native:
+                    tc = self._tile_constants(freq, k0, sst, F)
                     used.append(B.flush_loglike(self._d, self._w_templ, out, tile_const=tc,
                                                 out_off=g0))
-                    continue
-                gi, jobs = B.flush()
-                used.append(gi)
-                if own:
-                    sst = B.groups[gi]["stream"]
-                    tc = self._tile_constants(jobs[0][1], sst, F)
+                else:
+                    gi, jobs = B.flush()
+                    used.append(gi)
+                    tc = self._tile_constants(freq, k0, sst, F)
                     B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
                                   sst.cuda_stream, tile_const=tc)
-                    continue   # (the group's next flush is behind this sum on its stream)
-                _lib.check(lib.efd_stream_order(F["gst"][gi], F["sum1"], 1), "efd_stream_order",
-                           lib)
-                tc = self._tile_constants(jobs[0][1], s_sum)
-                B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
-                              s_sum.cuda_stream, tile_const=tc)
-                ev = F["ev"][gi]   # (flush waited on its previous record before this one)
-                ev.record(s_sum)
-                B.release(gi, ev)
-            if own:
-                # the other groups' streams join the last one, which copies out
-                last = used[-1]
-                vp = ctypes.c_void_p
-                for gj in sorted(set(used) - {last}):
-                    _lib.check(lib.efd_stream_order(F["gst"][gj], (vp * 1)(F["gst"][last]), 1),
-                               "efd_stream_order", lib)
-                dl = F["gst"][last]
-            else:
-                dl = s_sum.cuda_stream
-            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, dl),
+            # the other groups' streams join the last one, which copies out
+            last = used[-1]
+            for gj in sorted(set(used) - {last}):
+                _lib.check(lib.efd_stream_order(gst[gj], (ctypes.c_void_p * 1)(gst[last]), 1),
+                           "efd_stream_order", lib)
+            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, gst[last]),
                        "efd_download", lib)
         finally:
-            B._pending = []
+            B.drop_pending()
             # `out` belongs to the current stream: nothing may still write it when it is
             # returned, or freed after an exception
             if sys.exc_info()[0] is not None:
-                # a failure inside B.flush() (staging, workspace growth, preparation) may leave
+                # a failure inside a flush (staging, workspace growth, preparation) may leave
                 # a group's upload or preparation queued before that group reached `used`: wait
-                # for every group stream (and the sum stream), not only the recorded ones
-                for g in B.groups:
-                    g["stream"].synchronize()
-                if not own:
-                    s_sum.synchronize()
-            elif not own:
-                s_sum.synchronize()
+                # for every group stream, not only the recorded ones
+                for gi in range(len(gst)):
+                    B.stream(gi).synchronize()
             elif used:
-                B.groups[used[-1]]["stream"].synchronize()
+                B.stream(used[-1]).synchronize()
         host = pin[:n].numpy().copy()
         if np.isnan(host).any():
             B.wait()   # device-side errors of the groups' workspaces (sticky across reuse)
@@ -441,24 +403,23 @@ class Likelihood:
     # (efd_loglike_tile_constants; bitwise the same logL)
     fused_tile_constants = True
 
-    def _tile_constants(self, job, stream, fused=None):
+    def _tile_constants(self, freq, k0, stream, fused):
         """The fused sum's per-tile constants for (d, w_templ) on this grid, made once on
-        `stream` (ordered after the data's creation: the caller's stream waits on current).
-        With `fused` (the sums on the groups' own streams) every stream of fused["order"] is
-        then ordered after `stream`, so any group's later sum may read them."""
+        `stream`, a group's (ordered after the data's creation: it waits on the current
+        stream). Every stream of fused["order"] is then ordered after `stream`, so any group's
+        later sum may read them."""
         if not self.fused_tile_constants:
             return None
         from .summation import loglike_tile_constants
-        nf, k0 = int(job["freq"].numel()), int(job.get("k0", 0))
+        nf, k0 = int(freq.numel()), int(k0)
         key = (nf, k0, id(self._d), id(self._w_templ))
         tc = self._tile_const
         if tc is None or tc[0] != key:
             tc = self._tile_const = (key, loglike_tile_constants(
                 self._d, self._w_templ, nf, k0, stream.cuda_stream))
-            if fused is not None:
-                lib = fused["prep"].lib
-                _lib.check(lib.efd_stream_order(stream.cuda_stream, fused["order"],
-                                                len(fused["order"])), "efd_stream_order", lib)
+            lib = fused["prep"].lib
+            _lib.check(lib.efd_stream_order(stream.cuda_stream, fused["order"],
+                                            len(fused["order"])), "efd_stream_order", lib)
         return tc[1]
 
     def _fused_grid_ok(self, tm, kwargs):

@@ -47,6 +47,48 @@ def is_symmetric(freq):
     return bool(np.array_equal(f, -f[::-1]))
 
 
+_F64, _I32, _C128 = np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.complex128)
+# the mode sum's ten host inputs, in the order the native staging and the packed uploads take them
+HOST_KEYS = ("t", "phi_phi", "phi_r", "f_phi", "f_r", "amp", "m", "n", "ylm_p", "ylm_m")
+_HOST_DTYPES = (_F64,) * 5 + (_C128, _I32, _I32, _C128, _C128)
+
+
+def _host_arrays(host):
+    """(arrays, (N_t, K)) of a host dict: HOST_KEYS' ten arrays, C-contiguous, in that order and
+    in their device dtypes (amp [N_t][K], ylm_p, ylm_m complex128; m, n int32; the rest float64).
+    Arrays that already are come back as they are, the others as converted copies."""
+    arrays = [np.ascontiguousarray(host[k], dtype=dt) for k, dt in zip(HOST_KEYS, _HOST_DTYPES)]
+    nt, K = arrays[5].shape
+    if any(a.size != nt for a in arrays[:5]):
+        raise ValueError("trajectory arrays and amplitudes must share N_t")
+    if any(a.size != K for a in arrays[6:]):
+        raise ValueError("m, n, ylm_p, ylm_m must have K entries")
+    return arrays, (nt, K)
+
+
+def _packed_offsets(arrays):
+    """(offsets, total bytes >= 1) of the arrays packed in order, each 256-B aligned."""
+    offs, off = [], 0
+    for a in arrays:
+        off = (off + 255) // 256 * 256
+        offs.append(off)
+        off += a.nbytes
+    return offs, max(off, 1)
+
+
+def _pack(hb, arrays, offs):
+    """The arrays' bytes into the (pinned) uint8 numpy buffer hb at offs."""
+    for a, o in zip(arrays, offs):
+        hb[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+
+
+def _packed_views(d, arrays, offs):
+    """DeviceInputs' fields of the arrays packed in the device buffer d (complex as float64)."""
+    torch = _torch()
+    return {k: d[o:o + a.nbytes].view(torch.int32 if a.dtype == _I32 else torch.float64)
+            for k, a, o in zip(HOST_KEYS, arrays, offs)}
+
+
 @dataclass
 class DeviceInputs:
     """Hot-path inputs resident in HBM (one waveform)."""
@@ -78,35 +120,22 @@ class DeviceInputs:
         """
         torch = require_gpu()
         dev = device or torch.device("cuda", torch.cuda.current_device())
-        amps = np.ascontiguousarray(amps, dtype=np.complex128)
-        nt, K = amps.shape
-        if len(t) != nt:
-            raise ValueError("amplitude array must be [N_t, K]")
-        if nt < 2 or not np.all(np.diff(t) > 0):
+        arrays, (nt, K) = _host_arrays(dict(t=t, phi_phi=phi_phi, phi_r=phi_r, f_phi=f_phi,
+                                            f_r=f_r, amp=amps, m=m, n=n, ylm_p=ylm_p,
+                                            ylm_m=ylm_m))
+        if nt < 2 or not np.all(np.diff(arrays[0]) > 0):
             raise ValueError("trajectory times must be strictly increasing with N_t >= 2")
-        f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64).ravel()  # noqa: E731
-        c128 = lambda x: np.ascontiguousarray(x, dtype=np.complex128).view(np.float64).ravel()  # noqa: E731
-        fields = [("t", f64(t)), ("phi_phi", f64(phi_phi)), ("phi_r", f64(phi_r)),
-                  ("f_phi", f64(f_phi)), ("f_r", f64(f_r)), ("amp", amps.view(np.float64).ravel()),
-                  ("m", np.ascontiguousarray(m, dtype=np.int32).ravel()),
-                  ("n", np.ascontiguousarray(n, dtype=np.int32).ravel()),
-                  ("ylm_p", c128(ylm_p)), ("ylm_m", c128(ylm_m))]
-        views = _staged_upload([a for _, a in fields], dev, stream, staging)
-        return cls(**{name: v for (name, _), v in zip(fields, views)}, nt=int(nt), K=int(K))
+        return cls(**_staged_upload(arrays, dev, stream, staging), nt=int(nt), K=int(K))
 
 
 _STAGING = {}
 
 
 def _staged_upload(arrays, dev, stream=None, staging=None):
-    """Copy host arrays into one device buffer through a cached pinned buffer (see from_host)."""
+    """Copy _host_arrays' arrays into one device buffer through a cached pinned buffer (see
+    from_host); returns the fields' views."""
     torch = _torch()
-    offs, off = [], 0
-    for a in arrays:
-        off = (off + 255) // 256 * 256
-        offs.append(off)
-        off += a.nbytes
-    total = max(off, 1)
+    offs, total = _packed_offsets(arrays)
     if staging is None:
         staging = _STAGING.setdefault((dev.type, dev.index), {})
     st = staging
@@ -117,9 +146,7 @@ def _staged_upload(arrays, dev, stream=None, staging=None):
         st["done"] = None
     if st.get("done") is not None:
         st["done"].synchronize()        # the previous copy out of the staging buffer finished
-    hb = st["buf"].numpy()
-    for a, o in zip(arrays, offs):
-        hb[o:o + a.nbytes] = a.view(np.uint8)
+    _pack(st["buf"].numpy(), arrays, offs)
     strm = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.stream(strm):
         d = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -127,8 +154,7 @@ def _staged_upload(arrays, dev, stream=None, staging=None):
     done = torch.cuda.Event()
     done.record(strm)
     st["done"] = done
-    dt = {np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
-    return [d[o:o + a.nbytes].view(dt[a.dtype]) for a, o in zip(arrays, offs)]
+    return _packed_views(d, arrays, offs)
 
 
 # efd_modesum_workspace_bytes per (N_t, K, N_f): walkers repeat shapes, and the lookup is cheaper
@@ -285,6 +311,26 @@ class ModeSumEngine:
         return out
 
 
+def _marshal(what, jobs, one, stream):
+    """The batch calls' shared marshalling: (lib, args**, workspaces*, bytes*, count, stream
+    handle, workspaces) of 1..EFD_BATCH_MAX (engine, launch_kwargs) jobs, each job's
+    (argument struct, workspace) made by one(i, engine, kwargs); stream None: the current one
+    on the grid's device."""
+    import ctypes
+    jobs = list(jobs)
+    n = len(jobs)
+    if not 1 <= n <= _lib.EFD_BATCH_MAX:
+        raise ValueError(f"{what} takes 1..{_lib.EFD_BATCH_MAX} waveforms")
+    pairs = [one(i, eng, kw) for i, (eng, kw) in enumerate(jobs)]
+    wss = [ws for _, ws in pairs]
+    pa = (ctypes.POINTER(_lib.ModesumArgs) * n)(*[ctypes.pointer(a) for a, _ in pairs])
+    pw = (ctypes.c_void_p * n)(*[ws.data_ptr() for ws in wss])
+    pb = (ctypes.c_size_t * n)(*[ws.numel() for ws in wss])
+    if stream is None:
+        stream = _torch().cuda.current_stream(jobs[0][1]["freq"].device).cuda_stream
+    return jobs[0][0].lib, pa, pw, pb, n, stream, wss
+
+
 def sum_batch(jobs, stream=None, prof_events=(None, None)):
     """The mode sums of several prepared waveforms in one launch (efd_modesum_sum_batch).
 
@@ -295,33 +341,22 @@ def sum_batch(jobs, stream=None, prof_events=(None, None)):
     waveforms' tiles share one longest-first dispatch (one ramp, one tail, no launch gaps).
     prof_events bracket the launch. At most EFD_BATCH_MAX waveforms.
     """
-    import ctypes
-    torch = _torch()
-    jobs = list(jobs)
-    if not 1 <= len(jobs) <= _lib.EFD_BATCH_MAX:
-        raise ValueError(f"sum_batch takes 1..{_lib.EFD_BATCH_MAX} waveforms")
-    args, wss = [], []
-    for i, (eng, kw) in enumerate(jobs):
+    ptr = lambda x: x.data_ptr() if x is not None else None  # noqa: E731
+
+    def one(i, eng, kw):
         kw = dict(kw)
         a0 = kw.pop("_args", None)
-        if a0 is not None and "inp" not in kw:
-            # a BatchPreparer job: its prepare struct, with this call's outputs
-            a, ws = _lib.ModesumArgs.from_buffer_copy(a0), eng._ws
-            ptr = lambda x: x.data_ptr() if x is not None else None  # noqa: E731
-            a.out, a.hp, a.hc = ptr(kw.get("out")), ptr(kw.get("hp")), ptr(kw.get("hc"))
-            a.accumulate = 1 if kw.get("accumulate") else 0
-            a.prof_begin, a.prof_end = prof_events if i == 0 else (None, None)
-        else:
-            a, ws = eng._args(prof_events=prof_events if i == 0 else (None, None), **kw)
-        args.append(a)
-        wss.append(ws)
-    n = len(jobs)
-    pa = (ctypes.POINTER(_lib.ModesumArgs) * n)(*[ctypes.pointer(a) for a in args])
-    pw = (ctypes.c_void_p * n)(*[ws.data_ptr() for ws in wss])
-    pb = (ctypes.c_size_t * n)(*[ws.numel() for ws in wss])
-    lib = jobs[0][0].lib
-    freq = jobs[0][1]["freq"]
-    st = stream if stream is not None else torch.cuda.current_stream(freq.device).cuda_stream
+        prof = prof_events if i == 0 else (None, None)
+        if a0 is None or "inp" in kw:
+            return eng._args(prof_events=prof, **kw)
+        # a BatchPreparer job: its prepare struct, with this call's outputs
+        a = _lib.ModesumArgs.from_buffer_copy(a0)
+        a.out, a.hp, a.hc = ptr(kw.get("out")), ptr(kw.get("hp")), ptr(kw.get("hc"))
+        a.accumulate = 1 if kw.get("accumulate") else 0
+        a.prof_begin, a.prof_end = prof
+        return a, eng._ws
+
+    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch", jobs, one, stream)
     _lib.check(lib.efd_modesum_sum_batch(pa, pw, pb, n, st), "efd_modesum_sum_batch", lib)
     return wss
 
@@ -331,24 +366,12 @@ def prepare_batch(jobs, stream=None):
     (efd_modesum_prepare_batch). jobs: (engine, launch_kwargs) pairs as sum_batch takes them;
     each workspace ends bitwise as after the engine's own launch(..., phase="prepare"), so the
     jobs go on to sum_batch / sum_batch_loglike / launch(phase="sum") unchanged."""
-    import ctypes
-    torch = _torch()
-    jobs = list(jobs)
-    if not 1 <= len(jobs) <= _lib.EFD_BATCH_MAX:
-        raise ValueError(f"prepare_batch takes 1..{_lib.EFD_BATCH_MAX} waveforms")
-    args, wss = [], []
-    for eng, kw in jobs:
+    def one(i, eng, kw):
         a, ws = eng._args(**{k: v for k, v in kw.items() if k != "_args"})
         eng._last_args = a
-        args.append(a)
-        wss.append(ws)
-    n = len(jobs)
-    pa = (ctypes.POINTER(_lib.ModesumArgs) * n)(*[ctypes.pointer(a) for a in args])
-    pw = (ctypes.c_void_p * n)(*[ws.data_ptr() for ws in wss])
-    pb = (ctypes.c_size_t * n)(*[ws.numel() for ws in wss])
-    lib = jobs[0][0].lib
-    freq = jobs[0][1]["freq"]
-    st = stream if stream is not None else torch.cuda.current_stream(freq.device).cuda_stream
+        return a, ws
+
+    lib, pa, pw, pb, n, st, wss = _marshal("prepare_batch", jobs, one, stream)
     _lib.check(lib.efd_modesum_prepare_batch(pa, pw, pb, n, st), "efd_modesum_prepare_batch",
                lib)
     return wss
@@ -399,31 +422,20 @@ def sum_batch_loglike(jobs, d, w, out, stream=None, tile_const=None):
     (contiguous, on the device), out: float64 [len(jobs)] on the device (written in stream
     order, no host synchronisation). tile_const: loglike_tile_constants(d, w, nf, k0), or None.
     """
-    import ctypes
     torch = _torch()
     jobs = list(jobs)
-    if not 1 <= len(jobs) <= _lib.EFD_BATCH_MAX:
-        raise ValueError(f"sum_batch_loglike takes 1..{_lib.EFD_BATCH_MAX} waveforms")
-    freq = jobs[0][1]["freq"]
-    nb = int(freq.numel()) - int(jobs[0][1].get("k0", 0))
-    _check_ll_io(torch, d, w, out, nb, len(jobs))
-    args, wss = [], []
-    for eng, kw in jobs:
+    if jobs:   # (none: the marshaller's count check raises)
+        kw0 = jobs[0][1]
+        _check_ll_io(torch, d, w, out, int(kw0["freq"].numel()) - int(kw0.get("k0", 0)),
+                     len(jobs))
+
+    def one(i, eng, kw):
         kw = dict(kw)
-        a = kw.pop("_args", None)   # the prepare call's own struct (WaveformPipeline jobs)
-        if a is None:
-            a, ws = eng._args(**kw)
-        else:
-            ws = eng._ws
-        args.append(a)
-        wss.append(ws)
-    n = len(jobs)
-    pa = (ctypes.POINTER(_lib.ModesumArgs) * n)(*[ctypes.pointer(a) for a in args])
-    pw = (ctypes.c_void_p * n)(*[ws.data_ptr() for ws in wss])
-    pb = (ctypes.c_size_t * n)(*[ws.numel() for ws in wss])
-    lib = jobs[0][0].lib
-    st = stream if stream is not None else torch.cuda.current_stream(freq.device).cuda_stream
-    tc = _tile_const_ptr(tile_const, freq.numel(), lib)
+        a = kw.pop("_args", None)   # the prepare call's own struct, as it is
+        return (a, eng._ws) if a is not None else eng._args(**kw)
+
+    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_loglike", jobs, one, stream)
+    tc = _tile_const_ptr(tile_const, jobs[0][1]["freq"].numel(), lib)
     _lib.check(lib.efd_modesum_sum_loglike_ex(pa, pw, pb, n, torch.view_as_real(d).data_ptr(),
                                               w.data_ptr(), tc, out.data_ptr(), st),
                "efd_modesum_sum_loglike_ex", lib)
@@ -522,27 +534,10 @@ class WaveformPipeline:
         buffer, one asynchronous copy on the slot's stream (efd_upload). Buffers grow as needed
         and are reused in stream order; the field views are rebuilt only when (nt, K) change."""
         torch = _torch()
-        amps = np.ascontiguousarray(host["amp"], dtype=np.complex128)
-        nt, K = amps.shape
-        t = np.ascontiguousarray(host["t"], dtype=np.float64)
-        if len(t) != nt:
-            raise ValueError("amplitude array must be [N_t, K]")
-        f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64).ravel()  # noqa: E731
-        c128 = lambda x: np.ascontiguousarray(x, dtype=np.complex128).view(np.float64).ravel()  # noqa: E731
-        arrays = [t, f64(host["phi_phi"]), f64(host["phi_r"]), f64(host["f_phi"]),
-                  f64(host["f_r"]), amps.view(np.float64).ravel(),
-                  np.ascontiguousarray(host["m"], dtype=np.int32).ravel(),
-                  np.ascontiguousarray(host["n"], dtype=np.int32).ravel(),
-                  c128(host["ylm_p"]), c128(host["ylm_m"])]
-        key = (nt, K)
+        arrays, key = _host_arrays(host)
         lay = sl.get("layout")
         if lay is None or lay[0] != key:
-            offs, off = [], 0
-            for a in arrays:
-                off = (off + 255) // 256 * 256
-                offs.append(off)
-                off += a.nbytes
-            lay = (key, offs, max(off, 1))
+            lay = (key,) + _packed_offsets(arrays)
         _, offs, total = lay
         if sl.get("pin") is None or sl["pin"].numel() < total:
             if sl.get("pin_done") is not None:
@@ -554,9 +549,7 @@ class WaveformPipeline:
             sl["pin_done"] = None
         if sl.get("pin_done") is not None:
             sl["pin_done"].synchronize()   # the slot's previous copy out of the pinned buffer
-        hb = sl["pin_np"]
-        for a, o in zip(arrays, offs):
-            hb[o:o + a.nbytes] = a.view(np.uint8)
+        _pack(sl["pin_np"], arrays, offs)
         if sl.get("dbuf") is None or sl["dbuf"].numel() < total:
             with torch.cuda.stream(sl["stream"]):
                 sl["dbuf"] = torch.empty(max(2 * total, 1 << 20), dtype=torch.uint8,
@@ -569,11 +562,8 @@ class WaveformPipeline:
             sl["pin_done"] = torch.cuda.Event()
         sl["pin_done"].record(sl["stream"])
         if sl.get("layout") is None or sl["layout"][0] != key or sl.get("inp") is None:
-            d = sl["dbuf"]
-            dt = {np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
-            views = [d[o:o + a.nbytes].view(dt[a.dtype]) for a, o in zip(arrays, offs)]
-            names = ("t", "phi_phi", "phi_r", "f_phi", "f_r", "amp", "m", "n", "ylm_p", "ylm_m")
-            sl["inp"] = DeviceInputs(**dict(zip(names, views)), nt=int(nt), K=int(K))
+            sl["inp"] = DeviceInputs(**_packed_views(sl["dbuf"], arrays, offs),
+                                     nt=int(key[0]), K=int(key[1]))
             sl["layout"] = lay
         return sl["inp"]
 
@@ -593,8 +583,48 @@ class WaveformPipeline:
         self.join()
 
 
-_F64 = np.dtype(np.float64)
-_I32 = np.dtype(np.int32)
+class _Group:
+    """One of a BatchPreparer's rotating walker groups: `size` engines (a workspace each), the
+    stream its work runs on, its staging buffers and the argument arrays the native calls take."""
+
+    def __init__(self, size, caustic, device):
+        import ctypes
+        torch = _torch()
+        self.engines = [ModeSumEngine(caustic=caustic) for _ in range(size)]
+        self.stream = torch.cuda.Stream(device)
+        # the pinned staging buffer and its device copy (BatchPreparer._stage grows them)
+        self.pin = self.dbuf = None
+        # recorded after every copy out of `pin`; this first record, on the still empty stream,
+        # creates the handle efd_fused_group re-records
+        self.pin_done = torch.cuda.Event()
+        self.pin_done.record(self.stream)
+        self.busy = None      # release()'s event: the group's last sum has read its workspaces
+        self.used = False
+        self.n = 0            # walkers of the group's last flush
+        # the walkers' argument structs, with the args** table, the workspace pointer and size
+        # arrays of the batch calls, and the three arrays' addresses for efd_fused_group
+        args_t, args_pp = _lib.ModesumArgs, ctypes.POINTER(ctypes.POINTER(_lib.ModesumArgs))
+        self.args = (args_t * size)()
+        self.args_ptr = ctypes.addressof(self.args)
+        self.pa = ctypes.cast((ctypes.c_void_p * size)(
+            *[self.args_ptr + i * ctypes.sizeof(args_t) for i in range(size)]), args_pp)
+        self.pw = (ctypes.c_void_p * size)()
+        self.pb = (ctypes.c_size_t * size)()
+        self.pw_ptr, self.pb_ptr = ctypes.addressof(self.pw), ctypes.addressof(self.pb)
+        self.arg_views = [self.args[i] for i in range(size)]   # stable per-walker views
+        self.tmpl = None      # (key, template struct) of the last flush (BatchPreparer._take)
+        self.ws_floor = None  # (device, smallest workspace, walkers) flush_loglike sized last
+        # (first, count, args**, workspaces*, bytes*) per launch of at most EFD_BATCH_MAX of
+        # the group's first n walkers, for every n: pointers into the arrays above
+        self.chunks = [None]
+        pa0 = ctypes.cast(self.pa, ctypes.c_void_p).value
+        step = _lib.EFD_BATCH_MAX
+        for n in range(1, size + 1):
+            self.chunks.append([
+                (c0, min(step, n - c0), ctypes.cast(pa0 + 8 * c0, args_pp),
+                 ctypes.cast(self.pw_ptr + 8 * c0, ctypes.POINTER(ctypes.c_void_p)),
+                 ctypes.cast(self.pb_ptr + 8 * c0, ctypes.POINTER(ctypes.c_size_t)))
+                for c0 in range(0, n, step)])
 
 
 class BatchPreparer:
@@ -621,14 +651,13 @@ class BatchPreparer:
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.caustic = caustic
         self.group = group
-        self.groups = [dict(engines=[ModeSumEngine(caustic=caustic) for _ in range(group)],
-                            stream=torch.cuda.Stream(self.device), pin=None, pin_np=None,
-                            pin_done=None, dbuf=None, busy=None, used=False)
-                       for _ in range(depth)]
-        self.lib = self.groups[0]["engines"][0].lib
+        self.groups = [_Group(group, caustic, self.device) for _ in range(depth)]
+        self.lib = self.groups[0].engines[0].lib
         self._next = 0
         self._pending = []
-        self._jobs = []      # the last flush()'s (engine, job) pairs (last_jobs)
+        self._jobs = []          # the last flush()'s (engine, job) pairs (last_jobs)
+        self._last = None        # (gi, n, freq, k0, sym) of the last flush_loglike (last_jobs)
+        self._ll_checked = None  # the (d, w, bins) flush_loglike checked last
 
     # -- the WaveformPipeline surface the template chain uses ---------------------------------
     def next_slot(self):
@@ -648,120 +677,115 @@ class BatchPreparer:
         torch = _torch()
         cur = torch.cuda.current_stream(self.device)
         for g in self.groups:
-            g["stream"].wait_stream(cur)
+            g.stream.wait_stream(cur)
 
     def stream(self, gi):
-        return self.groups[gi]["stream"]
+        return self.groups[gi].stream
+
+    def drop_pending(self):
+        """Forget the walkers submitted since the last flush (a caller's error path)."""
+        self._pending = []
+
+    def next_flush(self):
+        """(stream, freq, k0) of the next flush() / flush_loglike(): the stream of the group it
+        rotates to and the pending walkers' grid (None, None while nothing is pending)."""
+        p = self._pending
+        freq, k0 = (p[0][1], p[0][4]) if p else (None, None)
+        return self.groups[self._next].stream, freq, k0
+
+    def workspace_ptrs(self, gi):
+        """Group gi's workspace pointer array (void*[group]; its last flush's walkers first)."""
+        return self.groups[gi].pw
 
     # -- one batch -----------------------------------------------------------------------------
-    # optional section timers of flush (tools/halfstep_host.py sets a dict: seconds per section)
-    FLUSH_TIMERS = None
-
-    def flush(self):
-        """Upload and prepare the collected walkers; returns (group index, jobs). A job's
-        argument struct lives in the group's reused array: use the jobs before the group's next
-        flush (sum_batch / sum_batch_loglike copy what they need)."""
-        import ctypes
-        import time
-        T = self.FLUSH_TIMERS
-        t_0 = time.perf_counter() if T is not None else 0.0
-        torch = _torch()
+    def _take(self, what):
+        """The pending walkers for the next group: (group index, group, walkers, template
+        struct). The walkers are checked first (one grid; symmetry, k0 and accumulate agree);
+        then the groups rotate and the group's stream waits for the sum that last read its
+        workspaces, the host for the last copy out of its pinned buffer."""
         pend, self._pending = self._pending, []
         if not pend:
-            raise ValueError("flush: nothing submitted")
+            raise ValueError(f"{what}: nothing submitted")
+        _, freq, sym, _, k0, acc = pend[0]
+        nf = int(freq.numel())
+        for _, f, s, _, k, a in pend:
+            if f is not freq and (int(f.numel()) != nf or f.data_ptr() != freq.data_ptr()):
+                raise ValueError("flush: the walkers of a group share one frequency grid")
+            if s != sym or k != k0 or a != acc:
+                raise ValueError("flush: grid symmetry, k0 and accumulate must agree in a group")
         gi = self._next
         self._next = (gi + 1) % len(self.groups)
         G = self.groups[gi]
-        st = G["stream"]
-        if G["busy"] is not None:
-            st.wait_event(G["busy"])        # the group's last sum has read its workspaces
-        if G["pin_done"] is not None:
-            G["pin_done"].synchronize()     # the group's previous copy out of the pinned buffer
+        if G.busy is not None:
+            G.stream.wait_event(G.busy)
+        G.pin_done.synchronize()
+        key = (freq.data_ptr(), nf, sym, acc, k0)
+        if G.tmpl is None or G.tmpl[0] != key:
+            G.tmpl = (key, _lib.ModesumArgs(
+                freq=freq.data_ptr(), nf=nf, grid_symmetric=1 if sym else 0,
+                caustic=CAUSTIC_MODES[self.caustic], accumulate=1 if acc else 0, k0=k0))
+        return gi, G, pend, G.tmpl[1]
+
+    @staticmethod
+    def _sources(pend):
+        """(src, shape, scale, keep) of efd_stage_batch for the pending walkers: the native
+        upstream's packed addresses and shapes (host["_src"], host["_shape"]: bytes) joined in
+        one call when every walker has them, or row by row with the other walkers' arrays
+        converted (_host_arrays; kept alive in keep until the staging copy)."""
         n = len(pend)
-        if "args" not in G:
-            self.flush_setup(G)
-        freq = pend[0][1]
-        nf = int(freq.numel())
-        for _, f, sym, _, k0, acc in pend:
-            if f is not freq and (int(f.numel()) != nf or f.data_ptr() != freq.data_ptr()):
-                raise ValueError("flush: the walkers of a group share one frequency grid")
-        _, _, sym, _, k0, acc = pend[0]
-        tmpl = _lib.ModesumArgs(freq=freq.data_ptr(), nf=nf, grid_symmetric=1 if sym else 0,
-                                caustic=CAUSTIC_MODES[self.caustic],
-                                accumulate=1 if acc else 0, k0=k0)
-        if any(p[2] != sym or p[4] != k0 or p[5] != acc for p in pend):
-            raise ValueError("flush: grid symmetry, k0 and accumulate must agree in a group")
-        keep = []    # arrays converted here stay alive until the staging copy below
+        keep = []
         fast = [p[0].get("_src") for p in pend]
         scale = np.array([p[3] for p in pend], dtype=np.complex128).view(np.float64)
-        allfast = None not in fast
-        if allfast:
-            # the native upstream's walkers (prepare() packs their arrays' addresses and shape
-            # as bytes): one join per group instead of a conversion row by row
+        if None not in fast:
             src = np.frombuffer(b"".join(fast), dtype=np.uint64)
             shape = np.frombuffer(b"".join([p[0]["_shape"] for p in pend]),
                                   dtype=np.int32).reshape(n, 2)
-        else:
-            src = np.empty((n, 10), dtype=np.uint64)
-            shape = np.empty((n, 2), dtype=np.int32)
-        for i, (host, _, _, sc, _, _) in enumerate(() if allfast else pend):
+            return src, shape, scale, keep
+        src = np.empty((n, 10), dtype=np.uint64)
+        shape = np.empty((n, 2), dtype=np.int32)
+        for i, p in enumerate(pend):
             if fast[i] is not None:
                 src[i] = np.frombuffer(fast[i], dtype=np.uint64)
-                shape[i] = np.frombuffer(host["_shape"], dtype=np.int32)
+                shape[i] = np.frombuffer(p[0]["_shape"], dtype=np.int32)
             else:
-                amps = np.ascontiguousarray(host["amp"], dtype=np.complex128)
-                nt, K = amps.shape
-                arrays = [np.ascontiguousarray(host[k], dtype=_F64)
-                          for k in ("t", "phi_phi", "phi_r", "f_phi", "f_r")]
-                arrays += [amps, np.ascontiguousarray(host["m"], dtype=_I32),
-                           np.ascontiguousarray(host["n"], dtype=_I32),
-                           np.ascontiguousarray(host["ylm_p"], dtype=np.complex128),
-                           np.ascontiguousarray(host["ylm_m"], dtype=np.complex128)]
-                if any(a.size != nt for a in arrays[:5]):
-                    raise ValueError("trajectory arrays and amplitudes must share N_t")
-                if any(a.size != K for a in arrays[6:]):
-                    raise ValueError("m, n, ylm_p, ylm_m must have K entries")
+                arrays, shape[i] = _host_arrays(p[0])
                 keep.append(arrays)
                 src[i] = [a.ctypes.data for a in arrays]
-                shape[i] = (nt, K)
-        if T is not None:
-            t_1 = time.perf_counter()
-            T["wait+src"] = T.get("wait+src", 0.0) + t_1 - t_0
+        return src, shape, scale, keep
+
+    def _stage(self, G, call, failed):
+        """The staging call call(pin, pin bytes, dbuf, dbuf bytes, &total) on G's buffers
+        (efd_stage_batch, or efd_fused_group, which goes on to the launches); a buffer too
+        small for `total` is grown to max(2 * total, 1 MiB) (the device one on G's stream) and
+        the call made once more. Returns total; failed(rc) is the error's text."""
+        import ctypes
+        torch = _torch()
         total = ctypes.c_size_t(0)
         for attempt in range(2):
-            pin = G["pin"]
-            dbuf = G["dbuf"]
-            rc = self.lib.efd_stage_batch(
-                pin.data_ptr() if pin is not None else None, pin.numel() if pin is not None else 0,
-                dbuf.data_ptr() if dbuf is not None else 0, n, src.ctypes.data,
-                shape.ctypes.data, scale.ctypes.data, ctypes.byref(tmpl), G["args"],
-                ctypes.byref(total))
-            if rc == _lib.EFD_OK and dbuf is not None and dbuf.numel() >= total.value:
-                break
+            pin, dbuf = G.pin, G.dbuf
+            rc = call(pin.data_ptr() if pin is not None else 0,
+                      pin.numel() if pin is not None else 0,
+                      dbuf.data_ptr() if dbuf is not None else 0,
+                      dbuf.numel() if dbuf is not None else 0, ctypes.byref(total))
+            need = total.value
+            if rc == _lib.EFD_OK and dbuf is not None and dbuf.numel() >= need:
+                return need
             if rc not in (_lib.EFD_OK, _lib.EFD_ERR_WORKSPACE) or attempt == 1:
-                raise _lib.EFDError(f"efd_stage_batch failed ({rc})")
-            cap = max(2 * total.value, 1 << 20)
-            G["pin"] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-            with torch.cuda.stream(st):
-                G["dbuf"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
-        del keep
-        if T is not None:
-            t_2 = time.perf_counter()
-            T["stage"] = T.get("stage", 0.0) + t_2 - t_1
-        _lib.check(self.lib.efd_upload(G["dbuf"].data_ptr(), G["pin"].data_ptr(), total.value,
-                                       st.cuda_stream), "efd_upload", self.lib)
-        if G["pin_done"] is None:
-            G["pin_done"] = torch.cuda.Event()
-        G["pin_done"].record(st)
-        A, pw, pb = G["args"], G["pw"], G["pb"]
-        if "A_i" not in G:   # stable views of the group's argument structs, made once
-            G["A_i"] = [A[i] for i in range(self.group)]
-        A_i, engines = G["A_i"], G["engines"]
-        if T is not None:
-            t_3 = time.perf_counter()
-            T["upload+event"] = T.get("upload+event", 0.0) + t_3 - t_2
+                raise _lib.EFDError(failed(rc))
+            cap = max(2 * need, 1 << 20)
+            if pin is None or pin.numel() < need:
+                G.pin = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            if dbuf is None or dbuf.numel() < need:
+                with torch.cuda.stream(G.stream):
+                    G.dbuf = torch.empty(cap, dtype=torch.uint8, device=self.device)
+
+    def _size_each(self, G, shape, freq, k0, sym):
+        """flush()'s workspaces: every engine sized for its own walker's (N_t, K) (the
+        generator's batches vary widely in K). Fills the group's pointer and size arrays and
+        returns the walkers' jobs."""
+        nf, dev, st = int(freq.numel()), freq.device, G.stream
+        pw, pb, views, engines = G.pw, G.pb, G.arg_views, G.engines
         jobs = []
-        dev = freq.device
         for i, (nt_i, K_i) in enumerate(shape.tolist()):
             eng = engines[i]
             nbytes = _WS_BYTES.get((nt_i, K_i, nf))
@@ -769,19 +793,59 @@ class BatchPreparer:
                 eng._workspace(nt_i, K_i, nf, dev, stream=st)   # sized, or grown, here
             pw[i] = eng._ws_ptr
             pb[i] = eng._ws_cap
-            a_i = A_i[i]
+            a_i = views[i]
             eng._last_args = a_i
             jobs.append((eng, {"freq": freq, "k0": k0, "grid_symmetric": sym, "_args": a_i}))
-        if T is not None:
-            t_4 = time.perf_counter()
-            T["jobs"] = T.get("jobs", 0.0) + t_4 - t_3
-        for c0, cnt, pa_c, pw_c, pb_c in self._chunks(G, n):
-            _lib.check(self.lib.efd_modesum_prepare_batch(pa_c, pw_c, pb_c, cnt, st.cuda_stream),
-                       "efd_modesum_prepare_batch", self.lib)
-        if T is not None:
-            T["prepare_batch"] = T.get("prepare_batch", 0.0) + time.perf_counter() - t_4
-        G["used"] = True
-        G["n"] = n
+        return jobs
+
+    def _size_group(self, G, shape, freq):
+        """flush_loglike()'s workspaces: sized for the group's largest (N_t, K) (the layout
+        grows with both), so once every engine holds that much the pointer and size arrays
+        stand as they are and no per-walker step is needed."""
+        nf, dev, n = int(freq.numel()), freq.device, len(shape)
+        kb = (int(shape[:, 0].max()), int(shape[:, 1].max()), nf)
+        nbmax = _WS_BYTES.get(kb)
+        if nbmax is None:
+            nbmax = int(self.lib.efd_modesum_workspace_bytes(*kb))
+            if nbmax == 0:
+                raise _lib.EFDError("efd_modesum_workspace_bytes rejected the shape")
+            _WS_BYTES[kb] = nbmax
+        floor = G.ws_floor
+        if floor is None or floor[0] != dev or floor[1] < nbmax or floor[2] < n:
+            engines = G.engines
+            for i in range(n):
+                eng = engines[i]
+                if eng._ws is None or eng._ws_cap < nbmax or eng._ws_dev != dev:
+                    eng._workspace(kb[0], kb[1], nf, dev, stream=G.stream)   # sized, or grown
+                G.pw[i] = eng._ws_ptr
+                G.pb[i] = eng._ws_cap
+                eng._last_args = G.arg_views[i]
+            G.ws_floor = (dev, min(engines[i]._ws_cap for i in range(n)), n)
+
+    def flush(self):
+        """Upload and prepare the collected walkers; returns (group index, jobs). A job's
+        argument struct lives in the group's reused array: use the jobs before the group's next
+        flush (sum_batch / sum_batch_loglike copy what they need)."""
+        import ctypes
+        gi, G, pend, tmpl = self._take("flush")
+        _, freq, sym, _, k0, _ = pend[0]
+        n, lib, st = len(pend), self.lib, G.stream
+        src, shape, scale, keep = self._sources(pend)
+        total = self._stage(
+            G, lambda pin, pin_bytes, dbuf, dbuf_bytes, total: lib.efd_stage_batch(
+                pin, pin_bytes, dbuf, n, src.ctypes.data, shape.ctypes.data, scale.ctypes.data,
+                ctypes.byref(tmpl), G.args, total),
+            lambda rc: f"efd_stage_batch failed ({rc})")
+        del keep
+        _lib.check(lib.efd_upload(G.dbuf.data_ptr(), G.pin.data_ptr(), total, st.cuda_stream),
+                   "efd_upload", lib)
+        G.pin_done.record(st)
+        jobs = self._size_each(G, shape, freq, k0, sym)
+        for c0, cnt, pa_c, pw_c, pb_c in G.chunks[n]:
+            _lib.check(lib.efd_modesum_prepare_batch(pa_c, pw_c, pb_c, cnt, st.cuda_stream),
+                       "efd_modesum_prepare_batch", lib)
+        G.used = True
+        G.n = n
         self._jobs, self._last = jobs, None
         return gi, jobs
 
@@ -795,30 +859,9 @@ class BatchPreparer:
         out[out_off : out_off + n]."""
         import ctypes
         torch = _torch()
-        pend, self._pending = self._pending, []
-        if not pend:
-            raise ValueError("flush_loglike: nothing submitted")
-        gi = self._next
-        self._next = (gi + 1) % len(self.groups)
-        G = self.groups[gi]
-        st = G["stream"]
-        if G["busy"] is not None:
-            st.wait_event(G["busy"])        # the group's last sum has read its workspaces
-        if G["pin_done"] is None:
-            G["pin_done"] = torch.cuda.Event()
-            G["pin_done"].record(st)        # (the native call re-records its handle)
-        G["pin_done"].synchronize()         # the group's previous copy out of the pinned buffer
-        n = len(pend)
-        if "args" not in G:
-            self.flush_setup(G)
-        freq = pend[0][1]
-        nf = int(freq.numel())
-        for _, f, sym, _, k0, acc in pend:
-            if f is not freq and (int(f.numel()) != nf or f.data_ptr() != freq.data_ptr()):
-                raise ValueError("flush: the walkers of a group share one frequency grid")
-        _, _, sym, _, k0, acc = pend[0]
-        if any(p[2] != sym or p[4] != k0 or p[5] != acc for p in pend):
-            raise ValueError("flush: grid symmetry, k0 and accumulate must agree in a group")
+        gi, G, pend, tmpl = self._take("flush_loglike")
+        _, freq, sym, _, k0, _ = pend[0]
+        n, lib, nf = len(pend), self.lib, int(freq.numel())
         dp, wp = d.data_ptr(), w.data_ptr()
         key = (dp, wp, nf - k0)
         if self._ll_checked != key:
@@ -826,66 +869,22 @@ class BatchPreparer:
             self._ll_checked = key
         if out.dtype != torch.float64 or out.numel() < out_off + n or not out.is_contiguous():
             raise ValueError(f"flush_loglike: out float64 [>= {out_off + n}], contiguous")
-        tkey = (freq.data_ptr(), nf, sym, acc, k0)
-        tmpl = G.get("tmpl")
-        if tmpl is None or tmpl[0] != tkey:
-            tmpl = G["tmpl"] = (tkey, _lib.ModesumArgs(
-                freq=freq.data_ptr(), nf=nf, grid_symmetric=1 if sym else 0,
-                caustic=CAUSTIC_MODES[self.caustic], accumulate=1 if acc else 0, k0=k0))
-        tmpl = tmpl[1]
         src, shape, scale, keep = self._sources(pend)
-        pw, pb, engines = G["pw"], G["pb"], G["engines"]
-        dev = freq.device
-        # the workspaces: sized for the group's largest (N_t, K) (the layout grows with both),
-        # so once every engine holds that much the pointer and size arrays stand as they are
-        # and no per-walker step is needed
-        kb = (int(shape[:, 0].max()), int(shape[:, 1].max()), nf)
-        nbmax = _WS_BYTES.get(kb)
-        if nbmax is None:
-            nbmax = int(self.lib.efd_modesum_workspace_bytes(*kb))
-            if nbmax == 0:
-                raise _lib.EFDError("efd_modesum_workspace_bytes rejected the shape")
-            _WS_BYTES[kb] = nbmax
-        floor = G.get("ws_floor")
-        if floor is None or floor[0] != dev or floor[1] < nbmax or floor[2] < n:
-            for i in range(n):
-                eng = engines[i]
-                if eng._ws is None or eng._ws_cap < nbmax or eng._ws_dev != dev:
-                    eng._workspace(kb[0], kb[1], nf, dev, stream=st)   # sized, or grown
-                pw[i] = eng._ws_ptr
-                pb[i] = eng._ws_cap
-                eng._last_args = G["A_i"][i]
-            G["ws_floor"] = (dev, min(engines[i]._ws_cap for i in range(n)), n)
-        total = ctypes.c_size_t(0)
+        self._size_group(G, shape, freq)
         tcp = tile_const.data_ptr() if tile_const is not None else None
         op = out.data_ptr() + 8 * out_off
-        for attempt in range(2):
-            pin, dbuf = G["pin"], G["dbuf"]
-            rc = self.lib.efd_fused_group(
-                pin.data_ptr() if pin is not None else None, pin.numel() if pin is not None else 0,
-                dbuf.data_ptr() if dbuf is not None else None,
-                dbuf.numel() if dbuf is not None else 0, n, src.ctypes.data, shape.ctypes.data,
-                scale.ctypes.data, ctypes.byref(tmpl), G["args_ptr"], G["pw_ptr"], G["pb_ptr"],
-                dp, wp, tcp, op, G["pin_done"].cuda_event, st.cuda_stream,
-                ctypes.byref(total))
-            if rc == _lib.EFD_OK:
-                break
-            if rc != _lib.EFD_ERR_WORKSPACE or attempt == 1:
-                raise _lib.EFDError(f"efd_fused_group: {_lib.last_error(self.lib)} ({rc})")
-            cap = max(2 * total.value, 1 << 20)
-            if pin is None or pin.numel() < total.value:
-                G["pin"] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-            if dbuf is None or dbuf.numel() < total.value:
-                with torch.cuda.stream(st):
-                    G["dbuf"] = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        ev, sth = G.pin_done.cuda_event, G.stream.cuda_stream
+        self._stage(
+            G, lambda pin, pin_bytes, dbuf, dbuf_bytes, total: lib.efd_fused_group(
+                pin, pin_bytes, dbuf, dbuf_bytes, n, src.ctypes.data, shape.ctypes.data,
+                scale.ctypes.data, ctypes.byref(tmpl), G.args_ptr, G.pw_ptr, G.pb_ptr, dp, wp,
+                tcp, op, ev, sth, total),
+            lambda rc: f"efd_fused_group: {_lib.last_error(lib)} ({rc})")
         del keep
-        G["used"] = True
-        G["n"] = n
+        G.used = True
+        G.n = n
         self._last = (gi, n, freq, k0, sym)
         return gi
-
-    _ll_checked = None
-    _last = None
 
     @property
     def last_jobs(self):
@@ -894,77 +893,20 @@ class BatchPreparer:
             return self._jobs
         gi, n, freq, k0, sym = self._last
         G = self.groups[gi]
-        return [(G["engines"][i], {"freq": freq, "k0": k0, "grid_symmetric": sym,
-                                   "_args": G["A_i"][i]}) for i in range(n)]
-
-    def flush_setup(self, G):
-        """A group's argument array, its pointer table and the workspace pointer / size arrays
-        (made once per group)."""
-        import ctypes
-        A = G["args"] = (_lib.ModesumArgs * self.group)()
-        size = ctypes.sizeof(_lib.ModesumArgs)
-        base = ctypes.addressof(A)
-        G["pa"] = ctypes.cast((ctypes.c_void_p * self.group)(
-            *[base + i * size for i in range(self.group)]),
-            ctypes.POINTER(ctypes.POINTER(_lib.ModesumArgs)))
-        G["pw"] = (ctypes.c_void_p * self.group)()
-        G["pb"] = (ctypes.c_size_t * self.group)()
-        G["args_ptr"] = base
-        G["pw_ptr"] = ctypes.addressof(G["pw"])
-        G["pb_ptr"] = ctypes.addressof(G["pb"])
-        G["A_i"] = [A[i] for i in range(self.group)]
-
-    @staticmethod
-    def _sources(pend):
-        """(src, shape, scale, keep) of efd_stage_batch for the pending walkers: the native
-        upstream's packed addresses joined, or each walker's arrays converted (kept alive in
-        keep until the staging copy)."""
-        n = len(pend)
-        keep = []
-        fast = [p[0].get("_src") for p in pend]
-        scale = np.array([p[3] for p in pend], dtype=np.complex128).view(np.float64)
-        if None not in fast:
-            src = np.frombuffer(b"".join(fast), dtype=np.uint64)
-            shape = np.frombuffer(b"".join([p[0]["_shape"] for p in pend]),
-                                  dtype=np.int32).reshape(n, 2)
-            return src, shape, scale, keep
-        src = np.empty((n, 10), dtype=np.uint64)
-        shape = np.empty((n, 2), dtype=np.int32)
-        for i, (host, _, _, _, _, _) in enumerate(pend):
-            if fast[i] is not None:
-                src[i] = np.frombuffer(fast[i], dtype=np.uint64)
-                shape[i] = np.frombuffer(host["_shape"], dtype=np.int32)
-                continue
-            amps = np.ascontiguousarray(host["amp"], dtype=np.complex128)
-            nt, K = amps.shape
-            arrays = [np.ascontiguousarray(host[k], dtype=_F64)
-                      for k in ("t", "phi_phi", "phi_r", "f_phi", "f_r")]
-            arrays += [amps, np.ascontiguousarray(host["m"], dtype=_I32),
-                       np.ascontiguousarray(host["n"], dtype=_I32),
-                       np.ascontiguousarray(host["ylm_p"], dtype=np.complex128),
-                       np.ascontiguousarray(host["ylm_m"], dtype=np.complex128)]
-            if any(a.size != nt for a in arrays[:5]):
-                raise ValueError("trajectory arrays and amplitudes must share N_t")
-            if any(a.size != K for a in arrays[6:]):
-                raise ValueError("m, n, ylm_p, ylm_m must have K entries")
-            keep.append(arrays)
-            src[i] = [a.ctypes.data for a in arrays]
-            shape[i] = (nt, K)
-        return src, shape, scale, keep
+        return [(G.engines[i], {"freq": freq, "k0": k0, "grid_symmetric": sym,
+                                "_args": G.arg_views[i]}) for i in range(n)]
 
     def sum_loglike(self, gi, d, w, out, stream, tile_const=None):
         """efd_modesum_sum_loglike(_ex) over group gi's last flush (its argument and workspace
         arrays as they are, no per-walker rebuilding); d, w, out, tile_const as
         sum_batch_loglike."""
-        import ctypes
         torch = _torch()
         G = self.groups[gi]
-        n = G["n"]
-        A = G["args"]
-        nb = int(A[0].nf) - int(A[0].k0)
+        n = G.n
+        nb = int(G.args[0].nf) - int(G.args[0].k0)
         _check_ll_io(torch, d, w, out, nb, n)
         dp, wp, op = torch.view_as_real(d).data_ptr(), w.data_ptr(), out.data_ptr()
-        for c0, cnt, pa_c, pw_c, pb_c in self._chunks(G, n):
+        for c0, cnt, pa_c, pw_c, pb_c in G.chunks[n]:
             if tile_const is None:
                 _lib.check(self.lib.efd_modesum_sum_loglike(pa_c, pw_c, pb_c, cnt, dp, wp,
                                                             op + 8 * c0, stream),
@@ -974,42 +916,23 @@ class BatchPreparer:
                     pa_c, pw_c, pb_c, cnt, dp, wp, tile_const.data_ptr(), op + 8 * c0, stream),
                     "efd_modesum_sum_loglike_ex", self.lib)
 
-    def _chunks(self, G, n):
-        """(first, count, args**, workspaces*, bytes*) per launch of at most EFD_BATCH_MAX of the
-        group's first n walkers (pointers into the group's arrays; made once per (group, n))."""
-        import ctypes
-        key = ("chunks", n)
-        ch = G.get(key)
-        if ch is None:
-            ch = []
-            step = _lib.EFD_BATCH_MAX
-            pa0 = ctypes.cast(G["pa"], ctypes.c_void_p).value
-            pw0, pb0 = ctypes.addressof(G["pw"]), ctypes.addressof(G["pb"])
-            for c0 in range(0, n, step):
-                ch.append((c0, min(step, n - c0),
-                           ctypes.cast(pa0 + 8 * c0, type(G["pa"])),
-                           ctypes.cast(pw0 + 8 * c0, ctypes.POINTER(ctypes.c_void_p)),
-                           ctypes.cast(pb0 + 8 * c0, ctypes.POINTER(ctypes.c_size_t))))
-            G[key] = ch
-        return ch
-
     def release(self, gi, event):
         """The group's workspaces and inputs are free again once `event` (recorded after the sum
         that reads them) has completed."""
-        self.groups[gi]["busy"] = event
+        self.groups[gi].busy = event
 
     def wait(self):
         """Synchronise every group and raise if any workspace reported a device-side error."""
         import ctypes
         for G in self.groups:
-            wss = [eng._ws.data_ptr() for eng in G["engines"] if eng._ws is not None]
-            if not G["used"] or not wss:
+            wss = [eng._ws.data_ptr() for eng in G.engines if eng._ws is not None]
+            if not G.used or not wss:
                 continue
             for c0 in range(0, len(wss), _lib.EFD_BATCH_MAX):
                 part = wss[c0:c0 + _lib.EFD_BATCH_MAX]
                 pw = (ctypes.c_void_p * len(part))(*part)
                 if self.lib.efd_modesum_status_batch(pw, len(part), None,
-                                                     G["stream"].cuda_stream) != _lib.EFD_OK:
+                                                     G.stream.cuda_stream) != _lib.EFD_OK:
                     raise _lib.EFDError(_lib.last_error(self.lib))
 
 

@@ -626,7 +626,7 @@ class GenerateEMRIWaveform:
                     if lanes_host is not None:
                         ls.wait_event(pev)
                     _lib.check(prep.lib.efd_modesum_lane_ranges(
-                        prep.groups[gi]["pw"], len(jobs), lanes[g0].data_ptr(),
+                        prep.workspace_ptrs(gi), len(jobs), lanes[g0].data_ptr(),
                         ls.cuda_stream), "efd_modesum_lane_ranges", prep.lib)
                     if lanes_host is not None:
                         _lib.check(prep.lib.efd_download(
@@ -640,7 +640,7 @@ class GenerateEMRIWaveform:
                 ev.record(gs)
                 prep.release(gi, ev)
         finally:
-            prep._pending = []
+            prep.drop_pending()
             for gi in used:
                 cur.wait_stream(prep.stream(gi))
             if lanes_host is not None and used:

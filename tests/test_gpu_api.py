@@ -194,7 +194,7 @@ def test_fused_likelihood_many_walkers(setup):
             with pytest.raises(RuntimeError, match="injected"):
                 like.get_ll(walkers, **kw)
             assert len(seen) == 2 and seen[0] != seen[1]
-            assert all(g["stream"].query() for g in Bp.groups)
+            assert all(g.stream.query() for g in Bp.groups)
         finally:
             delattr(Bp, name)
             del like.FUSED_NATIVE_GROUP

@@ -150,7 +150,7 @@ def test_prepare_batch_argument_checks(sources):
     B.wait()
     lib = _lib.load()
     # the C ABI: a shared workspace and a grid mismatch are refused before any launch
-    eng = B.groups[0]["engines"][0]
+    eng = B.groups[0].engines[0]
     a = B.last_jobs[0][1]["_args"]
     pa = (ctypes.POINTER(_lib.ModesumArgs) * 2)(ctypes.pointer(a), ctypes.pointer(a))
     pw = (ctypes.c_void_p * 2)(eng._ws.data_ptr(), eng._ws.data_ptr())
@@ -159,7 +159,7 @@ def test_prepare_batch_argument_checks(sources):
     assert lib.efd_modesum_prepare_batch(pa, pw, pb, 2, st) == _lib.EFD_ERR_ARG
     a2 = _lib.ModesumArgs.from_buffer_copy(a)
     a2.grid_symmetric = 0
-    eng2 = B.groups[0]["engines"][1]
+    eng2 = B.groups[0].engines[1]
     pa = (ctypes.POINTER(_lib.ModesumArgs) * 2)(ctypes.pointer(a), ctypes.pointer(a2))
     pw = (ctypes.c_void_p * 2)(eng._ws.data_ptr(), eng2._ws.data_ptr())
     pb = (ctypes.c_size_t * 2)(eng._ws.numel(), eng2._ws.numel())
@@ -182,7 +182,7 @@ def test_status_batch_names_failing_waveform(sources):
         B.wait()
     B.wait()   # reported once: the flag is cleared
     lib = _lib.load()
-    wss = [eng._ws.data_ptr() for eng in B.groups[0]["engines"]]
+    wss = [eng._ws.data_ptr() for eng in B.groups[0].engines]
     flags = (ctypes.c_int32 * 3)()
     rc = lib.efd_modesum_status_batch((ctypes.c_void_p * 3)(*wss), 3, flags,
                                       B.stream(0).cuda_stream)
@@ -343,3 +343,112 @@ def test_fused_loglike_split_tiles(split_min, monkeypatch):
     assert torch.all(torch.isfinite(ref))
     assert torch.equal(got[0], ref), (got[0] - ref) / ref
     assert torch.equal(got[1], got[0]) and torch.equal(got[2], got[0])
+
+
+def _ll_data(sources, seed=3):
+    """(freq, nf, k0, d, w) of a fused likelihood on the sources' grid."""
+    freq_h = sources[0]["freq"]
+    freq = torch.as_tensor(freq_h, device="cuda")
+    nf = int(freq.numel())
+    k0 = int(np.searchsorted(freq_h, 0.0))
+    nb = nf - k0
+    rng = np.random.default_rng(seed)
+    d = torch.as_tensor(rng.standard_normal((2, nb)) + 1j * rng.standard_normal((2, nb)),
+                        device="cuda") * 1e-22
+    w = torch.as_tensor(rng.uniform(0.5, 2.0, (2, nb)) * 1e40, device="cuda")
+    return freq, nf, k0, d, w
+
+
+@pytest.mark.parametrize("use_tc", [False, True])
+def test_flush_loglike_bitwise_equals_flush_then_sum(sources, use_tc):
+    """flush_loglike (one native call per group) writes, at out_off, bitwise the logL of flush()
+    + sum_loglike() on another preparer, with and without tile constants: two rounds over both
+    groups of depth = 2 (the buffers' first growth, then the waits on a reused group), a smaller
+    and reordered batch each time. The entries before out_off stay as they were."""
+    from emri_frequencydomainwaveforms_amd.summation import loglike_tile_constants
+    freq, nf, k0, d, w = _ll_data(sources)
+    tc = loglike_tile_constants(d, w, nf, k0) if use_tc else None
+    A = BatchPreparer(group=len(sources), depth=2)
+    R = BatchPreparer(group=len(sources), depth=2)
+    seen = []
+    for rnd in range(4):
+        batch = (sources[rnd:] + sources[:rnd])[:len(sources) - rnd]
+        n = len(batch)
+        out = torch.full((3 + n,), -7.0, dtype=torch.float64, device="cuda")
+        ref = torch.empty(n, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()     # d, w, tc and out are ready for the groups' streams
+        for B in (A, R):
+            for s in batch:
+                B.submit(_host(s), freq, True, s["prefactor"], k0=k0, prepare_only=True)
+        seen.append(A.flush_loglike(d, w, out, tile_const=tc, out_off=3))
+        gi, jobs = R.flush()
+        R.sum_loglike(gi, d, w, ref, R.stream(gi).cuda_stream, tile_const=tc)
+        A.wait()
+        R.wait()
+        assert len(A.last_jobs) == n and gi == seen[-1]
+        assert torch.all(torch.isfinite(ref)) and torch.all(ref < 0)
+        assert torch.equal(out[3:], ref)
+        assert torch.equal(out[:3], torch.full((3,), -7.0, dtype=torch.float64, device="cuda"))
+    assert seen == [0, 1, 0, 1]
+
+
+def test_flush_seventeen_walkers_bitwise_equals_smaller_groups(sources):
+    """One flush() + sum_loglike() of 17 walkers (EFD_BATCH_MAX + 1: the group's launches go in
+    chunks of 16 and 1) gives bitwise the logL of the same walkers in groups of 9 and 8."""
+    assert _lib.EFD_BATCH_MAX == 16
+    freq, nf, k0, d, w = _ll_data(sources, seed=4)
+    walkers = [sources[i % len(sources)] for i in range(17)]
+    torch.cuda.synchronize()
+
+    def run(B, parts):
+        out = torch.empty(17, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        g0 = 0
+        for cnt in parts:
+            for s in walkers[g0:g0 + cnt]:
+                B.submit(_host(s), freq, True, s["prefactor"], k0=k0, prepare_only=True)
+            gi, jobs = B.flush()
+            assert len(jobs) == cnt
+            B.sum_loglike(gi, d, w, out[g0:g0 + cnt], B.stream(gi).cuda_stream)
+            g0 += cnt
+        B.wait()
+        return out
+
+    got = run(BatchPreparer(group=17, depth=1), (17,))
+    ref = run(BatchPreparer(group=9, depth=2), (9, 8))
+    assert torch.all(torch.isfinite(ref)) and torch.all(ref < 0)
+    assert torch.equal(got, ref)
+
+
+def test_flush_rejects_disagreeing_walkers_and_recovers(sources):
+    """A pending group whose second walker has another k0, or sits on another grid tensor, makes
+    flush() raise ValueError and leaves the preparer empty; the next valid group then gives
+    bitwise a fresh preparer's spectra."""
+    freq = torch.as_tensor(sources[0]["freq"], device="cuda")
+    other = freq.clone()
+    nf = int(freq.numel())
+    k0 = int(np.searchsorted(sources[0]["freq"], 0.0))
+
+    def spectra(B):
+        for s in sources[:3]:
+            B.submit(_host(s), freq, True, s["prefactor"], k0=k0, prepare_only=True)
+        gi, jobs = B.flush()
+        outs = [torch.empty(nf, dtype=torch.complex128, device="cuda") for _ in jobs]
+        with torch.cuda.stream(B.stream(gi)):
+            sum_batch([(eng, dict(kw, out=torch.view_as_real(o)))
+                       for (eng, kw), o in zip(jobs, outs)], stream=B.stream(gi).cuda_stream)
+        B.wait()
+        return outs
+
+    ref = spectra(BatchPreparer(group=3, depth=2))
+    assert all(float(o.abs().max()) > 0 for o in ref)
+    B = BatchPreparer(group=3, depth=2)
+    for f1, k1 in ((freq, k0 + 1), (other, k0)):
+        B.submit(_host(sources[0]), freq, True, 1.0, k0=k0, prepare_only=True)
+        B.submit(_host(sources[1]), f1, True, 1.0, k0=k1, prepare_only=True)
+        assert B.next_slot() == 2
+        with pytest.raises(ValueError):
+            B.flush()
+        assert B.next_slot() == 0
+        for o, r in zip(spectra(B), ref):
+            assert torch.equal(o, r)

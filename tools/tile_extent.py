@@ -14,7 +14,7 @@ for cfg in (dict(Tobs=2.0, dt=10.0, eps=1e-2, nwalkers=16, ntemps=1),
     torch.cuda.synchronize()
     B = s.like._fused["prep"]
     G = B.groups[0]
-    for eng in G["engines"][:4]:
+    for eng in G.engines[:4]:
         h = eng._ws[:64].cpu().numpy().view(np.int32)
         a = eng._last_args
         nl = (a.nf + 1) // 2
