@@ -43,6 +43,13 @@
 //
 //   K9 k_td_modesum       the TD sum over k_group's groups and k_prep's splines
 //
+// Written once here: SumDesc (one prepared waveform as the sum sees it: sum_desc fills it, both
+// sum kernels take it by value, one modesum_tile overload unpacks it); the pieces of the tile
+// list that K6 and the sum's own build share (seg_hits_tile, hit_records, list_key,
+// scatter_slot, and block_excl_scan of emrifd_layout.h), pinned together by
+// tests/test_gpu_tile_lists.py; the chunk-record header (HDR_*, hdr_pack, hdr_lo ... hdr_j4); the
+// experiment counters (-DEFD_EXP), every use one EFD_EXP_DO(...) line.
+//
 // This unit is the mode sum (FD and TD), the tile lists it reads, and their C ABI. The
 // preparation (K0-K5, efd_modesum_prepare*, efd_spline_build) is emrifd_prepare.hip; the two
 // share emrifd_layout.h (constants, record and workspace formats, the host functions that cross).
@@ -65,11 +72,6 @@ int efdhip::fail(int code, const std::string& msg) {
 namespace {
 
 constexpr int NWAVE = TILE / 64;    // waves per workgroup
-// k_modesum's packed chunk record header (one word per record, read by v_readlane): the
-// sub-branch's lane range relative to the tile (HDR_HB bits each), s, the series length J (3
-// bits) and Item::fdneg (2 bits)
-constexpr int HDR_HB = TILE_LANES < 1024 ? 10 : 11;
-constexpr int HDR_S = 2 * HDR_HB, HDR_J = 2 * HDR_HB + 1, HDR_FD = 2 * HDR_HB + 4;
 constexpr int XCD_GROUP = 1024 / TILE;  // consecutive tiles per XCD in the dispatch order
 constexpr int SEGWIN = TILE;        // segments examined per window (tile list build): 4 KB of LDS
                                     // instead of 16 at 4 x TILE, so 4 workgroups fit a CU
@@ -77,6 +79,65 @@ constexpr int PIECES = (int)sizeof(Item) / 16;  // 16-B pieces per record
 constexpr int B_PIECE = (int)offsetof(Item, b) / 16;   // first piece of b (b[0]: 4, b[1]: 4)
 constexpr int ROUNDS = 2;                        // 16-B pieces per thread per LDS stage
 constexpr int NC = (ROUNDS * TILE) / PIECES;     // records per LDS stage
+
+// ----------------------------------------------------------------------------------------
+// The tile's record list: the pieces that its two builds (k_tile_keys in the preparation phase,
+// modesum_tile's own in the sum) share, so that both write the same keys in the same order.
+// With block_excl_scan (emrifd_layout.h) for the placement of the hits' keys.
+// ----------------------------------------------------------------------------------------
+
+// a segment with lane range lh = [lo, hi) reaches into the tile [tlo, thi)
+__device__ __forceinline__ bool seg_hits_tile(int2 lh, int32_t tlo, int32_t thi) {
+    return lh.y > tlo && lh.x < thi;
+}
+
+// Records [p0, p0 + count) (lane order) of segment sg that reach into the tile [tlo, thi): from
+// the segment-tile boundaries of k_seg_tiles, or by two bisections over the records' lane ranges
+struct HitRecords {
+    int p0, count;
+};
+__device__ __forceinline__ HitRecords hit_records(
+    int sg, int64_t tile, int32_t tlo, int32_t thi, const int32_t* __restrict__ segbase,
+    const int32_t* __restrict__ stb0, const int32_t* __restrict__ stb1,
+    const int4* __restrict__ seginfo, const int4* __restrict__ ranges) {
+    const int32_t sbase = segbase[sg];
+    if (sbase != SEG_NO_STB) {
+        const int q0 = stb0[sbase + tile], q1 = stb1[sbase + tile];
+        return {q0, max(q1 - q0, 0)};
+    }
+    const int4 info = seginfo[sg];
+    const int base = info.x, n = info.y, dir = info.z, sb = info.w;
+    int lo = 0, hi = n;            // first p (lane order) with khi > tlo
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
+        if ((sb ? rg.w : rg.y) > tlo) hi = mid; else lo = mid + 1;
+    }
+    const int p0 = lo;
+    hi = n;                        // first p with klo >= thi
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
+        if ((sb ? rg.z : rg.x) >= thi) hi = mid; else lo = mid + 1;
+    }
+    return {p0, lo - p0};
+}
+
+// the key of record p (lane order) of the segment info = (first record, count, direction,
+// sub-branch): record index << 1 | sub-branch
+__device__ __forceinline__ uint32_t list_key(int4 info, int p) {
+    const int j = info.z > 0 ? p : info.y - 1 - p;
+    return ((uint32_t)(info.x + j) << 1) | (uint32_t)info.w;
+}
+
+// Where key x of a window's `take` keys goes: the bijection x -> x * P mod take (P prime,
+// take % P != 0). A segment's records cover neighbouring lanes, i.e. mostly one wave, and
+// unscattered a chunk of NC consecutive records would keep one wave busy while the others wait
+// at its barrier
+__device__ __forceinline__ int scatter_slot(int x, int take) {
+    const int P = (take % 97) ? 97 : 101;
+    return (int)(((unsigned)x * (unsigned)P) % (unsigned)take);
+}
 
 // ----------------------------------------------------------------------------------------
 // SPA arithmetic
@@ -441,6 +502,30 @@ __device__ __forceinline__ uint64_t class_mask(double x, int32_t cls) {
 __device__ __forceinline__ double ftz_select(bool ok, double v) {
     return __hiloint2double(ok ? __double2hiint(v) : 0, __double2loint(v));
 }
+// k_modesum's packed chunk record header: one word per record, built by one lane per record
+// once per chunk and read by v_readlane (a VALU instruction, as costly as an FMA) instead of an
+// LDS round trip and 5 address / readfirstlane operations per record. Fields, low bits first:
+// the sub-branch's lane range clamped to the tile, relative to its first lane (lo, hi: HDR_HB
+// bits each), the sub-branch s (1 bit), the series length Item::jser (3 bits) and Item::fdneg
+// (2 bits: F' < 0, certified safe)
+constexpr int HDR_HB = TILE_LANES < 1024 ? 10 : 11;   // bits of a tile-relative bound
+constexpr uint32_t HDR_HM = (1u << HDR_HB) - 1u;
+constexpr int HDR_S = 2 * HDR_HB, HDR_J = 2 * HDR_HB + 1, HDR_FD = 2 * HDR_HB + 4;
+static_assert(FAST_J < 8, "header: jser in 3 bits");
+static_assert(TILE_LANES < 2048 && HDR_FD + 2 <= 32, "header: one 32-bit word");
+__device__ __forceinline__ uint32_t hdr_pack(uint32_t lo, uint32_t hi, int s, int32_t jser,
+                                             int32_t fdneg) {
+    return lo | (hi << HDR_HB) | ((uint32_t)s << HDR_S) | ((uint32_t)jser << HDR_J) |
+           ((uint32_t)fdneg << HDR_FD);
+}
+__device__ __forceinline__ int32_t hdr_lo(uint32_t ha) { return (int32_t)(ha & HDR_HM); }
+__device__ __forceinline__ int32_t hdr_hi(uint32_t ha) {
+    return (int32_t)((ha >> HDR_HB) & HDR_HM);
+}
+__device__ __forceinline__ int hdr_s(uint32_t ha) { return (int)((ha >> HDR_S) & 1u); }
+__device__ __forceinline__ uint32_t hdr_jser(uint32_t ha) { return (ha >> HDR_J) & 7u; }
+__device__ __forceinline__ uint32_t hdr_fdneg(uint32_t ha) { return (ha >> HDR_FD) & 3u; }
+__device__ __forceinline__ uint32_t hdr_safe(uint32_t ha) { return (ha >> (HDR_FD + 1)) & 1u; }
 // A wave-uniform test of the record header, re-derived in SALU at each use: the empty asm
 // makes the header word "new" to the compiler, so the test is an s_and + s_cmp on the SGPR
 // instead of a boolean kept alive across the bins' blocks, which the compiler turned into a
@@ -451,11 +536,11 @@ __device__ __forceinline__ bool hdr_test(uint32_t ha, uint32_t mask) {
 }
 __device__ __forceinline__ bool hdr_j3(uint32_t ha) {   // the record's series length J >= 3
     asm volatile("" : "+s"(ha));
-    return ((ha >> HDR_J) & 7u) >= 3u;
+    return hdr_jser(ha) >= 3u;
 }
 __device__ __forceinline__ bool hdr_j4(uint32_t ha) {   // J >= 4
     asm volatile("" : "+s"(ha));
-    return ((ha >> HDR_J) & 7u) >= 4u;
+    return hdr_jser(ha) >= 4u;
 }
 // The common record class on its own straight-line body: certified safe, series length J <= 2
 // and covering the wave's whole 64 BPL-lane chunk (every lane evaluates, every lane passes the
@@ -626,6 +711,65 @@ __device__ unsigned long long g_exp_count[EXP_NCOUNT];  // [8..15]: |y| bands of
 // coverage, J >= 3, not certified; a record may count in several)
 __device__ unsigned int g_exp_tile[16384];       // record evaluations per tile (first 16384)
 __device__ unsigned long long g_exp_tclk[16384];  // wall clock (s_memrealtime) per tile
+// EFD_EXP_DO(statements): the statements in an experiment build, nothing in the product
+#define EFD_EXP_DO(...) __VA_ARGS__
+__device__ __forceinline__ void exp_add(int i, unsigned long long n = 1ull) {
+    atomicAdd(&g_exp_count[i], n);
+}
+// spa_general: t(g) overshot the record's interval [4], by how much [18..23]
+__device__ __forceinline__ void exp_overshoot(double wl, double dtj) {
+    exp_add(4);
+    const double ov = fmax(-wl, wl - dtj) / dtj;
+    exp_add(ov < 1e-12 ? 18 : ov < 1e-9 ? 19 : ov < 1e-6 ? 20 : ov < 1e-3 ? 21
+            : ov < 1e-1 ? 22 : 23);
+}
+// spa_general: |y| < FAST_Y [5, 6] and its band [8..15]
+__device__ __forceinline__ void exp_small_y(double ww) {
+    exp_add(fabs(ww) * 18.4 <= 1.0 ? 5 : 6);
+    const double ay = 1.0 / fabs(ww);
+    exp_add(ay >= 153.0 ? 8 : ay >= 75.0 ? 9 : ay >= 48.0 ? 10 : ay >= 29.4 ? 11
+            : ay >= 23.1 ? 12 : ay >= 20.3 ? 13 : ay >= 18.4 ? 14 : 15);
+}
+// the last chunk's barrier balance [24..26] from the waves' evaluation counts wv[NWAVE]
+__device__ __forceinline__ void exp_chunk_balance(const int* wv) {
+    int mx = 0, sm = 0;
+    for (int w = 0; w < NWAVE; ++w) { mx = max(mx, wv[w]); sm += wv[w]; }
+    exp_add(24, (unsigned long long)mx);
+    exp_add(25, (unsigned long long)sm);
+    exp_add(26);
+}
+// a wave evaluates a record [0] of `tile`
+__device__ __forceinline__ void exp_record(int64_t tile) {
+    exp_add(0);
+    if (tile < 16384) atomicAdd(&g_exp_tile[tile], 1u);
+}
+// the evaluated record's class from its header: [32..35], [29], [37..39] (partial: the record
+// covers the wave's bins only partly)
+__device__ __forceinline__ void exp_record_class(uint32_t ha, bool partial) {
+    exp_add(31 + min((int)hdr_jser(ha), 4));
+    if (hdr_safe(ha)) exp_add(29);
+    if (partial) exp_add(37);
+    if (hdr_jser(ha) >= 3u) exp_add(38);
+    if (!hdr_safe(ha)) exp_add(39);
+}
+// the cold block runs for a wave [16] with this many lanes [17]
+template <int NB>
+__device__ __forceinline__ void exp_cold(const bool (&need)[NB], int lane) {
+    unsigned long long nl = 0;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) nl += __popcll(__ballot(need[i]));
+    if (lane == 0) {
+        exp_add(16);
+        exp_add(17, nl);
+    }
+}
+__device__ __forceinline__ void exp_tile_clock(int64_t tile, unsigned long long t_start) {
+    if (tile < 16384)
+        g_exp_tclk[tile] = ((t_start & 0xffffffffull) << 32) |
+                           ((wall_clock64() - t_start) & 0xffffffffull);
+}
+#else
+#define EFD_EXP_DO(...)
 #endif
 
 // General (cold) path: scipy interval selection for t(g) and the full K_{1/3} evaluation.
@@ -654,15 +798,7 @@ __device__ __noinline__ ColdEval spa_general(const Item* __restrict__ it, double
         fd = fma(fma(it->fd[0], w, it->fd[1]), w, it->fd[2]);
         fdd = INV_FDD_SCALE * fma(fma(it->fdd[0], w, it->fdd[1]), w, it->fdd[2]);
     } else {  // t(g) overshot the record's knot interval: evaluate like scipy
-#ifdef EFD_EXP
-        atomicAdd(&g_exp_count[4], 1ull);
-        {
-            const double ov = fmax(-wl, wl - it->dtj) / it->dtj;
-            const int band = ov < 1e-12 ? 18 : ov < 1e-9 ? 19 : ov < 1e-6 ? 20 : ov < 1e-3 ? 21
-                           : ov < 1e-1 ? 22 : 23;
-            atomicAdd(&g_exp_count[band], 1ull);
-        }
-#endif
+        EFD_EXP_DO(exp_overshoot(wl, it->dtj);)
         const FwdEval fe = forward_generic(tt, t, nt, jrec, h, K, gm[h], gn[h], coefA, coefT);
         for (int q = 0; q < 4; ++q) c.b[q] = fe.b[s ? q ^ 2 : q];
         ph = fe.ph; fd = fe.fd; fdd = fe.fdd;
@@ -677,15 +813,7 @@ __device__ __noinline__ ColdEval spa_general(const Item* __restrict__ it, double
         if (fabs(ww) * FAST_Y <= 1.0) {
             kseries_fast(ww, R, I);
         } else {
-#ifdef EFD_EXP
-            atomicAdd(&g_exp_count[fabs(ww) * 18.4 <= 1.0 ? 5 : 6], 1ull);
-            {
-                const double ay = 1.0 / fabs(ww);
-                const int band = ay >= 153.0 ? 8 : ay >= 75.0 ? 9 : ay >= 48.0 ? 10 : ay >= 29.4 ? 11
-                               : ay >= 23.1 ? 12 : ay >= 20.3 ? 13 : ay >= 18.4 ? 14 : 15;
-                atomicAdd(&g_exp_count[band], 1ull);
-            }
-#endif
+            EFD_EXP_DO(exp_small_y(ww);)
             kfactor_slow(fd, fdd, R, I);
         }
     }
@@ -760,9 +888,7 @@ struct TileLds {
     int hits[SEGWIN], hp0[SEGWIN], hcnt[SEGWIN], hoff[SEGWIN];
     int wcnt[(SEGWIN / TILE) * NWAVE];
     double2 sctab[SCTAB];   // (sin, cos)(k pi/128) for sincos_tab
-#ifdef EFD_EXP
-    int wimb[2][NWAVE];     // records each wave evaluated in a chunk (barrier balance)
-#endif
+    EFD_EXP_DO(int wimb[2][NWAVE];)   // records each wave evaluated in a chunk (barrier balance)
 };
 __device__ __forceinline__ TileLds& tile_lds() {
     __shared__ TileLds lds;
@@ -827,9 +953,7 @@ __device__ __forceinline__ void modesum_tile(
     int* const hoff = L_.hoff;
     int* const wcnt = L_.wcnt;
     double2* const sctab = L_.sctab;
-#ifdef EFD_EXP
-    int (*const wimb)[NWAVE] = L_.wimb;
-#endif
+    EFD_EXP_DO(int (*const wimb)[NWAVE] = L_.wimb;)
     if (NB == BPL) ioff = 0;
     // Tile order. Blocks are dealt round-robin over the 8 XCDs; XCD x = b % 8 here gets groups
     // of XCD_GROUP consecutive tiles (neighbouring tiles share interval records, which then hit
@@ -860,9 +984,7 @@ __device__ __forceinline__ void modesum_tile(
         tile = ngrid - 1 - lin;
         if (tile >= ntiles) return;
     }
-#ifdef EFD_EXP
-    const unsigned long long t_start = wall_clock64();
-#endif
+    EFD_EXP_DO(const unsigned long long t_start = wall_clock64();)
     // MODE.FP_DENORM[3:2] (FP64/FP16) = 0: flush denormal inputs and outputs (ftz_select). The
     // mode is per wave and set from the kernel descriptor at every wave launch.
     __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 0);   // hwreg(HW_REG_MODE, 6, 2)
@@ -986,10 +1108,7 @@ __device__ __forceinline__ void modesum_tile(
                 for (int row = 0; row < ROWS; ++row) {
                     const int sgi = win + row * TILE + tid;
                     bool hit = false;
-                    if (sgi < nseg) {
-                        const int2 lh = seglh[sgi];
-                        hit = lh.y > tlo && lh.x < thi;
-                    }
+                    if (sgi < nseg) hit = seg_hits_tile(seglh[sgi], tlo, thi);
                     bal[row] = __ballot(hit);
                     if (lane == 0) wcnt[row * NWAVE + wave] = __popcll(bal[row]);
                 }
@@ -1016,76 +1135,35 @@ __device__ __forceinline__ void modesum_tile(
                 // (2) each hit segment's records reaching into the tile: [p0, p1) from the
                 // segment-tile boundaries of k_seg_tiles, or by bisection
                 for (int i = tid; i < nhit; i += TILE) {
-                    const int32_t sbase = segbase[hits[i]];
-                    if (sbase != SEG_NO_STB) {
-                        const int q0 = stb0[sbase + tile], q1 = stb1[sbase + tile];
-                        hp0[i] = q0;
-                        hcnt[i] = max(q1 - q0, 0);
-                        continue;
-                    }
-                    const int4 info = seginfo[hits[i]];
-                    const int base = info.x, n = info.y, dir = info.z, sb = info.w;
-                    int lo = 0, hi = n;            // first p (lane order) with khi > tlo
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
-                        if ((sb ? rg.w : rg.y) > tlo) hi = mid; else lo = mid + 1;
-                    }
-                    const int p0 = lo;
-                    hi = n;                        // first p with klo >= thi
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
-                        if ((sb ? rg.z : rg.x) >= thi) hi = mid; else lo = mid + 1;
-                    }
-                    hp0[i] = p0;
-                    hcnt[i] = lo - p0;
+                    const HitRecords hr = hit_records(hits[i], tile, tlo, thi, segbase, stb0,
+                                                      stb1, seginfo, ranges);
+                    hp0[i] = hr.p0;
+                    hcnt[i] = hr.count;
                 }
                 __syncthreads();
                 // (3) exclusive scan of the counts (serial per thread over a block of hits,
-                // then a wave scan and one barrier for the wave totals)
+                // then the block scan of the threads' sums)
                 const int hper = (nhit + TILE - 1) / TILE;
                 const int h0 = min(nhit, tid * hper), h1 = min(nhit, h0 + hper);
                 int mine = 0;
                 for (int i = h0; i < h1; ++i) mine += hcnt[i];
-                int incl = mine;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(incl, o, 64);
-                    if (lane >= o) incl += v;
-                }
-                if (lane == 63) part[wave] = incl;
-                __syncthreads();
-                int woff = 0, wsum = 0;
-#pragma unroll
-                for (int w = 0; w < NWAVE; ++w) {
-                    woff += w < wave ? part[w] : 0;
-                    wsum += part[w];
-                }
-                int run_off = woff + incl - mine;
+                int run_off = block_excl_scan<NWAVE>(mine, part, lane, wave, wtotal);
                 for (int i = h0; i < h1; ++i) { hoff[i] = run_off; run_off += hcnt[i]; }
-                wtotal = wsum;
                 wdone = 0;
                 __syncthreads();
                 continue;
             }
-            // write keys [wdone, wdone + take) of this window at keys[nkeys ...], scattered by
-            // the bijection x -> x * P mod take (P prime, take % P != 0): a segment's records
-            // cover neighbouring lanes, i.e. mostly one wave, and unscattered a chunk of NC
-            // consecutive records would keep one wave busy while the others wait at its barrier
+            // write keys [wdone, wdone + take) of this window at keys[nkeys ...], scattered
+            // (scatter_slot) over the take
             const int take = min(KEYCAP - nkeys, wtotal - wdone);
-            const int P = (take % 97) ? 97 : 101;
             for (int i = tid; i < nhit; i += TILE) {
                 const int o = hoff[i], c = hcnt[i];
                 const int lo = max(o, wdone), hi = min(o + c, wdone + take);
                 if (lo >= hi) continue;
                 const int4 info = seginfo[hits[i]];
-                for (int g = lo; g < hi; ++g) {
-                    const int p = hp0[i] + (g - o);
-                    const int j = info.z > 0 ? p : info.y - 1 - p;
-                    keys[nkeys + (int)(((unsigned)(g - wdone) * (unsigned)P) % (unsigned)take)] =
-                        ((uint32_t)(info.x + j) << 1) | (uint32_t)info.w;
-                }
+                for (int g = lo; g < hi; ++g)
+                    keys[nkeys + scatter_slot(g - wdone, take)] =
+                        list_key(info, hp0[i] + (g - o));
             }
             nkeys += take;
             wdone += take;
@@ -1111,16 +1189,8 @@ __device__ __forceinline__ void modesum_tile(
             if (c + 1 < nchunk) EFD_GLDS(c + 1, (c + 1) & 1);
             const int nin = (int)rfl((uint32_t)min(NC, cnt - c * NC));   // loop bound in an SGPR
             const Item* stg = stage[c & 1];
-            // the chunk's record headers, one lane per record, read from LDS once per chunk and
-            // packed into one word: the sub-branch's lane range clamped to the tile, relative
-            // to its first lane (HB bits each), s and the series length: hdr = lo | hi << HB |
-            // s << 2 HB | jser << (2 HB + 1) | fdneg << (2 HB + 4). Each record then takes one v_readlane (a VALU instruction,
-            // as costly as an FMA) instead of an LDS round trip and 5 address / readfirstlane
-            // operations (round 1), or two readlanes of absolute bounds (round 2 first form).
-            static_assert(FAST_J < 8, "header: jser in 3 bits");
-            constexpr int HB = TILE_LANES < 1024 ? 10 : 11;   // bits of a tile-relative bound
-            constexpr uint32_t HM = (1u << HB) - 1u;
-            static_assert(TILE_LANES < 2048 && 2 * HB + 6 <= 32, "header: one 32-bit word");
+            // the chunk's record headers (hdr_pack), one lane per record, read from LDS once per
+            // chunk; each record then takes one v_readlane
             uint32_t hdr = 0;
             if (lane < nin) {
                 const uint32_t kl = keys[c * NC + lane];
@@ -1128,49 +1198,26 @@ __device__ __forceinline__ void modesum_tile(
                 const Item* il = stg + lane;
                 const uint32_t lo = (uint32_t)min(max(il->klo[sl] - tlo, 0), TILE_LANES);
                 const uint32_t hi = (uint32_t)min(max(il->khi[sl] - tlo, 0), TILE_LANES);
-                hdr = lo | (hi << HB) | ((uint32_t)sl << (2 * HB)) |
-                      ((uint32_t)il->jser << (2 * HB + 1)) | ((uint32_t)il->fdneg << (2 * HB + 4));
+                hdr = hdr_pack(lo, hi, sl, il->jser, il->fdneg);
             }
-#ifdef EFD_EXP
-            int nev = 0;
-            if (c > 0 && tid == 0) {
-                int mx = 0, sm = 0;
-                for (int w = 0; w < NWAVE; ++w) { mx = max(mx, wimb[(c - 1) & 1][w]); sm += wimb[(c - 1) & 1][w]; }
-                atomicAdd(&g_exp_count[24], (unsigned long long)mx);
-                atomicAdd(&g_exp_count[25], (unsigned long long)sm);
-                atomicAdd(&g_exp_count[26], 1ull);
-            }
-#endif
+            EFD_EXP_DO(int nev = 0; if (c > 0 && tid == 0) exp_chunk_balance(wimb[(c - 1) & 1]);)
             for (int ii = 0; ii < nin; ++ii) {
                 const uint32_t ha = (uint32_t)__builtin_amdgcn_readlane((int)hdr, ii);
-                const int s = (int)((ha >> (2 * HB)) & 1u);
-                const int32_t klo = tlo + (int32_t)(ha & HM);
-                const int32_t khi = tlo + (int32_t)((ha >> HB) & HM);
+                const int s = hdr_s(ha);
+                const int32_t klo = tlo + hdr_lo(ha);
+                const int32_t khi = tlo + hdr_hi(ha);
                 const Item* it = stg + ii;
                 if (khi <= e_lo || klo >= e_hi) {              // misses this wave's bins
-#ifdef EFD_EXP
-                    if (lane == 0) atomicAdd(&g_exp_count[3], 1ull);
-#endif
+                    EFD_EXP_DO(if (lane == 0) exp_add(3);)
                     continue;
                 }
-#ifdef EFD_EXP
-                ++nev;
-                if (lane == 0) {
-                    atomicAdd(&g_exp_count[0], 1ull);
-                    if (tile < 16384) atomicAdd(&g_exp_tile[tile], 1u);
-                }
-#endif
+                EFD_EXP_DO(++nev; if (lane == 0) exp_record(tile);)
                 bool anyneed = false;
                 bool need[NB];
                 {
                     // one body: sub-branch sign (the register state above) and series length as
                     // wave-uniform values
-#ifdef EFD_EXP   // records by series length [32..35], sub-branch flips [36]
-                    if (lane == 0) {
-                        atomicAdd(&g_exp_count[31 + min((int)((ha >> (2 * HB + 1)) & 7u), 4)], 1ull);
-                        if (s != s_cur) atomicAdd(&g_exp_count[36], 1ull);
-                    }
-#endif
+                    EFD_EXP_DO(if (lane == 0 && s != s_cur) exp_add(36);)   // sub-branch flips
                     if (s != s_cur) {
 #pragma unroll
                         for (int i = 0; i < NB; ++i) {
@@ -1181,23 +1228,14 @@ __device__ __forceinline__ void modesum_tile(
                         }
                         s_cur = s;
                     }
-                    const int J = CAUSTIC == EFD_CAUSTIC_UNIFORM ? (int)((ha >> (2 * HB + 1)) & 7u) : FAST_J;
+                    const int J = CAUSTIC == EFD_CAUSTIC_UNIFORM ? (int)hdr_jser(ha) : FAST_J;
                     // the stage holds b[s] at b[0] (EFD_GLDS swaps the halves for s = 1)
                     const double* xo = &it->b[0][0][0];
                     const double* xm = &it->b[1][0][0];
                     double wr[NB], wi[NB], w[NB];
                     uint64_t needm[NB], needany = 0;
-                    const RecSign rs = rec_sign((ha >> (2 * HB + 4)) & 3u);
-#ifdef EFD_EXP   // [29]: wave-records of certified-safe records
-                    if (lane == 0 && rs.safe) atomicAdd(&g_exp_count[29], 1ull);
-#endif
-#ifdef EFD_EXP   // [37]: partial coverage of the wave's bins, [38]: J >= 3, [39]: not certified
-                    if (lane == 0) {
-                        if ((e_lo - klo) < 0 || (khi - e_hi) < 0) atomicAdd(&g_exp_count[37], 1ull);
-                        if (((ha >> HDR_J) & 7u) >= 3u) atomicAdd(&g_exp_count[38], 1ull);
-                        if (!((ha >> (HDR_FD + 1)) & 1u)) atomicAdd(&g_exp_count[39], 1ull);
-                    }
-#endif
+                    const RecSign rs = rec_sign(hdr_fdneg(ha));
+                    EFD_EXP_DO(if (lane == 0) exp_record_class(ha, e_lo < klo || khi < e_hi);)
                     // envelope records (series length field 0): the straight envelope body when
                     // the record covers the wave's whole chunk, else the same with a lane mask
                     if (CAUSTIC == EFD_CAUSTIC_UNIFORM && !hdr_test(ha, 7u << HDR_J)) {
@@ -1220,8 +1258,8 @@ __device__ __forceinline__ void modesum_tile(
                     // amplitude cubics and accumulation below are shared
                     if (CAUSTIC == EFD_CAUSTIC_UNIFORM &&
                         !hdr_test(((uint32_t)((e_lo - klo) | (khi - e_hi)) >> 31) |
-                                  ((((ha >> HDR_J) & 7u) + 5u) >> 3) |
-                                  (((ha >> (HDR_FD + 1)) & 1u) ^ 1u), 1u)) {
+                                  ((hdr_jser(ha) + 5u) >> 3) |
+                                  (hdr_safe(ha) ^ 1u), 1u)) {
 #pragma unroll
                         for (int i = 0; i < NB; ++i) {
                             spa_simple(it, fk[i], tfk[i], sctab, rs, wr[i], wi[i], w[i]);
@@ -1230,8 +1268,8 @@ __device__ __forceinline__ void modesum_tile(
                     } else
                     if (CAUSTIC == EFD_CAUSTIC_UNIFORM &&
                         !hdr_test(((uint32_t)((e_lo - klo) | (khi - e_hi)) >> 31) |
-                                  (((((ha >> HDR_J) & 7u) ^ 3u) + 7u) >> 3) |
-                                  (((ha >> (HDR_FD + 1)) & 1u) ^ 1u), 1u)) {
+                                  (((hdr_jser(ha) ^ 3u) + 7u) >> 3) |
+                                  (hdr_safe(ha) ^ 1u), 1u)) {
 #pragma unroll
                         for (int i = 0; i < NB; ++i) {
                             spa_simple3(it, fk[i], tfk[i], sctab, rs, wr[i], wi[i], w[i]);
@@ -1270,17 +1308,7 @@ __device__ __forceinline__ void modesum_tile(
                         }
                     }
                     if (__builtin_expect(anyneed, 0)) {   // cold: general path, some lanes
-#ifdef EFD_EXP
-                        {
-                            unsigned long long nl_ = 0;
-#pragma unroll
-                            for (int i = 0; i < NB; ++i) nl_ += __popcll(__ballot(need[i]));
-                            if (lane == 0) {
-                                atomicAdd(&g_exp_count[16], 1ull);
-                                atomicAdd(&g_exp_count[17], nl_);
-                            }
-                        }
-#endif
+                        EFD_EXP_DO(exp_cold(need, lane);)
                         const uint32_t key = rfl(keys[c * NC + ii]);
                         const int hg = (int)((key >> 1) / (uint32_t)ni);
                         const int jr = (int)((key >> 1) - (uint32_t)hg * (uint32_t)ni);
@@ -1315,9 +1343,7 @@ __device__ __forceinline__ void modesum_tile(
                     }
                 }
             }
-#ifdef EFD_EXP
-            if (lane == 0) wimb[c & 1][wave] = nev;
-#endif
+            EFD_EXP_DO(if (lane == 0) wimb[c & 1][wave] = nev;)
             // retire this wave's LDS-DMA pieces, then the barrier publishes chunk c+1's stage
             __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
@@ -1388,10 +1414,7 @@ __device__ __forceinline__ void modesum_tile(
         tile_epilogue<PAIRED>(own_r, own_i, mir_r, mir_i, w_lo, tid & 63, wave, tid, nlanes, nf,
                               k0, accumulate_out, out, hp, hc, lld, llw, llpart, tile);
     }
-#ifdef EFD_EXP
-    if (threadIdx.x == 0 && tile < 16384)
-        g_exp_tclk[tile] = ((t_start & 0xffffffffull) << 32) | ((wall_clock64() - t_start) & 0xffffffffull);
-#endif
+    EFD_EXP_DO(if (threadIdx.x == 0) exp_tile_clock(tile, t_start);)
 }
 
 // The tile's epilogue (whole tile, or the last arriver of a sub-bin split): the spectrum S,
@@ -1479,42 +1502,9 @@ __device__ __forceinline__ void tile_epilogue(
     }
 }
 
-#define EFD_MODESUM_PARAMS                                                                    \
-    const Item* __restrict__ items, const int4* __restrict__ ranges,                          \
-        const int2* __restrict__ seglh, const int4* __restrict__ seginfo,                     \
-        const int32_t* __restrict__ nsegp, const double* __restrict__ freq, int64_t nf,       \
-        int64_t nlanes, int64_t ntiles, int nt, int K, const int32_t* __restrict__ gm,        \
-        const int32_t* __restrict__ gn, const double* __restrict__ t,                         \
-        const double* __restrict__ coefA, const double* __restrict__ coefT,                   \
-        const double2* __restrict__ sctab_g, const uint32_t* __restrict__ tkeys,              \
-        const int32_t* __restrict__ tcnt, const int32_t* __restrict__ tperm,                  \
-        const int32_t* __restrict__ segbase, const int32_t* __restrict__ stb0,                \
-        const int32_t* __restrict__ stb1, Header* __restrict__ hdr, int accumulate_out,       \
-        double* __restrict__ out, double* __restrict__ hp, double* __restrict__ hc, int64_t k0
-#define EFD_MODESUM_ARGS                                                                      \
-    items, ranges, seglh, seginfo, nsegp, freq, nf, nlanes, ntiles, nt, K, gm, gn, t, coefA,  \
-        coefT, sctab_g, tkeys, tcnt, tperm, segbase, stb0, stb1, hdr, accumulate_out, out, hp,  \
-        hc, k0
-
-// K8: the mode sum (one workgroup per tile; prebuilt lists when tcnt is given)
-template <bool PAIRED, int CAUSTIC, int BPL>
-__global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(EFD_WAVES_PER_EU, 8)))
-void k_modesum(EFD_MODESUM_PARAMS) {
-    modesum_tile<PAIRED, CAUSTIC>(EFD_MODESUM_ARGS, nullptr, nullptr, nullptr, nullptr,
-                                       (int64_t)blockIdx.x);
-}
-
-// K8 over a batch of prepared waveforms in one launch (efd_modesum_sum_batch): workgroup g takes
-// waveform g mod n at place g / n of that waveform's dispatch order, so the waveforms' tiles
-// interleave longest-first and one launch's ramp, tail and inter-launch gap are shared by n
-// waveforms. Each waveform keeps its own workspace and outputs; its tiles run exactly the code of
-// a single launch (bitwise the same spectrum). The per-waveform pointers travel in the kernel
-// arguments (n <= EFD_BATCH_MAX), read with wave-uniform scalar loads. Config 2 (bench.py, 2
-// rounds): 1,238 waveforms/s one sum per launch; 2 / 4 / 8 / 16 per launch 1,311 / 1,331 /
-// 1,291 / 1,288 (k_modesum 0.781 -> 0.742 ms per waveform at 4; past 4 the concurrent
-// waveforms' records outgrow the caches). Waveform-major order (each waveform's longest-first
-// order in turn) measured 1,288 / 1,290 / 1,226 / 1,187.
-struct BatchDesc {
+// One prepared waveform as the sum sees it (sum_desc fills it): the workspace's buffers and the
+// caller's arrays. k_modesum takes one by value, k_modesum_batch one per waveform (SumBatch).
+struct SumDesc {
     const Item* items;
     const int4* ranges;
     const int2* seglh;
@@ -1541,8 +1531,45 @@ struct BatchDesc {
     int64_t k0;
     int32_t nt, K;
 };
+// The tile of waveform d: the one entry of the kernels into modesum_tile. The grid-wide values
+// (nf, nlanes, ntiles, accumulate_out), the fused likelihood's data (lld, llw, llconst) and the
+// tile's place (b, direct, ioff, spart, scnt) are the kernel's; the rest is unpacked here, into
+// the restrict-qualified parameters the record loop's alias analysis works from. d comes by
+// value: through a reference k_modesum_batch's sparse instances took up to 67 more SGPR spills
+// and one a VGPR more; by value their registers, scratch and LDS are the explicit calls'.
+template <bool PAIRED, int CAUSTIC, int NB = BPL>
+__device__ __forceinline__ void modesum_tile(
+    const SumDesc d, int64_t nf, int64_t nlanes, int64_t ntiles, int accumulate_out,
+    const double* __restrict__ lld, const double* __restrict__ llw,
+    const double* __restrict__ llconst, int64_t b, bool direct = false, int ioff = 0,
+    double* __restrict__ spart = nullptr, int32_t* __restrict__ scnt = nullptr) {
+    modesum_tile<PAIRED, CAUSTIC, NB>(
+        d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles, d.nt, d.K,
+        d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt, d.tperm, d.segbase, d.stb0,
+        d.stb1, d.hdr, accumulate_out, d.out, d.hp, d.hc, d.k0, lld, llw, d.llpart, llconst, b,
+        direct, ioff, spart, scnt);
+}
+
+// K8: the mode sum (one workgroup per tile; prebuilt lists when tcnt is given)
+template <bool PAIRED, int CAUSTIC, int BPL>
+__global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(EFD_WAVES_PER_EU, 8)))
+void k_modesum(const SumDesc d, int64_t nf, int64_t nlanes, int64_t ntiles, int accumulate_out) {
+    modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, nullptr, nullptr,
+                                  nullptr, (int64_t)blockIdx.x);
+}
+
+// K8 over a batch of prepared waveforms in one launch (efd_modesum_sum_batch): workgroup g takes
+// waveform g mod n at place g / n of that waveform's dispatch order, so the waveforms' tiles
+// interleave longest-first and one launch's ramp, tail and inter-launch gap are shared by n
+// waveforms. Each waveform keeps its own workspace and outputs; its tiles run exactly the code of
+// a single launch (bitwise the same spectrum). The per-waveform pointers travel in the kernel
+// arguments (n <= EFD_BATCH_MAX), read with wave-uniform scalar loads. Config 2 (bench.py, 2
+// rounds): 1,238 waveforms/s one sum per launch; 2 / 4 / 8 / 16 per launch 1,311 / 1,331 /
+// 1,291 / 1,288 (k_modesum 0.781 -> 0.742 ms per waveform at 4; past 4 the concurrent
+// waveforms' records outgrow the caches). Waveform-major order (each waveform's longest-first
+// order in turn) measured 1,288 / 1,290 / 1,226 / 1,187.
 struct SumBatch {
-    BatchDesc d[EFD_BATCH_MAX];
+    SumDesc d[EFD_BATCH_MAX];
     int32_t n;
 };
 static_assert(sizeof(SumBatch) <= 3584, "batch descriptors must fit the kernel arguments");
@@ -1614,7 +1641,7 @@ void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t n
         w = (int)(r % (unsigned)n);
         pos = (int64_t)(r / (unsigned)n) * 8 + (g & 7u);
     }
-    const BatchDesc& d = batch.d[w];
+    const SumDesc& d = batch.d[w];
     if constexpr (SPARSE) {
         const int32_t nit = d.hdr->nitems;
         if (nit > 0) {
@@ -1628,18 +1655,12 @@ void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t n
                 const int S = e.y & 0xffff, j = e.y >> 16;
                 if (S > 1)
                     modesum_tile<PAIRED, CAUSTIC, 1>(
-                        d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles,
-                        d.nt, d.K, d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt,
-                        d.tperm, d.segbase, d.stb0, d.stb1, d.hdr, accumulate_out, d.out, d.hp,
-                        d.hc, d.k0, lld, llw, d.llpart, llconst, e.x, true, j,
+                        d, nf, nlanes, ntiles, accumulate_out, lld, llw, llconst, e.x, true, j,
                         ws_at<double>(W, L.spart) + (size_t)e.z * TILE_LANES * 4,
                         ws_at<int32_t>(W, L.scnt) + e.w);
                 else
-                    modesum_tile<PAIRED, CAUSTIC>(
-                        d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles,
-                        d.nt, d.K, d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt,
-                        d.tperm, d.segbase, d.stb0, d.stb1, d.hdr, accumulate_out, d.out, d.hp,
-                        d.hc, d.k0, lld, llw, d.llpart, llconst, e.x, true);
+                    modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw,
+                                                  llconst, e.x, true);
                 __syncthreads();   // the next tile's LDS writes after every wave's last reads
             }
             return;
@@ -1648,20 +1669,14 @@ void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t n
         if (lo < hi) {
             const int64_t t1 = min((int64_t)(hi - 1) / TILE_LANES, ntiles - 1);
             for (int64_t tile = lo / TILE_LANES + pos; tile <= t1; tile += nper) {
-                modesum_tile<PAIRED, CAUSTIC>(
-                    d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles,
-                    d.nt, d.K, d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt,
-                    d.tperm, d.segbase, d.stb0, d.stb1, d.hdr, accumulate_out, d.out, d.hp, d.hc,
-                    d.k0, lld, llw, d.llpart, llconst, tile, true);
+                modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw,
+                                              llconst, tile, true);
                 __syncthreads();   // the next tile's LDS writes after every wave's last reads
             }
         }
         return;
     }
-    modesum_tile<PAIRED, CAUSTIC>(
-        d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles, d.nt, d.K,
-        d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt, d.tperm, d.segbase, d.stb0,
-        d.stb1, d.hdr, accumulate_out, d.out, d.hp, d.hc, d.k0, lld, llw, d.llpart, llconst, pos);
+    modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw, llconst, pos);
 }
 
 // The fused likelihood's partial of a tile whose waveform has no record on it (every bin's
@@ -1799,9 +1814,8 @@ __device__ __forceinline__ void tile_keys_body(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t tlo = (int32_t)(tile * TILE_LANES), thi = tlo + TILE_LANES;
     const int nseg = *nsegp;
-#ifdef EFD_EXP   // segment table size [27], hits per tile summed [28]
-    if (tile == 0 && tid == 0) atomicAdd(&g_exp_count[27], (unsigned long long)nseg);
-#endif
+    // segment table size [27], hits per tile summed [28]
+    EFD_EXP_DO(if (tile == 0 && tid == 0) exp_add(27, (unsigned long long)nseg);)
     // (1) the segments overlapping the tile, in table order
     int nhit = 0;
     for (int base = 0; base < nseg; base += TK_ROWS * TILE) {
@@ -1810,10 +1824,7 @@ __device__ __forceinline__ void tile_keys_body(
         for (int r = 0; r < TK_ROWS; ++r) {
             const int sgi = base + r * TILE + tid;
             bool hit = false;
-            if (sgi < nseg) {
-                const int2 lh = seglh[sgi];
-                hit = lh.y > tlo && lh.x < thi;
-            }
+            if (sgi < nseg) hit = seg_hits_tile(seglh[sgi], tlo, thi);
             bal[r] = __ballot(hit);
             if (lane == 0) wcnt[r * NWAVE + wave] = __popcll(bal[r]);
         }
@@ -1831,9 +1842,7 @@ __device__ __forceinline__ void tile_keys_body(
         }
         __syncthreads();
     }
-#ifdef EFD_EXP
-    if (tid == 0) atomicAdd(&g_exp_count[28], (unsigned long long)nhit);
-#endif
+    EFD_EXP_DO(if (tid == 0) exp_add(28, (unsigned long long)nhit);)
     if (nhit > TK_HITS) {
         if (tid == 0) tcnt[tile] = -1;
         return;
@@ -1842,53 +1851,20 @@ __device__ __forceinline__ void tile_keys_body(
     int c = 0;
     if (tid < nhit) {
         const int sg = hits[tid];
-        const int32_t sbase = segbase[sg];
-        const int4 info = seginfo[sg];
-        int p0 = 0;
-        if (sbase != SEG_NO_STB) {
-            p0 = stb0[sbase + tile];
-            c = max(stb1[sbase + tile] - p0, 0);
-        } else {
-            const int base = info.x, n = info.y, dir = info.z, sb = info.w;
-            int lo = 0, hi = n;            // first p (lane order) with khi > tlo
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
-                if ((sb ? rg.w : rg.y) > tlo) hi = mid; else lo = mid + 1;
-            }
-            p0 = lo;
-            hi = n;                        // first p with klo >= thi
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                const int4 rg = ranges[base + (dir > 0 ? mid : n - 1 - mid)];
-                if ((sb ? rg.z : rg.x) >= thi) hi = mid; else lo = mid + 1;
-            }
-            c = lo - p0;
-        }
-        hp0[tid] = p0;
+        const HitRecords hr = hit_records(sg, tile, tlo, thi, segbase, stb0, stb1, seginfo, ranges);
+        c = hr.count;
+        hp0[tid] = hr.p0;
         hcnt[tid] = c;
-        hinfo[tid] = info;
+        hinfo[tid] = seginfo[sg];
     }
     // (3) exclusive scan of the counts
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int total = 0, woff = 0;
-#pragma unroll
-    for (int w = 0; w < NWAVE; ++w) {
-        woff += w < wave ? part[w] : 0;
-        total += part[w];
-    }
+    int total;
+    const int off = block_excl_scan<NWAVE>(c, part, lane, wave, total);
     if (total > KEYCAP) {
         if (tid == 0) tcnt[tile] = -1;
         return;
     }
-    if (tid < nhit) hoff[tid] = woff + incl - c;
+    if (tid < nhit) hoff[tid] = off;
     __syncthreads();
     // (4) each hit's SEGWIN window: where its keys start and how many it holds (the scatter's
     // range). Hits are in table order, so a window's hits are consecutive: the window's start
@@ -1898,8 +1874,8 @@ __device__ __forceinline__ void tile_keys_body(
         const int w = tid < nhit ? hits[tid] / SEGWIN : INT32_MAX;
         const bool first = tid < nhit && (tid == 0 || hits[tid - 1] / SEGWIN != w);
         const bool last = tid < nhit && (tid == nhit - 1 || hits[tid + 1] / SEGWIN != w);
-        int st = first ? woff + incl - c : INT32_MIN;       // this hit's offset = hoff[tid]
-        int en = last ? woff + incl : INT32_MAX;            // hoff[tid] + hcnt[tid]
+        int st = first ? off : INT32_MIN;       // this hit's offset = hoff[tid]
+        int en = last ? off + c : INT32_MAX;    // hoff[tid] + hcnt[tid]
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const int vs = __shfl_up(st, o, 64), ve = __shfl_down(en, o, 64);
@@ -1926,13 +1902,8 @@ __device__ __forceinline__ void tile_keys_body(
             const int mid = (lo + hi + 1) >> 1;
             if (hoff[mid] <= g) lo = mid; else hi = mid - 1;
         }
-        const int4 info = hinfo[lo];
-        const int p = hp0[lo] + (g - hoff[lo]);
-        const int j = info.z > 0 ? p : info.y - 1 - p;
         const int ws = hws[lo], take = hwt[lo];
-        const int P = (take % 97) ? 97 : 101;
-        out[ws + (int)(((unsigned)(g - ws) * (unsigned)P) % (unsigned)take)] =
-            ((uint32_t)(info.x + j) << 1) | (uint32_t)info.w;
+        out[ws + scatter_slot(g - ws, take)] = list_key(hinfo[lo], hp0[lo] + (g - hoff[lo]));
     }
     if (tid == 0) tcnt[tile] = total;
 }
@@ -1944,8 +1915,6 @@ __global__ __launch_bounds__(TILE) void k_tile_keys(const PrepBatch B) {
                    ws_at<int32_t>(W, L.stb0), ws_at<int32_t>(W, L.stb1), L.ntiles,
                    ws_at<uint32_t>(W, L.tkeys), ws_at<int32_t>(W, L.tcnt));
 }
-#undef EFD_MODESUM_PARAMS
-#undef EFD_MODESUM_ARGS
 
 // K7: dispatch order for the sum, most expensive tiles first (longest-processing-time list
 // scheduling). Cost = the tile's record count from k_tile_keys (tcnt; -1, a list over one
@@ -2278,13 +2247,12 @@ int efdhip::launch_tile_lists(const void* prep_batch, int64_t ntiles, bool any_l
     return EFD_OK;
 }
 
-// One prepared waveform as the sum sees it: the workspace's buffers (its Layout L) and the
-// caller's arrays. k_modesum_batch takes these per waveform; k_modesum takes the same fields as
-// its launch arguments.
-static BatchDesc sum_desc(const efd_modesum_args* a, void* workspace, const Layout& L) {
+// The sum's descriptor of one prepared waveform: the workspace's buffers (its Layout L) and the
+// caller's arrays
+static SumDesc sum_desc(const efd_modesum_args* a, void* workspace, const Layout& L) {
     char* ws = (char*)workspace;
     const int32_t lists = efdhip::list_mode(a->K, L.ntiles);
-    BatchDesc d{};
+    SumDesc d{};
     d.items = (const Item*)(ws + L.items);
     d.ranges = (const int4*)(ws + L.ranges);
     d.seglh = (const int2*)(ws + L.seglh);
@@ -2420,14 +2388,11 @@ static int modesum_impl(const efd_modesum_args* a, void* workspace, size_t works
         const int64_t gq = 8 * XCD_GROUP;
         const dim3 grid((unsigned)((L.ntiles + gq - 1) / gq * gq)), block(TILE);
         const int acc = a->accumulate ? 1 : 0;
-        const BatchDesc d = sum_desc(a, workspace, L);
+        const SumDesc d = sum_desc(a, workspace, L);
         if (a->prof_begin) HIP_TRY(hipEventRecord((hipEvent_t)a->prof_begin, st));
         for_sum_variant(paired != 0, a->caustic, [&](auto P, auto C) {
             hipLaunchKernelGGL((k_modesum<decltype(P)::value, decltype(C)::value, BPL>), grid,
-                               block, 0, st, d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq,
-                               a->nf, L.nlanes, L.ntiles, d.nt, d.K, d.gm, d.gn, d.t, d.coefA,
-                               d.coefT, d.sctab, d.tkeys, d.tcnt, d.tperm, d.segbase, d.stb0,
-                               d.stb1, d.hdr, acc, d.out, d.hp, d.hc, d.k0);
+                               block, 0, st, d, a->nf, L.nlanes, L.ntiles, acc);
         });
         HIP_TRY(hipGetLastError());
         if (a->prof_end) HIP_TRY(hipEventRecord((hipEvent_t)a->prof_end, st));

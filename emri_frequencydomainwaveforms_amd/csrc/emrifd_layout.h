@@ -1,9 +1,9 @@
 // emrifd_layout.h -- what the two units of the mode-sum chain share: emrifd_prepare.hip (K0-K5)
 // writes the workspace that emrifd.hip (K6-K9) reads. The constants, the record and header
-// formats, the workspace layouts and the batch descriptor of the preparation kernels, in an
-// anonymous namespace: each unit compiles its own copy (no relocatable device code), and a
-// table keeps a place only in the code object that reads it. Below them, the few host functions
-// that cross between the two units.
+// formats, the workspace layouts, the batch descriptor of the preparation kernels and the
+// workgroup's exclusive scan (block_excl_scan), in an anonymous namespace: each unit compiles its
+// own copy (no relocatable device code), and a table keeps a place only in the code object that
+// reads it. Below them, the few host functions that cross between the two units.
 #pragma once
 
 #include "emrifd_common.h"
@@ -219,6 +219,31 @@ static_assert(sizeof(PrepBatch) <= 3072, "kernel arguments stay well inside 4 KB
     char* const W = D.ws
 template <class T>
 __device__ __forceinline__ T* ws_at(char* ws, size_t off) { return reinterpret_cast<T*>(ws + off); }
+
+// Exclusive scan of one value per thread over a workgroup of NW waves, in thread order: a scan
+// within each wave, the wave totals through wsum[NW] (LDS) and one barrier. Returns the sum of
+// v over the threads before this one; total: over all of them. lane, wave: the caller's
+// (threadIdx.x & 63, threadIdx.x >> 6). No barrier after the reads of wsum: a caller that
+// writes wsum again adds its own.
+template <int NW>
+__device__ __forceinline__ int block_excl_scan(int v, int* wsum, int lane, int wave, int& total) {
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        before += w < wave ? wsum[w] : 0;
+        total += wsum[w];
+    }
+    return before + incl - v;
+}
 
 // Segment-tile boundaries: segment s covers tiles [t0, t1] (t0 = lo / TILE_LANES); its
 // (p0, p1) pairs for those tiles sit at stb[toff(s) .. toff(s) + t1 - t0] in compacted segment

@@ -432,18 +432,8 @@ __device__ __forceinline__ void group_body(const int32_t* __restrict__ marr,
     const int p0 = min(K, tid * per), p1 = min(K, p0 + per);
     int mine = 0;
     for (int p = p0; p < p1; ++p) mine += (p == 0 || (gkeys[p] >> 32) != (gkeys[p - 1] >> 32));
-    int incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int g = incl - mine, G = 0;
-    for (int w = 0; w < NW; ++w) {
-        if (w < wave) g += wsum[w];
-        G += wsum[w];
-    }
+    int G;
+    int g = block_excl_scan<NW>(mine, wsum, lane, wave, G);
     for (int p = p0; p < p1; ++p) {
         const unsigned long long k = gkeys[p];
         gmem[p] = (int32_t)(unsigned)(k & 0xffffffffu);
@@ -1646,7 +1636,8 @@ __device__ __forceinline__ void segment_compact_body(const int2* __restrict__ sl
     if (i < nslot) { info = slot_info[i]; lh = slot_lh[i]; }
     const bool valid = info.y > 0;
     const int ntl = valid ? (lh.y - 1) / TILE_LANES - lh.x / TILE_LANES + 1 : 0;
-    // exclusive scan of the tile counts over the block's slots (slot order)
+    // exclusive scan of the tile counts over the block's slots (slot order). Not block_excl_scan:
+    // 64-bit wave totals, and the barrier is shared with the ballot counts
     int incl = ntl;
     for (int o = 1; o < 64; o <<= 1) {
         const int v = __shfl_up(incl, o, 64);
@@ -1754,26 +1745,6 @@ __global__ __launch_bounds__(256) void k_seg_tiles(const PrepBatch B) {
 // bisection of the segments' record offsets in LDS). The same tables as the three kernels, in
 // one launch instead of three.
 constexpr int64_t SEG1_LDS_CAP = 40 * 1024;   // bytes of staged ranges (+ 33 KB static LDS)
-__device__ __forceinline__ int seg1_excl_scan(int v, int* wsum, int& total) {
-    constexpr int NW = SEG1_NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-    for (int w = 0; w < NW; ++w) {
-        const int x = wsum[w];
-        if (w < wave) before += x;
-        total += x;
-    }
-    __syncthreads();   // wsum free for the next scan
-    return before + incl - v;
-}
 __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     PREP_WALKER(B);
     constexpr int NW = SEG1_NT / 64;
@@ -1804,9 +1775,12 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
                      (int)(B.paired ? B.nl : B.nf), (int)(B.paired ? B.nl1 : B.nf), lh, info);
     const bool valid = info.y > 0;
     const int ntl = valid ? (lh.y - 1) / TILE_LANES - lh.x / TILE_LANES + 1 : 0;
+    // (a barrier after each block scan frees wsum for the next)
     int nseg, ntot;
-    const int pos = seg1_excl_scan(valid ? 1 : 0, wsum, nseg);
-    const int toff = seg1_excl_scan(ntl, wsum, ntot);
+    const int pos = block_excl_scan<NW>(valid ? 1 : 0, wsum, lane, wave, nseg);
+    __syncthreads();
+    const int toff = block_excl_scan<NW>(ntl, wsum, lane, wave, ntot);
+    __syncthreads();
     int32_t sbase = SEG_NO_STB;
     if (valid) {
         sbase = ((int64_t)toff + ntl <= L.stbcap) ? (int32_t)(toff - lh.x / TILE_LANES)
@@ -1820,7 +1794,8 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     }
     int nrec_all;
     const int nrec = (valid && sbase != SEG_NO_STB) ? info.y + 1 : 0;
-    const int roff = seg1_excl_scan(nrec, wsum, nrec_all);
+    const int roff = block_excl_scan<NW>(nrec, wsum, lane, wave, nrec_all);
+    __syncthreads();
     if (valid) s_roff[pos] = roff;
     // the lane union (k_segment_compact's, one workgroup: no atomics)
     int lo = valid ? lh.x : INT32_MAX, hi = valid ? lh.y : INT32_MIN;
@@ -1909,8 +1884,10 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     // and none of the scans below
     if (!__syncthreads_or(my_split > 0)) return;
     int n_items, n_split;
-    const int io = seg1_excl_scan(my_items, wsum, n_items);
-    const int po = seg1_excl_scan(my_split, wsum, n_split);
+    const int io = block_excl_scan<NW>(my_items, wsum, lane, wave, n_items);
+    __syncthreads();
+    const int po = block_excl_scan<NW>(my_split, wsum, lane, wave, n_split);
+    __syncthreads();
     if (n_split == 0 || n_items > SPLIT_ITEM_CAP || n_split > SPLIT_TILE_CAP)
         return;   // nothing to split, or past the plan's capacity: the plain tile loop
     int4* items = ws_at<int4>(W, L.sitem);
