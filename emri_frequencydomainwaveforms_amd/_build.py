@@ -12,7 +12,9 @@ source is compiled to an object under build/, all of them at once, and one link 
   csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode
                          sum, its preparation, the window path, the channel split and reductions)
                          -> hipcc --offload-arch=gfx950 -c each; all share csrc/emrifd_common.h,
-                         the first two also csrc/emrifd_layout.h (no relocatable device code)
+                         the first two also csrc/emrifd_layout.h (no relocatable device code);
+                         emrifd_prepare.hip includes csrc/emrifd_modes_device.inc (amplitudes and
+                         mode selection on the device)
   link                -> hipcc -shared over the eight objects, with libgomp and libmvec
 """
 

@@ -29,6 +29,7 @@ EFD_TD_SPLIT_SCRATCH = 1024   # efd_td_split_loglike's scratch doubles per row
 EFD_PAIR_MAX_ROWS = 64
 EFD_PAIR_SCRATCH = 655360   # the pair statistics' scratch doubles (1024 chunks x 64 rows x 10)
 EFD_WINDOW_MAX_ROWS = 16   # efd_window_rows' windows per call
+EFD_MODES_AMP_OVERFLOW = 1   # efd_modes_select_batch's status bit: amp capacity too small
 
 # every symbol include/emrifd.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -99,6 +100,8 @@ EXPORTED_SYMBOLS = (
     "efd_host_p_at_t",
     "efd_host_modes",
     "efd_host_set_threads",
+    "efd_modes_workspace_bytes",
+    "efd_modes_select_batch",
 )
 
 
@@ -160,6 +163,45 @@ class TdArgs(ctypes.Structure):
         ("hc", ctypes.c_void_p),
         ("prof_begin", ctypes.c_void_p),
         ("prof_end", ctypes.c_void_p),
+    ]
+
+
+class ModesTable(ctypes.Structure):
+    """Mirror of `efd_modes_table` (include/emrifd.h)."""
+
+    _fields_ = [
+        ("l", ctypes.c_void_p),
+        ("m", ctypes.c_void_p),
+        ("n", ctypes.c_void_p),
+        ("phase0", ctypes.c_void_p),
+        ("jitter", ctypes.c_void_p),
+        ("nmodes", ctypes.c_int32),
+    ]
+
+
+class ModesWalker(ctypes.Structure):
+    """Mirror of `efd_modes_walker` (include/emrifd.h)."""
+
+    _fields_ = [
+        ("p", ctypes.c_void_p),
+        ("e", ctypes.c_void_p),
+        ("nt", ctypes.c_int32),
+        ("ylm_p", ctypes.c_void_p),
+        ("ylm_m", ctypes.c_void_p),
+        ("eps", ctypes.c_double),
+        ("include_minus_m", ctypes.c_int32),
+        ("teuk", ctypes.c_void_p),
+        ("keep", ctypes.c_void_p),
+        ("nkeep", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("amp", ctypes.c_void_p),
+        ("amp_cap", ctypes.c_int64),
+        ("m_out", ctypes.c_void_p),
+        ("n_out", ctypes.c_void_p),
+        ("ylm_p_out", ctypes.c_void_p),
+        ("ylm_m_out", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -355,6 +397,12 @@ def load(path=None):
             global _host_threads
             _host_threads = hostcpu.threads()
             lib.efd_host_set_threads(_host_threads)
+    if hasattr(lib, "efd_modes_select_batch"):   # amplitudes and selection on the device
+        lib.efd_modes_workspace_bytes.restype = sz
+        lib.efd_modes_workspace_bytes.argtypes = [i32, i32]
+        lib.efd_modes_select_batch.restype = ctypes.c_int
+        lib.efd_modes_select_batch.argtypes = [ctypes.POINTER(ModesTable),
+                                               ctypes.POINTER(ModesWalker), i32, vp]
     _ = dbl
     if path is None:
         _lib = lib

@@ -13,6 +13,10 @@ BASELINE configs. NOT FEW physics: only the workload shape (modes, supports) is 
 recalled in SURVEY.md]: per trajectory point, sort |A Y|^2 over the m>=0 and partner -m
 branches, keep the modes needed to reach (1 - eps) of the power, fold -m picks onto +m, take
 the union over time.
+
+The same model and selection also run on the device for batched callers
+(csrc/emrifd_modes_device.inc: efd_modes_select_batch): `device_select`,
+`SyntheticTeukolskyAmplitude.select_batch_device` and `ModeSelector(m0mask, use_gpu=True)`.
 """
 
 import ctypes
@@ -34,6 +38,112 @@ def mode_list(lmax=LMAX, nmax=NMAX):
                 n_arr.append(n)
     return (np.asarray(l_arr, dtype=np.int32), np.asarray(m_arr, dtype=np.int32),
             np.asarray(n_arr, dtype=np.int32))
+
+
+def _f64(x):
+    """float64 view of a device tensor (complex128 as interleaved re, im)."""
+    import torch
+    return torch.view_as_real(x).reshape(-1) if x.is_complex() else x
+
+
+def device_select(table, nmodes, walkers, device, stream=None, state=None, prof=None):
+    """efd_modes_select_batch for 1..EFD_BATCH_MAX walkers on `stream` (a torch stream; default
+    the current one), then one efd_download of every walker's nkeep, status and keep and one
+    stream synchronisation (the mode sum's K is a host argument).
+
+    table: _lib.ModesTable over device arrays. walkers: dicts with p, e (float64 [nt] on the
+    device), ylm_p, ylm_m (float64 views of complex [nmodes]), eps, include_minus_m, teuk
+    (float64 view of complex [nt][nmodes], or None: the stand-in model) and want_amp. state: a
+    dict the caller keeps per stream (the pinned download buffer lives there). prof: a pair of
+    torch timing events recorded around efd_modes_select_batch's launches alone.
+
+    Returns one dict per walker: K, keep (device int32 [K]), keep_host (numpy int32 [K]), amp
+    (float64 view of complex [nt][K], or None), m, n (int32 [K]), ylm_p, ylm_m (float64 [2 K]):
+    views into the selection's output buffers, in the mode sum's input layout. An amplitude
+    buffer that turns out too small is an error (the buffers here hold the worst case)."""
+    import torch
+
+    from . import _lib
+    lib = _lib.load()
+    n = len(walkers)
+    if not 1 <= n <= _lib.EFD_BATCH_MAX:
+        raise ValueError(f"device_select takes 1..{_lib.EFD_BATCH_MAX} walkers")
+    strm = stream if stream is not None else torch.cuda.current_stream(device)
+    state = state if state is not None else {}
+    row = 2 + nmodes                      # int32 per walker: nkeep, status, keep[nmodes]
+    nts = [int(w["p"].numel()) for w in walkers]
+    wsb = [int(lib.efd_modes_workspace_bytes(nt, nmodes)) for nt in nts]
+    if not all(wsb):
+        raise _lib.EFDError("efd_modes_workspace_bytes rejected the shape")
+    al = lambda b: (b + 255) // 256 * 256   # noqa: E731
+    # one block per group: [ints | m, n | ylm_p, ylm_m | workspaces | amplitudes]
+    o_int = 0
+    o_mn = al(4 * row * n)
+    o_y = o_mn + al(8 * nmodes * n)
+    o_ws = o_y + al(32 * nmodes * n)
+    offs_ws, off = [], o_ws
+    for b in wsb:
+        offs_ws.append(off)
+        off = al(off + b)
+    offs_amp = []
+    for w, nt in zip(walkers, nts):
+        offs_amp.append(off)
+        if w.get("want_amp", True):
+            off = al(off + 16 * nt * nmodes)
+    with torch.cuda.stream(strm):
+        blk = torch.empty(off, dtype=torch.uint8, device=device)
+    base = blk.data_ptr()
+    ints = blk[o_int:o_int + 4 * row * n].view(torch.int32)
+    ws = (_lib.ModesWalker * n)()
+    for i, (w, nt) in enumerate(zip(walkers, nts)):
+        a = ws[i]
+        a.p, a.e, a.nt = w["p"].data_ptr(), w["e"].data_ptr(), nt
+        a.ylm_p, a.ylm_m = w["ylm_p"].data_ptr(), w["ylm_m"].data_ptr()
+        a.eps, a.include_minus_m = float(w["eps"]), 1 if w.get("include_minus_m", True) else 0
+        a.teuk = w["teuk"].data_ptr() if w.get("teuk") is not None else None
+        a.nkeep = base + o_int + 4 * row * i
+        a.status = a.nkeep + 4
+        a.keep = a.nkeep + 8
+        a.m_out = base + o_mn + 8 * nmodes * i
+        a.n_out = a.m_out + 4 * nmodes
+        a.ylm_p_out = base + o_y + 32 * nmodes * i
+        a.ylm_m_out = a.ylm_p_out + 16 * nmodes
+        a.workspace, a.workspace_bytes = base + offs_ws[i], wsb[i]
+        if w.get("want_amp", True):
+            a.amp, a.amp_cap = base + offs_amp[i], nt * nmodes
+    st = strm.cuda_stream
+    if prof is not None:   # (begin, end) torch events around the three launches alone
+        prof[0].record(strm)
+    _lib.check(lib.efd_modes_select_batch(ctypes.byref(table), ws, n, st),
+               "efd_modes_select_batch", lib)
+    if prof is not None:
+        prof[1].record(strm)
+    hb = state.get("ints")
+    if hb is None or hb.numel() < row * n:
+        hb = state["ints"] = torch.empty(row * _lib.EFD_BATCH_MAX, dtype=torch.int32,
+                                         pin_memory=True)
+    _lib.check(lib.efd_download(hb.data_ptr(), ints.data_ptr(), 4 * row * n, st), "efd_download",
+               lib)
+    strm.synchronize()
+    host = hb.numpy()[:row * n].reshape(n, row)
+    out = []
+    for i, (w, nt) in enumerate(zip(walkers, nts)):
+        K, status = int(host[i, 0]), int(host[i, 1])
+        if status & _lib.EFD_MODES_AMP_OVERFLOW:
+            raise _lib.EFDError("efd_modes_select_batch: amplitude buffer too small")
+        o = o_mn + 8 * nmodes * i
+        oy = o_y + 32 * nmodes * i
+        amp = None
+        if w.get("want_amp", True):
+            amp = blk[offs_amp[i]:offs_amp[i] + 16 * nt * K].view(torch.float64)
+        out.append(dict(
+            K=K, nt=nt, keep=ints[row * i + 2:row * i + 2 + K],
+            keep_host=host[i, 2:2 + K].copy(), amp=amp,
+            m=blk[o:o + 4 * K].view(torch.int32),
+            n=blk[o + 4 * nmodes:o + 4 * nmodes + 4 * K].view(torch.int32),
+            ylm_p=blk[oy:oy + 16 * K].view(torch.float64),
+            ylm_m=blk[oy + 16 * nmodes:oy + 16 * nmodes + 16 * K].view(torch.float64)))
+    return out
 
 
 class SyntheticTeukolskyAmplitude:
@@ -92,6 +202,60 @@ class SyntheticTeukolskyAmplitude:
         return out
 
 
+    def device_table(self, device):
+        """(_lib.ModesTable, tensors) of this model's mode list on `device`: l, m, n, phase0 and
+        jitter, uploaded once per generator and device."""
+        import torch
+
+        from . import _lib
+        cache = self.__dict__.setdefault("_dev_tables", {})
+        key = (device.type, device.index)
+        if key not in cache:
+            t = [torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                 for a in (self.l_arr, self.m_arr, self.n_arr, self._phase0, self._jitter)]
+            torch.cuda.current_stream(device).synchronize()
+            cache[key] = (_lib.ModesTable(*[x.data_ptr() for x in t], self.num_teuk_modes), t)
+        return cache[key]
+
+    def select_batch_device(self, p_list, e_list, ylms_list, eps, include_minus_m=True,
+                            device=None, stream=None, state=None, want_amp=True, prof=None):
+        """ModeSelector(eps) and the kept modes' amplitudes of several walkers on the device
+        (efd_modes_select_batch, the stand-in model evaluated in the kernels): select() without
+        the host. p_list, e_list: each walker's knots (float64 [nt], device tensors or numpy);
+        ylms_list: each walker's GetYlms output over the whole mode list (complex128 [2 K],
+        device tensor or numpy; walkers may share one object); eps: one value or one per walker.
+
+        Returns one (keep, K, views) per walker: keep the kept indices (device int32 [K]), views
+        a dict of amp, m, n, ylm_p, ylm_m (and keep_host, nt), ready to be
+        summation.DeviceInputs fields. prof: device_select's event pair."""
+        import torch
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        table, _ = self.device_table(dev)
+        n = len(p_list)
+        eps = np.broadcast_to(np.asarray(eps, dtype=np.float64), (n,))
+        K = self.num_teuk_modes
+        strm = stream if stream is not None else torch.cuda.current_stream(dev)
+
+        def dev_t(x, dt):
+            if isinstance(x, np.ndarray):
+                with torch.cuda.stream(strm):
+                    return torch.from_numpy(np.array(x, dtype=dt, order="C")).to(dev)
+            return x
+
+        ycache = {}
+        walkers = []
+        for i in range(n):
+            y = ycache.get(id(ylms_list[i]))
+            if y is None:
+                y = ycache[id(ylms_list[i])] = _f64(dev_t(ylms_list[i], np.complex128))
+            if y.numel() != 4 * K:
+                raise ValueError("ylms must hold 2 K complex values (+m, then the partners)")
+            walkers.append(dict(p=dev_t(p_list[i], np.float64), e=dev_t(e_list[i], np.float64),
+                                ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=float(eps[i]),
+                                include_minus_m=include_minus_m, teuk=None, want_amp=want_amp))
+        res = device_select(table, K, walkers, dev, strm, state, prof)
+        return [(r["keep"], r["K"], r) for r in res]
+
     def select(self, p, e, ylms, eps, lib=None):
         """(keep, teuk): ModeSelector(eps) over this model's modes and the kept modes' complex
         amplitudes [N_t][K], in one native call (csrc/emrifd_host.cpp: efd_host_modes) when the
@@ -136,9 +300,40 @@ class ModeSelector:
     def __init__(self, m0mask, use_gpu=False):
         self.m0mask = np.asarray(m0mask, dtype=bool)
         self.num_m_1_p = len(self.m0mask)
+        self.use_gpu = bool(use_gpu)
+        self._table = {}
+
+    def _device_call(self, teuk_modes, ylms, eps):
+        """The selection on the device (efd_modes_select_batch with the amplitudes given):
+        complex128 device tensors in, the kept indices out as a device int32 tensor."""
+        import torch
+
+        from . import _lib
+        dev = teuk_modes.device
+        nt, K = teuk_modes.shape
+        if K != len(self.m0mask) or ylms.numel() != 2 * K:
+            raise ValueError("teuk_modes [N_t, K] and ylms [2 K] must match m0mask")
+        key = (dev.type, dev.index)
+        if key not in self._table:
+            # the selection reads m != 0 only; l, n, phase0 and jitter belong to the stand-in
+            # model, which a call with the amplitudes given never evaluates
+            m = torch.from_numpy(self.m0mask.astype(np.int32)).to(dev)
+            zi = torch.zeros(K, dtype=torch.int32, device=dev)
+            zd = torch.zeros(K, dtype=torch.float64, device=dev)
+            self._table[key] = (_lib.ModesTable(zi.data_ptr(), m.data_ptr(), zi.data_ptr(),
+                                                zd.data_ptr(), zd.data_ptr(), K), (m, zi, zd))
+        table, (_, _, zd) = self._table[key]
+        y = _f64(ylms.to(torch.complex128).contiguous())
+        pe = torch.ones(nt, dtype=torch.float64, device=dev)   # unused with teuk given
+        w = dict(p=pe, e=pe, ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=float(eps),
+                 teuk=_f64(teuk_modes.to(torch.complex128).contiguous()), want_amp=False)
+        return device_select(table, K, [w], dev)[0]["keep"].clone()
 
     def __call__(self, teuk_modes, ylms, modeinds, eps=1e-5):
-        """teuk_modes [N_t, K]; ylms [K + K] (+m then partner); returns kept mode indices."""
+        """teuk_modes [N_t, K]; ylms [K + K] (+m then partner); returns kept mode indices (with
+        use_gpu: device tensors in, a device int32 tensor out)."""
+        if self.use_gpu:
+            return self._device_call(teuk_modes, ylms, eps)
         K = teuk_modes.shape[1]
         ylm_p, ylm_m = ylms[:K], ylms[K:]
         # m = 0 modes have no separate partner branch (their +-n mirrors are separate modes)
@@ -151,6 +346,7 @@ class ModeSelector:
         keep = np.ones(cumsum.shape, dtype=bool)
         keep[:, 1:] = cumsum[:, :-1] < cumsum[:, -1][:, None] * (1.0 - eps)
         picked = inds_sort[keep]
-        # fold partner picks back onto their +m mode
-        picked = np.where(picked < K, picked, partner_idx[np.clip(picked - K, 0, None)])
+        # fold partner picks back onto their +m mode (no m != 0 mode: no partner to fold)
+        if partner_idx.size:
+            picked = np.where(picked < K, picked, partner_idx[np.clip(picked - K, 0, None)])
         return np.unique(picked)

@@ -2098,6 +2098,8 @@ int efdhip::td_prepare(const efd_td_args* a, void* workspace, hipStream_t st) {
     return EFD_OK;
 }
 
+#include "emrifd_modes_device.inc"
+
 extern "C" {
 
 int efd_spline_build(const double* x, int n, const double* y, int ninterp, double* coef,

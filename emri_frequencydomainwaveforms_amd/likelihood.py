@@ -209,6 +209,13 @@ class Likelihood:
             for i in range(num_likes):
                 h = self._as_channels(h_all[i])
                 self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
+        elif (self.device_upstream and getattr(tm, "can_pipeline", False) and not args
+              and (host := self._get_ll_device(tm, params, kwargs, out)) is not None):
+            if self.noise_has_been_added:
+                raise NotImplementedError
+            if self.use_gpu and self.return_cupy:
+                return out
+            return host
         elif (getattr(tm, "can_pipeline", False) and self.fused_likelihood
               and (host := self._get_ll_fused(tm, params, args, kwargs, out)) is not None):
             if self.noise_has_been_added:
@@ -397,6 +404,87 @@ class Likelihood:
         host = pin[:n].numpy().copy()
         if np.isnan(host).any():
             B.wait()   # device-side errors of the groups' workspaces (sticky across reuse)
+        return host
+
+    # amplitudes and mode selection on the device (pe.setup(upstream="device")): get_ll's
+    # pipelined templates on symmetric grids take _get_ll_device; False keeps the host upstream
+    device_upstream = False
+
+    def _get_ll_device(self, tm, params, kwargs, out):
+        """The fused likelihood with the upstream's amplitudes and mode selection on the device:
+        the walkers' trajectories start on the prefetch pool at once; per balanced group of at
+        most EFD_BATCH_MAX walkers, on one of two rotating streams, the generator's
+        device_group (packed trajectory upload, efd_modes_select_batch, the read of the group's
+        K and efd_modesum_prepare_batch) and one efd_modesum_sum_loglike_ex with the tile
+        constants write the group's log-likelihoods into its slice of out; a group's device
+        chain runs beside the next group's trajectories and selection. One copy out per batch.
+        Returns the log-likelihoods on the host, or None, before queueing anything, when the
+        template is not a GenerateEMRIWaveform on a symmetric grid or the call names an
+        explicit mode list (the caller then takes the host upstream's path)."""
+        import types
+        torch = self.torch
+        from .summation import sum_batch_loglike
+        few = getattr(tm, "waveform_generator", None)
+        if (not hasattr(few, "device_group") or kwargs.get("mode_selection") is not None
+                or not self._fused_grid_ok(tm, kwargs)):
+            return None
+        cw = few.waveform_generator.create_waveform
+        T, dt, eps = kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("eps", 1e-5)
+        freq, _ = cw._grid(T, dt, kwargs.get("f_arr"))
+        k0 = cw.positive_start()
+        if getattr(tm, "_suffix_k0", k0) != k0:
+            raise ValueError("positive_frequency_mask does not match the generator's grid")
+        n = len(params)
+        if n == 0:
+            return np.empty(0, dtype=np.float64)
+        ngroups = -(-n // _lib.EFD_BATCH_MAX)
+        G = -(-n // ngroups)                       # balanced groups of at most EFD_BATCH_MAX
+        st = few._device_state(self.device, cw.caustic)
+        lib = st["engines"][0][0].lib
+        D = st.get("like")
+        if D is None:
+            gst = [s.cuda_stream for s in st["streams"]]
+            D = st["like"] = dict(prep=types.SimpleNamespace(lib=lib), gst=gst,
+                                  order=(ctypes.c_void_p * len(gst))(*gst))
+        gst = D["gst"]
+        calls, scales = few.device_calls(params, T, eps)
+        futs = few.waveform_generator.trajectories_async(calls)
+        _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
+                                        D["order"], len(gst)), "efd_stream_order", lib)
+        pin = D.get("pin")
+        if pin is None or pin.numel() < n:
+            pin = D["pin"] = torch.empty(max(n, 64), dtype=torch.float64, pin_memory=True)
+        include_minus_m = bool(kwargs.get("include_minus_m", True))
+        last = None
+        try:
+            for gidx, g0 in enumerate(range(0, n, G)):
+                slot = gidx % 2
+                jobs = few.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
+                                        futs[g0:g0 + G], freq, k0, None, include_minus_m)
+                tc = self._tile_constants(freq, k0, st["streams"][slot], D)
+                sum_batch_loglike(jobs, self._d, self._w_templ, out[g0:g0 + len(jobs)],
+                                  stream=gst[slot], tile_const=tc)
+                last = slot
+            if ngroups > 1:   # the other slot's stream joins the last one, which copies out
+                _lib.check(lib.efd_stream_order(gst[1 - last], (ctypes.c_void_p * 1)(gst[last]),
+                                                1), "efd_stream_order", lib)
+            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, gst[last]),
+                       "efd_download", lib)
+        finally:
+            for f in futs:
+                f.cancel()
+            # `out` belongs to the current stream: nothing may still write it when it is
+            # returned, or freed after an exception
+            if sys.exc_info()[0] is not None:
+                for s in st["streams"]:
+                    s.synchronize()
+            elif last is not None:
+                st["streams"][last].synchronize()
+        host = pin[:n].numpy().copy()
+        if np.isnan(host).any():
+            few._device_check()   # device-side errors of the slots' workspaces raise
+        else:
+            st["used"] = [0, 0]
         return host
 
     # tiles no harmonic reaches take a precomputed partial instead of re-reading d and w

@@ -48,7 +48,7 @@ class PESetup:
 
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
-          window=None, start_cov=None, template="fd", injectFD=None):
+          window=None, start_cov=None, template="fd", injectFD=None, upstream="host"):
     """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
     generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
     not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
@@ -69,9 +69,16 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     modules, the likelihood, its grids) out of the cyclic collector's reach (gc.freeze), as a
     sampler process would once its setup is done: a full collection otherwise walks ~200 k
     objects, 35 ms (130 ms with a dropped setup's garbage), inside whichever likelihood call
-    happens to trigger it (tools/api_trace.py, tools/gc_cycles.py)."""
+    happens to trigger it (tools/api_trace.py, tools/gc_cycles.py).
+    upstream: "host" (default) or "device": the likelihood's walkers take their amplitudes and
+    mode selection on the device (Likelihood.device_upstream; only the trajectories stay on the
+    host), where the template can pipeline on a symmetric grid. The injection is the same."""
     if template not in ("fd", "td"):
         raise ValueError("template: 'fd' or 'td'")
+    if upstream not in ("host", "device"):
+        raise ValueError("upstream: 'host' or 'device'")
+    if upstream == "device" and template != "fd":
+        raise ValueError("upstream='device' is the FD template's")
     if template == "td" and downsample:
         raise ValueError("Cannot run downsampling with time domain template")   # emri_pe.py:326
     from .fdutils import get_fd_waveform_fromFD, get_fd_waveform_fromTD, get_sensitivity
@@ -150,6 +157,9 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     info.update(template=template, injectFD=bool(inject_fd))
     like = Likelihood(gen, 2, parameter_transforms={"emri": tc}, vectorized=False,
                       transpose_params=False, subset=like_subset, f_arr=f_like, use_gpu=True)
+    if upstream == "device":
+        like.device_upstream = True
+    info["upstream"] = upstream
     data = (gen_fd if inject_fd else gen_td)(*injection, **kw)
     like.inject_signal(data_stream=data, noise_fn=[get_sensitivity, get_sensitivity],
                        noise_kwargs=[{}, {}])

@@ -12,6 +12,9 @@ Call surfaces kept from the reference (so its drivers only change the import lin
 Upstream of the hot path (trajectory, amplitudes, Ylm, mode selection) runs on the host with
 the stand-ins of trajectory.py / amplitude.py (NOT FEW physics).
 The FD summation itself runs in libemrifd.so on the GPU.
+The batched calls (generate_batch, spectrum_batch, the likelihood) can also take the amplitudes
+and the mode selection on the GPU (upstream="device": efd_modes_select_batch); the trajectory
+then is the only host part.
 `use_gpu` selects the return type (torch tensors on the GPU, or numpy copies); the compute
 always runs on the GPU -- there is no CPU fallback.
 
@@ -182,6 +185,102 @@ class FastSchwarzschildEccentricFlux:
                     m=amp.m_arr[keep], n=amp.n_arr[keep],
                     f_phi=om_phi / (2.0 * np.pi * M * MTSUN_SI),
                     f_r=om_r / (2.0 * np.pi * M * MTSUN_SI))
+
+    # -- device-side upstream: only the trajectory stays on the host ---------------------------
+    def trajectories_async(self, calls):
+        """The trajectories of `calls` (prepare() argument tuples) on the prefetch pool: one
+        Future of with_frequencies' (t, p, e, Phi_phi, Phi_r, f_phi, f_r) per call, started in
+        order. No amplitudes are made on the host."""
+        traj = self.inspiral_generator.with_frequencies
+        pool = _pool()
+        return [pool.submit(traj, c[0], c[1], 0.0, c[2], c[3], 1.0, Phi_phi0=c[7], Phi_r0=c[8],
+                            T=c[9]) for c in calls]
+
+    def _ylms_device(self, theta, phi, dev):
+        """_ylms on the device (float64 view of complex [2 K]), uploaded once per viewing angle."""
+        torch = require_gpu()
+        key = (float(theta), float(phi), dev.type, dev.index)
+        y = self._ylm_dev.get(key) if hasattr(self, "_ylm_dev") else None
+        if y is None:
+            if not hasattr(self, "_ylm_dev") or len(self._ylm_dev) > 64:
+                self._ylm_dev = {}
+            host = np.ascontiguousarray(self._ylms(theta, phi), dtype=np.complex128)
+            y = torch.from_numpy(host.view(np.float64).copy()).to(dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._ylm_dev[key] = y
+        return y
+
+    def device_inputs_batch(self, calls, include_minus_m=True, device=None, stream=None,
+                            state=None, futures=None):
+        """summation.DeviceInputs of 1..EFD_BATCH_MAX sources with the amplitudes and the mode
+        selection made on the device (efd_modes_select_batch): prepare() for batched callers,
+        with only the trajectory on the host. `calls` are prepare() argument tuples (M, mu, p0,
+        e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps).
+
+        The trajectories come from the native call on the prefetch pool (futures: those of
+        trajectories_async(calls), started earlier); t, p, e, Phi_phi, Phi_r, f_phi and f_r of
+        the whole group go up in one packed pinned copy on `stream` (a torch stream; default the
+        current one); the selection runs behind it and one efd_download of nkeep, status and
+        keep with one stream synchronisation gives the host each walker's K. The DeviceInputs'
+        fields are views into the upload and the selection's output buffers: no amplitude array
+        crosses PCIe. The mode table is uploaded once per generator, Ylm once per viewing
+        angle. state: a dict the caller keeps per stream (pinned buffers). last_modes holds the
+        last walker's (l, m, n), last_modes_batch every walker's."""
+        torch = require_gpu()
+        from .summation import DeviceInputs
+        calls = [tuple(c) for c in calls]
+        n = len(calls)
+        if not 1 <= n <= _lib.EFD_BATCH_MAX:
+            raise ValueError(f"device_inputs_batch takes 1..{_lib.EFD_BATCH_MAX} sources")
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        strm = stream if stream is not None else torch.cuda.current_stream(dev)
+        state = state if state is not None else {}
+        amp = self.amplitude_generator
+        table, _ = amp.device_table(dev)
+        ys = [self._ylms_device(c[4], c[5], dev) for c in calls]
+        futures = futures if futures is not None else self.trajectories_async(calls)
+        trajs = [f.result() for f in futures]
+        # one packed upload: walker i's seven arrays, nt doubles each, from a 256-B boundary
+        offs, off = [], 0
+        for tr in trajs:
+            offs.append(off)
+            off += (7 * len(tr[0]) + 31) // 32 * 32
+        pin = state.get("pin")
+        if pin is None or pin.numel() < off:
+            pin = state["pin"] = torch.empty(max(off, 1 << 16), dtype=torch.float64,
+                                             pin_memory=True)
+        hb = pin.numpy()
+        for tr, o in zip(trajs, offs):
+            nt = len(tr[0])
+            if nt < 2:
+                raise ValueError("trajectory with fewer than 2 knots")
+            for k, a in enumerate(tr):
+                hb[o + k * nt:o + (k + 1) * nt] = a
+        with torch.cuda.stream(strm):
+            dbuf = torch.empty(off, dtype=torch.float64, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.efd_upload(dbuf.data_ptr(), pin.data_ptr(), 8 * off, strm.cuda_stream),
+                   "efd_upload", lib)
+        K = amp.num_teuk_modes
+        walkers, fields = [], []
+        for tr, o, y, c in zip(trajs, offs, ys, calls):
+            nt = len(tr[0])
+            v = [dbuf[o + k * nt:o + (k + 1) * nt] for k in range(7)]   # t p e Pphi Pr fphi fr
+            fields.append(v)
+            walkers.append(dict(p=v[1], e=v[2], ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=c[10],
+                                include_minus_m=include_minus_m, teuk=None))
+        from .amplitude import device_select
+        res = device_select(table, K, walkers, dev, strm, state)   # (synchronises strm)
+        out, modes = [], []
+        for v, r in zip(fields, res):
+            out.append(DeviceInputs(t=v[0], phi_phi=v[3], phi_r=v[4], f_phi=v[5], f_r=v[6],
+                                    amp=r["amp"], m=r["m"], n=r["n"], ylm_p=r["ylm_p"],
+                                    ylm_m=r["ylm_m"], nt=r["nt"], K=r["K"]))
+            keep = r["keep_host"]
+            modes.append((amp.l_arr[keep], amp.m_arr[keep], amp.n_arr[keep]))
+        self.last_modes_batch = modes
+        self.last_modes = modes[-1]
+        return out
 
     def prefetch(self, calls, wait=True, concurrency=None):
         """Run the host upstream of several sources at once: `calls` are prepare() argument
@@ -370,6 +469,19 @@ def _nbytes(d):
     return sum(v.nbytes for v in d.values() if isinstance(v, np.ndarray))
 
 
+UPSTREAMS = ("host", "device")
+
+
+def _check_upstream(upstream, kwargs):
+    """The batched calls' `upstream` argument: "host" (the default route) or "device"; explicit
+    mode lists keep the host route."""
+    if upstream not in UPSTREAMS:
+        raise ValueError(f"upstream must be one of {UPSTREAMS}, got {upstream!r}")
+    if upstream == "device" and kwargs.get("mode_selection") is not None:
+        raise ValueError("upstream='device' selects the modes on the device: an explicit "
+                         "mode_selection list keeps upstream='host'")
+
+
 _WAVEFORMS = {"FastSchwarzschildEccentricFlux": FastSchwarzschildEccentricFlux}
 _POOL = None
 
@@ -495,7 +607,8 @@ class GenerateEMRIWaveform:
     # efd_modesum_prepare_batch and one efd_modesum_sum_batch each (EFD_BATCH_MAX at most)
     BATCH_GROUP = 16
 
-    def generate_batch(self, params, out, T=1.0, dt=10.0, eps=1e-5, f_arr=None, **kwargs):
+    def generate_batch(self, params, out, T=1.0, dt=10.0, eps=1e-5, f_arr=None, upstream="host",
+                       **kwargs):
         """[h+, hx] over f >= 0 of every row of params (B x 14, FEW's order) into out
         (complex128 [B][2][N_pos] on the device): the vectorised form of B calls
         `self(*row, T=T, dt=dt, eps=eps, mask_positive=True)` with return_list=True (bitwise
@@ -505,18 +618,25 @@ class GenerateEMRIWaveform:
         amplitudes, selection; this rank's host-core share), then the device work goes in
         groups of BATCH_GROUP: one packed upload and one efd_modesum_prepare_batch per group on
         that group's stream, one efd_modesum_sum_batch writing the group's h+/hx on the same
-        stream, two groups in flight. Returns out, ordered after the work on the current stream."""
+        stream, two groups in flight. Returns out, ordered after the work on the current stream.
+
+        upstream="device": only the trajectories run on the host; the amplitudes and the mode
+        selection of each group run on the device (device_inputs_batch) and feed the same
+        preparation and sum. The kept modes are the host route's; the amplitudes agree with it
+        to rounding (1e-14 max|A|), so the templates agree to the mode sum's response to that,
+        not bitwise. Not with an explicit mode_selection list."""
         torch = require_gpu()
+        _check_upstream(upstream, kwargs)
         npos = self._batch_grid(T, dt, f_arr)[1]
         B = len(np.asarray(params, dtype=np.float64).reshape(-1, 14))
         if tuple(out.shape) != (B, 2, npos) or out.dtype != torch.complex128:
             raise ValueError(f"out must be complex128 [{B}][2][{npos}]")
         return self._run_batch(params, out, lambda j: dict(hp=torch.view_as_real(out[j, 0]),
                                                            hc=torch.view_as_real(out[j, 1])),
-                               T, dt, eps, f_arr, kwargs)
+                               T, dt, eps, f_arr, kwargs, upstream=upstream)
 
     def spectrum_batch(self, params, out, T=1.0, dt=10.0, eps=1e-5, f_arr=None, lanes=None,
-                       check=True, lanes_host=None, **kwargs):
+                       check=True, lanes_host=None, upstream="host", **kwargs):
         """The two-sided spectra S = h+ - i hx of every row of params into the rows of out
         (complex128 [B][N], contiguous rows, on the device): generate_batch's device groups
         with the sum writing S (the windowed templates' input, fdutils.HannConvolution); bitwise
@@ -526,8 +646,9 @@ class GenerateEMRIWaveform:
         calls check_batch() once its own work on the spectra is queued. lanes_host (pinned int32
         [B][2], with lanes): the lane ranges are gathered right after each group's preparation
         and copied there on a side stream, beside the sum; lanes_ready() waits for those copies
-        only, so the host can read them while the sums run."""
+        only, so the host can read them while the sums run. upstream: as generate_batch."""
         torch = require_gpu()
+        _check_upstream(upstream, kwargs)
         n = self._batch_grid(T, dt, f_arr)[0]
         B = len(np.asarray(params, dtype=np.float64).reshape(-1, 14))
         if (out.dim() != 2 or tuple(out.shape) != (B, n) or out.dtype != torch.complex128
@@ -542,15 +663,16 @@ class GenerateEMRIWaveform:
             raise ValueError(f"lanes_host must be pinned int32 [{B}][2] beside lanes")
         return self._run_batch(params, out, lambda j: dict(out=torch.view_as_real(out[j])),
                                T, dt, eps, f_arr, kwargs, lanes=lanes, check=check,
-                               lanes_host=lanes_host)
+                               lanes_host=lanes_host, upstream=upstream)
 
     def lanes_ready(self):
         """Wait for the last spectrum_batch's lane-range copies into lanes_host (each group's
         event; the sums behind them keep running)."""
-        st = getattr(self, "_gen_batch", None)
-        if st is not None:
-            for ev in st.get("lanes_ev_used", ()):
-                ev.synchronize()
+        for name in ("_gen_batch", "_dev_batch"):
+            st = getattr(self, name, None)
+            if st is not None:
+                for ev in st.get("lanes_ev_used", ()):
+                    ev.synchronize()
 
     def check_batch(self):
         """Synchronise the last batch's groups and raise if a workspace reported a device-side
@@ -558,6 +680,7 @@ class GenerateEMRIWaveform:
         st = getattr(self, "_gen_batch", None)
         if st is not None:
             st["prep"].wait()
+        self._device_check()
 
     def positive_bins(self, T=1.0, dt=10.0, f_arr=None):
         """N_pos, the f >= 0 bins of the grid generate_batch writes (its out's last dimension)."""
@@ -574,8 +697,11 @@ class GenerateEMRIWaveform:
         return int(freq.numel()), int(freq.numel()) - cw._k0
 
     def _run_batch(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes=None,
-                   check=True, lanes_host=None):
+                   check=True, lanes_host=None, upstream="host"):
         torch = require_gpu()
+        if upstream == "device":
+            return self._run_batch_device(params, out, outputs, T, dt, eps, f_arr, kwargs,
+                                          lanes, check, lanes_host)
         from .summation import BatchPreparer, sum_batch
         cw = self.waveform_generator.create_waveform
         params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
@@ -647,6 +773,124 @@ class GenerateEMRIWaveform:
                 cur.wait_stream(st["lstream"])
         if check:
             prep.wait()   # device-side errors of the groups' workspaces raise here
+        return out
+
+    # -- the batched generator with the amplitudes and the selection on the device ------------
+    def _device_state(self, dev, caustic):
+        """Two rotating group slots for the device upstream: a stream, EFD_BATCH_MAX engines
+        (a workspace each) and the selection's pinned buffers per slot."""
+        torch = require_gpu()
+        st = getattr(self, "_dev_batch", None)
+        if st is None or st["device"] != dev or st["caustic"] != caustic:
+            from .summation import ModeSumEngine
+            st = self._dev_batch = dict(
+                device=dev, caustic=caustic, used=[0, 0],
+                streams=[torch.cuda.Stream(dev) for _ in range(2)],
+                engines=[[ModeSumEngine(caustic) for _ in range(_lib.EFD_BATCH_MAX)]
+                         for _ in range(2)],
+                sel=[{}, {}], lanes_ev=[torch.cuda.Event(), torch.cuda.Event()])
+        return st
+
+    def device_calls(self, params, T=1.0, eps=1e-5):
+        """(calls, scales) of the rows of params (B x 14): device_inputs_batch's argument tuples
+        and each row's complex scale (the spectrum path's rounding)."""
+        calls, scales = [], []
+        for prm in np.asarray(params, dtype=np.float64).reshape(-1, 14).tolist():
+            M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
+            theta, phi, rot = self._angles(qS, phiS, qK, phiK)
+            calls.append((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps))
+            scales.append(complex(rot * (mu * MRSUN_SI / (dist * Gpc))))
+        return calls, scales
+
+    def device_group(self, st, slot, calls, scales, futures, freq, k0, outputs=None,
+                     include_minus_m=True):
+        """One group of at most EFD_BATCH_MAX walkers on slot `slot` of _device_state's st:
+        device_inputs_batch and efd_modesum_prepare_batch on the slot's stream. Returns the
+        (engine, launch_kwargs) jobs for sum_batch / sum_batch_loglike on that stream."""
+        torch = require_gpu()
+        from .summation import prepare_batch
+        gs = st["streams"][slot]
+        inps = self.waveform_generator.device_inputs_batch(
+            calls, include_minus_m=include_minus_m, device=st["device"], stream=gs,
+            state=st["sel"][slot], futures=futures)
+        jobs = [(eng, dict(dict(inp=inp, freq=freq, out=None, grid_symmetric=True, scale=sc,
+                                k0=k0), **(outputs(i) if outputs is not None else {})))
+                for i, (eng, inp, sc) in enumerate(zip(st["engines"][slot], inps, scales))]
+        st["used"][slot] = max(st["used"][slot], len(jobs))
+        with torch.cuda.stream(gs):   # (a grown workspace is allocated on the slot's stream)
+            prepare_batch(jobs, stream=gs.cuda_stream)
+        return jobs
+
+    def _device_check(self):
+        """Synchronise the device route's slots and raise if a workspace reported a device-side
+        error."""
+        import ctypes
+        st = getattr(self, "_dev_batch", None)
+        if st is None:
+            return
+        for slot, n in enumerate(st["used"]):
+            eng = [e for e in st["engines"][slot][:n] if e._ws is not None]
+            st["used"][slot] = 0
+            if not eng:
+                continue
+            pw = (ctypes.c_void_p * len(eng))(*[e._ws.data_ptr() for e in eng])
+            lib = eng[0].lib
+            if lib.efd_modesum_status_batch(pw, len(eng), None,
+                                            st["streams"][slot].cuda_stream) != _lib.EFD_OK:
+                raise _lib.EFDError(f"efd_modesum: {_lib.last_error(lib)}")
+
+    def _run_batch_device(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes, check,
+                          lanes_host):
+        import ctypes
+        torch = require_gpu()
+        from .summation import sum_batch
+        gen = self.waveform_generator
+        cw = gen.create_waveform
+        freq, _ = cw._grid(T, dt, f_arr)
+        kc = cw._k0
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
+        B = len(params)
+        if B == 0:
+            return out
+        include_minus_m = bool(kwargs.get("include_minus_m", True))
+        st = self._device_state(out.device, cw.caustic)
+        calls, scales = self.device_calls(params, T, eps)
+        futs = gen.trajectories_async(calls)
+        G = min(self.BATCH_GROUP, _lib.EFD_BATCH_MAX)
+        cur = torch.cuda.current_stream(out.device)
+        for gs in st["streams"]:
+            gs.wait_stream(cur)
+        st["lanes_ev_used"] = []
+        used = set()
+        try:
+            for gidx, g0 in enumerate(range(0, B, G)):
+                slot = gidx % 2
+                gs = st["streams"][slot]
+                used.add(slot)
+                jobs = self.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
+                                         futs[g0:g0 + G], freq, kc,
+                                         lambda i, g0=g0: outputs(g0 + i), include_minus_m)
+                sum_batch(jobs, stream=gs.cuda_stream)
+                if lanes is not None:
+                    lib = jobs[0][0].lib
+                    pw = (ctypes.c_void_p * len(jobs))(*[e._ws.data_ptr() for e, _ in jobs])
+                    _lib.check(lib.efd_modesum_lane_ranges(pw, len(jobs), lanes[g0].data_ptr(),
+                                                           gs.cuda_stream),
+                               "efd_modesum_lane_ranges", lib)
+                    if lanes_host is not None:
+                        _lib.check(lib.efd_download(lanes_host[g0].data_ptr(),
+                                                    lanes[g0].data_ptr(), 8 * len(jobs),
+                                                    gs.cuda_stream), "efd_download", lib)
+                        lev = torch.cuda.Event()
+                        lev.record(gs)
+                        st["lanes_ev_used"].append(lev)
+        finally:
+            for f in futs:
+                f.cancel()
+            for slot in used:
+                cur.wait_stream(st["streams"][slot])
+        if check:
+            self._device_check()
         return out
 
     # prefetch(wait=False) is supported (the likelihood's groups then overlap the upstream)

@@ -692,6 +692,66 @@ int efd_fused_group(void* pin, size_t pin_bytes, void* dbuf, size_t dbuf_bytes, 
                     const double* w, const double* tile_const, double* out, void* staged_event,
                     void* stream, size_t* total);
 
+/*
+ * Amplitudes and ModeSelector(eps) on the device for batched callers (not part of the
+ * reference's interface; csrc/emrifd_modes_device.inc). efd_host_modes' work for `count` walkers
+ * (1 <= count <= EFD_BATCH_MAX) in three launches on `stream`: asynchronous, allocation-free, no
+ * host synchronisation, no atomics; bitwise reproducible, and each walker's outputs are bitwise
+ * those of its own call with count = 1.
+ *
+ * At every knot the branch powers |A_k|^2 |Y_k|^2 (every mode) and |A_k|^2 |Y_{l,-m}|^2 (modes
+ * with m != 0) are sorted descending (ties: the +m branches before the partners, then by mode
+ * index); a branch is kept while the sum of those before it is < (1 - eps) total, the largest
+ * always; partner picks fold onto their +m mode; the kept set is the union over the knots.
+ *
+ * The mode table is shared by the walkers (device): 1 <= nmodes <= 4096.
+ */
+typedef struct efd_modes_table {
+    const int32_t* l;         /* [nmodes]                                                     */
+    const int32_t* m;         /* [nmodes] m != 0 adds the partner branch                      */
+    const int32_t* n;         /* [nmodes]                                                     */
+    const double* phase0;     /* [nmodes] the stand-in model's seeded phases                  */
+    const double* jitter;     /* [nmodes] and log10-magnitude jitter                          */
+    int32_t nmodes;
+} efd_modes_table;
+
+/* One walker of efd_modes_select_batch; every pointer is device memory. */
+typedef struct efd_modes_walker {
+    const double* p;          /* [nt] trajectory knots (1 <= nt <= 1024)                      */
+    const double* e;          /* [nt]                                                         */
+    int32_t nt;
+    const double* ylm_p;      /* complex [nmodes]: Y_lm (walkers may share the pointer)       */
+    const double* ylm_m;      /* complex [nmodes]: (-1)^l Y_{l,-m}                            */
+    double eps;               /* 0 <= eps <= 1                                                */
+    int32_t include_minus_m;  /* 0: ylm_m_out is written as zeros                             */
+    const double* teuk;       /* optional complex [nt][nmodes]: the amplitudes to select on
+                               * and to gather; NULL = the stand-in model of efd_host_modes,
+                               * evaluated in the kernels (STAND-IN PHYSICS, NOT FEW)          */
+    /* outputs, in the mode sum's input layout (efd_modesum_args: amp, m, n, ylm_p, ylm_m) */
+    int32_t* keep;            /* [nmodes] capacity: kept mode indices, ascending              */
+    int32_t* nkeep;           /* [1] K                                                        */
+    int32_t* status;          /* [1] 0, or EFD_MODES_AMP_OVERFLOW                             */
+    double* amp;              /* complex [nt][K], or NULL: no amplitudes wanted               */
+    int64_t amp_cap;          /* complex elements amp holds; nt K > amp_cap sets
+                               * EFD_MODES_AMP_OVERFLOW in status (nkeep is still written,
+                               * nothing is stored past the capacity, amp's content is void)   */
+    int32_t* m_out;           /* [nmodes] capacity: m of the kept modes                       */
+    int32_t* n_out;           /* [nmodes] capacity                                            */
+    double* ylm_p_out;        /* complex [nmodes] capacity                                    */
+    double* ylm_m_out;        /* complex [nmodes] capacity                                    */
+    void* workspace;          /* efd_modes_workspace_bytes(nt, nmodes), 4-byte aligned, the
+                               * walker's own; needs no initialisation                         */
+    size_t workspace_bytes;
+} efd_modes_walker;
+
+#define EFD_MODES_AMP_OVERFLOW 1
+
+/* Bytes of workspace one walker of efd_modes_select_batch needs; 0 for an invalid shape
+ * (nt < 1 or nt > 1024, nmodes < 1 or nmodes > 4096). Host-only query. */
+size_t efd_modes_workspace_bytes(int32_t nt, int32_t nmodes);
+int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w, int32_t count,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
