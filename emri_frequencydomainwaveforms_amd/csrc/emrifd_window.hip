@@ -96,26 +96,44 @@ __device__ __forceinline__ HannRow hann_row(const uint64_t* __restrict__ info, i
     h.scale = __longlong_as_double((long long)info[4 * r + 0]);
     return h;
 }
+// complex64 values as 2-wide float vectors: the arithmetic below compiles to packed FP32
+// instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32, one issue slot per complex add or
+// half a complex multiply), about half the VALU instructions of scalar float2 code
+typedef float fcv __attribute__((ext_vector_type(2)));
+// a row's scaled support, element s of the m-point transform's input: S[first + s] / scale for
+// s < len, zero up to m
+struct HannSupport {
+    const double2* src;   // the row of S at its first nonzero bin
+    int64_t len;
+    double inv;           // 1 / scale (0 for an all-zero row; NaN scale: NaN row)
+    bool bad;             // len > m (the host sized m from info: never, but never write past Y)
+};
+__device__ __forceinline__ HannSupport hann_support(const double2* __restrict__ S, int64_t stride,
+                                                    const uint64_t* __restrict__ info, int r,
+                                                    int64_t m) {
+    const HannRow h = hann_row(info, r);
+    return {S + (int64_t)r * stride + h.first, h.len, h.scale == 0.0 ? 0.0 : 1.0 / h.scale,
+            h.len > m};
+}
+__device__ __forceinline__ fcv fc_load_scaled(const HannSupport x, int64_t s) {
+    fcv v = {0.f, 0.f};
+    if (x.bad) {
+        v = (fcv){__int_as_float(0x7fc00000), 0.f};
+    } else if (s < x.len) {
+        const double2 d = x.src[s];
+        v = (fcv){(float)(d.x * x.inv), (float)(d.y * x.inv)};
+    }
+    return v;
+}
 __global__ __launch_bounds__(256) void k_hann_stage(const double2* __restrict__ S, int64_t stride,
                                                     const uint64_t* __restrict__ info, int64_t m,
                                                     float2* __restrict__ Y) {
     const int r = blockIdx.y;
-    const HannRow h = hann_row(info, r);
-    const double2* row = S + (int64_t)r * stride + h.first;
-    float2* y = Y + (int64_t)r * m;
-    const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;   // NaN scale: NaN row
-    const bool bad = h.len > m;     // the host sized m from info: never, but never write past Y
+    fcv* y = reinterpret_cast<fcv*>(Y) + (int64_t)r * m;
+    const HannSupport x = hann_support(S, stride, info, r, m);
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < m;
-         s += (int64_t)gridDim.x * blockDim.x) {
-        float2 v = make_float2(0.f, 0.f);
-        if (bad) {
-            v = make_float2(__int_as_float(0x7fc00000), 0.f);
-        } else if (s < h.len) {
-            const double2 x = row[s];
-            v = make_float2((float)(x.x * inv), (float)(x.y * inv));
-        }
-        y[s] = v;
-    }
+         s += (int64_t)gridDim.x * blockDim.x)
+        y[s] = fc_load_scaled(x, s);
 }
 // ---- The Hann correction's convolution as one four-step FFT pipeline (efd_hann_convolve).
 // Y = ifft_m(fft_m(y) * kf) for power-of-two m = R * C, C = 8192, R = m / C (256..4096), in
@@ -136,10 +154,6 @@ constexpr int FC_NT = 512;             // threads of a column or row workgroup
 constexpr float FC_2PI = 6.283185307179586f;
 constexpr float FC_SQRT_HALF = 0.70710678118654752f;
 
-// complex64 values as 2-wide float vectors: the arithmetic below compiles to packed FP32
-// instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32, one issue slot per complex add or
-// half a complex multiply), about half the VALU instructions of scalar float2 code
-typedef float fcv __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ fcv cmulf(fcv a, fcv b) {
     const fcv t = a.xx * b;
     return __builtin_elementwise_fma(a.yy, b.yx * (fcv){-1.0f, 1.0f}, t);
@@ -262,6 +276,42 @@ struct FcCols {
     static constexpr int NCOL = R >= 4096 ? 2 : R >= 2048 ? 4 : R >= 1024 ? 8 : 16;
     static constexpr int LOGL = NCOL == 2 ? 1 : NCOL == 4 ? 2 : NCOL == 8 ? 3 : 4;
 };
+// XCD-aware column blocks: workgroups are dealt round-robin over the 8 XCDs (x = b mod 8), so
+// XCD x takes the contiguous eighth [x G/8, (x+1) G/8) of the G column blocks in order; a
+// block's rows are NCOL * 8 or 16 B wide, and the neighbouring blocks sharing their 128-B lines
+// then hit the same L2. rows: the rows that share the grid's x with the column blocks, a column
+// block's rows on consecutive workgroups of its XCD (1: the rows lie along y)
+template <int G, class T>
+__device__ __forceinline__ T fc_col_block(T rows) {
+    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
+    return (T)(blockIdx.x & 7) * (G / 8) + (T)(blockIdx.x >> 3) / rows;
+}
+// the column twiddle w_M^(SIGN c e) of column c at row frequency e
+template <int SIGN, int64_t M>
+__device__ __forceinline__ fcv fc_col_twiddle(int c, int e) {
+    const uint32_t p = (uint32_t)c * (uint32_t)e;   // < C R = M: no reduction
+    float sn, cs;
+    __sincosf((float)SIGN * FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
+    return (fcv){cs, sn};
+}
+// (C)'s first half for the NCOL columns from c0: load, conjugate twiddle, inverse FFT; the
+// columns are left in sm in natural order
+template <int R, int C>
+__device__ __forceinline__ void fc_cols_inverse(fcv* sm, const fcv* y, int c0) {
+    constexpr int NCOL = FcCols<R>::NCOL;
+    static_assert(R * NCOL % FC_NT == 0, "whole rounds of elements per thread");
+    const FcColIdx<NCOL> idx;
+#pragma unroll
+    for (int q = 0; q < R * NCOL / FC_NT; ++q) {
+        const int i = threadIdx.x + q * FC_NT;
+        const int e = i / NCOL, j = i % NCOL;   // e = f_r
+        const int c = c0 + j;
+        const fcv w = fc_col_twiddle<1, (int64_t)R * C>(c, e);
+        sm[idx(j, e)] = cmulf(y[(int64_t)e * C + c], w);
+    }
+    __syncthreads();
+    fc_fft<1, R, FcCols<R>::LOGL>(sm, idx);
+}
 
 // (A) and (C): NCOL columns per workgroup. FWD: load the scaled support of row blockIdx.y
 // straight from S (efd_hann_stage's values), forward FFT, twiddle, store. Inverse: load,
@@ -276,35 +326,17 @@ void k_fc_cols(const double2* __restrict__ S, int64_t stride, const uint64_t* __
     constexpr int NQ = R * NCOL / FC_NT;   // elements per thread
     static_assert(R * NCOL % FC_NT == 0, "whole rounds of elements per thread");
     __shared__ fcv sm[R * FcColIdx<NCOL>::STRIDE];
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
     const FcColIdx<NCOL> idx;
     const int row = blockIdx.y;
-    // XCD-aware column blocks: workgroups are dealt round-robin over the 8 XCDs (x = b mod 8),
-    // so XCD x takes the contiguous eighth [x G/8, (x+1) G/8) of the G column blocks in order;
-    // a block's rows are NCOL * 8 or 16 B wide, and the neighbouring blocks sharing their
-    // 128-B lines then hit the same L2
-    constexpr int G = C / NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
-    const int c0 = ((blockIdx.x & 7) * (G / 8) + (blockIdx.x >> 3)) * NCOL;
-    fcv* y = Y + (int64_t)row * M;
+    const int c0 = fc_col_block<C / NCOL>(1u) * NCOL;
+    fcv* y = reinterpret_cast<fcv*>(Yv) + (int64_t)row * M;
     if (FWD) {
-        const HannRow h = hann_row(info, row);
-        const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;
-        const double2* src = S + (int64_t)row * stride + h.first;
-        const bool bad = h.len > M;
+        const HannSupport x = hann_support(S, stride, info, row, M);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int i = threadIdx.x + q * FC_NT;
             const int e = i / NCOL, j = i % NCOL;
-            const int64_t s = (int64_t)e * C + c0 + j;
-            fcv v = {0.f, 0.f};
-            if (bad) {
-                v = (fcv){__int_as_float(0x7fc00000), 0.f};
-            } else if (s < h.len) {
-                const double2 x = src[s];
-                v = (fcv){(float)(x.x * inv), (float)(x.y * inv)};
-            }
-            sm[idx(j, e)] = v;
+            sm[idx(j, e)] = fc_load_scaled(x, (int64_t)e * C + c0 + j);
         }
         __syncthreads();
         fc_fft<-1, R, LOGL>(sm, idx);
@@ -313,24 +345,11 @@ void k_fc_cols(const double2* __restrict__ S, int64_t stride, const uint64_t* __
             const int i = threadIdx.x + q * FC_NT;
             const int e = i / NCOL, j = i % NCOL;   // e = f_r
             const int c = c0 + j;
-            const uint32_t p = (uint32_t)c * (uint32_t)e;   // < C R = M: no reduction
-            float sn, cs;
-            __sincosf(-FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-            y[(int64_t)e * C + c] = cmulf(sm[idx(j, e)], (fcv){cs, sn});
+            const fcv w = fc_col_twiddle<-1, M>(c, e);
+            y[(int64_t)e * C + c] = cmulf(sm[idx(j, e)], w);
         }
     } else {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = threadIdx.x + q * FC_NT;
-            const int e = i / NCOL, j = i % NCOL;   // e = f_r
-            const int c = c0 + j;
-            const uint32_t p = (uint32_t)c * (uint32_t)e;   // < C R = M: no reduction
-            float sn, cs;
-            __sincosf(FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-            sm[idx(j, e)] = cmulf(y[(int64_t)e * C + c], (fcv){cs, sn});
-        }
-        __syncthreads();
-        fc_fft<1, R, LOGL>(sm, idx);
+        fc_cols_inverse<R, C>(sm, y, c0);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int i = threadIdx.x + q * FC_NT;
@@ -368,90 +387,70 @@ __device__ __forceinline__ fcv fc_w(int j) {
     const int q = (j * (32 / N)) & 31;
     return (fcv){FC_COS32[q], (float)SIGN * FC_COS32[(q + 24) & 31]};
 }
-// natural-order DFT-16 (4 x 4) and DFT-32 (4 x 8) in registers, exp(SIGN 2 pi i n k / N)
-template <int SIGN>
-__device__ __forceinline__ void fc_dft16(fcv* v) {
-    fcv t[4][4];
+// natural-order DFT-16 (N1 = 4: 4 x 4) and DFT-32 (N1 = 8: 4 x 8) in registers,
+// exp(SIGN 2 pi i n k / (4 N1))
+template <int SIGN, int N1>
+__device__ __forceinline__ void fc_dft4x(fcv* v) {
+    static_assert(N1 == 4 || N1 == 8, "DFT-16 or DFT-32");
+    fcv t[N1][4];
 #pragma unroll
-    for (int n1 = 0; n1 < 4; ++n1) {   // DFT-4 over n2 of x[n1 + 4 n2]
-        fcv a0 = v[n1], a1 = v[n1 + 4], a2 = v[n1 + 8], a3 = v[n1 + 12];
+    for (int n1 = 0; n1 < N1; ++n1) {   // DFT-4 over n2 of x[n1 + N1 n2]
+        fcv a0 = v[n1], a1 = v[n1 + N1], a2 = v[n1 + 2 * N1], a3 = v[n1 + 3 * N1];
         fc_dft4<SIGN>(a0, a1, a2, a3);
         t[n1][0] = a0; t[n1][1] = a1; t[n1][2] = a2; t[n1][3] = a3;
     }
 #pragma unroll
-    for (int n1 = 1; n1 < 4; ++n1)
+    for (int n1 = 1; n1 < N1; ++n1)
 #pragma unroll
-        for (int k1 = 1; k1 < 4; ++k1) t[n1][k1] = cmulf(t[n1][k1], fc_w<SIGN, 16>(n1 * k1));
+        for (int k1 = 1; k1 < 4; ++k1) t[n1][k1] = cmulf(t[n1][k1], fc_w<SIGN, 4 * N1>(n1 * k1));
 #pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {   // DFT-4 over n1 -> X[k1 + 4 k2]
-        fcv a0 = t[0][k1], a1 = t[1][k1], a2 = t[2][k1], a3 = t[3][k1];
-        fc_dft4<SIGN>(a0, a1, a2, a3);
-        v[k1] = a0; v[k1 + 4] = a1; v[k1 + 8] = a2; v[k1 + 12] = a3;
+    for (int k1 = 0; k1 < 4; ++k1) {   // DFT-N1 over n1 -> X[k1 + 4 k2]
+        fcv e[N1];
+#pragma unroll
+        for (int n1 = 0; n1 < N1; ++n1) e[n1] = t[n1][k1];
+        if constexpr (N1 == 8) fc_dft8<SIGN>(e);
+        else fc_dft4<SIGN>(e[0], e[1], e[2], e[3]);
+#pragma unroll
+        for (int k2 = 0; k2 < N1; ++k2) v[k1 + 4 * k2] = e[k2];
     }
 }
 template <int SIGN>
-__device__ __forceinline__ void fc_dft32(fcv* v) {
-    fcv t[8][4];
-#pragma unroll
-    for (int n1 = 0; n1 < 8; ++n1) {   // DFT-4 over n2 of x[n1 + 8 n2]
-        fcv a0 = v[n1], a1 = v[n1 + 8], a2 = v[n1 + 16], a3 = v[n1 + 24];
-        fc_dft4<SIGN>(a0, a1, a2, a3);
-        t[n1][0] = a0; t[n1][1] = a1; t[n1][2] = a2; t[n1][3] = a3;
-    }
-#pragma unroll
-    for (int n1 = 1; n1 < 8; ++n1)
-#pragma unroll
-        for (int k1 = 1; k1 < 4; ++k1) t[n1][k1] = cmulf(t[n1][k1], fc_w<SIGN, 32>(n1 * k1));
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {   // DFT-8 over n1 -> X[k1 + 4 k2]
-        fcv e[8];
-#pragma unroll
-        for (int n1 = 0; n1 < 8; ++n1) e[n1] = t[n1][k1];
-        fc_dft8<SIGN>(e);
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2) v[k1 + 4 * k2] = e[k2];
-    }
-}
-// v[j] *= w^j, j = 0 .. N-1, w = exp(i theta): powers from w and w^8 (at most 3 + 7 products)
-template <int N>
-__device__ __forceinline__ void fc_twiddle_pow(fcv* v, float theta) {
-    float s1, c1, s8, c8;
-    __sincosf(theta, &s1, &c1);
-    __sincosf(8.0f * theta, &s8, &c8);
-    const fcv w1 = {c1, s1}, w8 = {c8, s8};
-    fcv p[8];
-    p[0] = (fcv){1.0f, 0.0f};
-    p[1] = w1;
-#pragma unroll
-    for (int j = 2; j < 8; ++j) p[j] = cmulf(p[j - 1], w1);
-    fcv b = (fcv){1.0f, 0.0f};
-#pragma unroll
-    for (int a = 0; a < N / 8; ++a) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (a + j > 0) v[8 * a + j] = cmulf(v[8 * a + j], a == 0 ? p[j] : (j == 0 ? b : cmulf(b, p[j])));
-        b = a == 0 ? w8 : cmulf(b, w8);
-    }
-}
-// v[j] *= w0 w^j, j = 0 .. N-1, w = exp(i theta): fc_twiddle_pow with the constant factor w0
-// folded into the powers (8 products instead of N)
-template <int N>
-__device__ __forceinline__ void fc_twiddle_pow_from(fcv* v, fcv w0, float theta) {
+__device__ __forceinline__ void fc_dft16(fcv* v) { fc_dft4x<SIGN, 4>(v); }
+template <int SIGN>
+__device__ __forceinline__ void fc_dft32(fcv* v) { fc_dft4x<SIGN, 8>(v); }
+// v[j] *= w^j, j = 0 .. N-1, w = exp(i theta): powers from w and w^8 (at most 3 + 7 products).
+// FROM: v[j] *= w0 w^j, the constant factor w0 folded into the powers (8 products more instead
+// of N); without it no product by 1 is formed
+template <int N, bool FROM = false>
+__device__ __forceinline__ void fc_twiddle_pow(fcv* v, float theta, fcv w0 = {1.0f, 0.0f}) {
     float s1, c1, s8, c8;
     __sincosf(theta, &s1, &c1);
     __sincosf(8.0f * theta, &s8, &c8);
     const fcv w1 = {c1, s1}, w8 = {c8, s8};
     fcv p[8];
     p[0] = w0;
+    if constexpr (!FROM) p[1] = w1;
 #pragma unroll
-    for (int j = 1; j < 8; ++j) p[j] = cmulf(p[j - 1], w1);
+    for (int j = FROM ? 1 : 2; j < 8; ++j) p[j] = cmulf(p[j - 1], w1);
     fcv b = (fcv){1.0f, 0.0f};
 #pragma unroll
     for (int a = 0; a < N / 8; ++a) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[8 * a + j] = cmulf(v[8 * a + j], a == 0 ? p[j] : cmulf(b, p[j]));
+        for (int j = 0; j < 8; ++j)
+            if (FROM || a + j > 0)
+                v[8 * a + j] = cmulf(v[8 * a + j],
+                                     a == 0 ? p[j] : (!FROM && j == 0) ? b : cmulf(b, p[j]));
         b = a == 0 ? w8 : cmulf(b, w8);
     }
+}
+// the workgroup's (row f_r, walker) pair as p = f_r rows + walker: XCD x = b mod 8 takes the
+// contiguous eighth of the pairs in f_r-major order, so a kernel-spectrum row is read from HBM
+// once per XCD and from its L2 for the group's other walkers (gridDim.x = R * rows, a multiple
+// of 8). (The row kernels split p themselves: split in here, the compiler orders their address
+// arithmetic differently, the only change that made to their instruction streams.)
+__device__ __forceinline__ int64_t fc_row_pair() {
+    const int64_t npair = (int64_t)gridDim.x;
+    return (int64_t)(blockIdx.x & 7) * (npair >> 3) + (blockIdx.x >> 3);
 }
 __global__ __launch_bounds__(FR_NT)
 void k_fc_rows(const float2* __restrict__ kfpv, int64_t m, int rows, float2* __restrict__ Yv) {
@@ -459,11 +458,7 @@ void k_fc_rows(const float2* __restrict__ kfpv, int64_t m, int rows, float2* __r
     __shared__ fcv sm[32 * FR_S1];   // exchange 1 [k1][n2] (stride 257); exchange 2 [k2a][n2a][k1]
     const fcv* kfp = reinterpret_cast<const fcv*>(kfpv);
     fcv* Y = reinterpret_cast<fcv*>(Yv);
-    // (row f_r, walker) pairs: XCD x = b mod 8 takes the contiguous eighth of them in f_r-major
-    // order, so a kernel-spectrum row is read from HBM once per XCD and from its L2 for the
-    // group's other walkers (gridDim.x = R * rows, a multiple of 8)
-    const int64_t npair = (int64_t)gridDim.x;
-    const int64_t p = (int64_t)(blockIdx.x & 7) * (npair >> 3) + (blockIdx.x >> 3);
+    const int64_t p = fc_row_pair();   // = f_r rows + walker
     const int fr = (int)(p / rows), wk = (int)(p - (int64_t)fr * rows);
     fcv* y = Y + (int64_t)wk * m + (int64_t)fr * FC_C;
     const fcv* kr = kfp + (int64_t)fr * FC_C;
@@ -568,8 +563,7 @@ void k_fc_rows16k_h(const float2* __restrict__ kfpv, int64_t m, int rows, float2
     __shared__ float sf[32 * (FR16_T1 > FR16_T2 ? FR16_T1 : FR16_T2)];
     const fcv* kfp = reinterpret_cast<const fcv*>(kfpv);
     fcv* Y = reinterpret_cast<fcv*>(Yv);
-    const int64_t npair = (int64_t)gridDim.x;
-    const int64_t p = (int64_t)(blockIdx.x & 7) * (npair >> 3) + (blockIdx.x >> 3);
+    const int64_t p = fc_row_pair();   // = f_r rows + walker
     const int fr = (int)(p / rows), wk = (int)(p - (int64_t)fr * rows);
     fcv* y = Y + (int64_t)wk * m + (int64_t)fr * FC_C16;
     const fcv* kr = kfp + (int64_t)fr * FC_C16;
@@ -642,7 +636,8 @@ void k_fc_rows16k_h(const float2* __restrict__ kfpv, int64_t m, int rows, float2
     {
         float s0, c0;
         __sincosf(W16K * (float)(nb * kb), &s0, &c0);
-        fc_twiddle_pow_from<32>(u, (fcv){c0, s0}, W16K * 16.0f * (float)kb);
+        const fcv w0 = {c0, s0};
+        fc_twiddle_pow<32, true>(u, W16K * 16.0f * (float)kb, w0);
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) {   // exchange 1 back -> inverse (A): n2 = t
@@ -682,12 +677,9 @@ void k_fc_cols1024(const double2* __restrict__ S, int64_t stride, const uint64_t
     constexpr int64_t M = (int64_t)FCD_R * C;
     // exchange 1: 16 x 64 x 8 = 8192; exchange 2: 16 x 8 x 9 x 8 = 9216 elements (73.7 KB)
     __shared__ fcv sm[16 * 8 * FCD_S2 * FCD_NCOL];
-    fcv* Y = reinterpret_cast<fcv*>(Yv);
     const int row = blockIdx.y;
-    constexpr int G = C / FCD_NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
-    const int c0 = ((blockIdx.x & 7) * (G / 8) + (blockIdx.x >> 3)) * FCD_NCOL;
-    fcv* y = Y + (int64_t)row * M;
+    const int c0 = fc_col_block<C / FCD_NCOL>(1u) * FCD_NCOL;
+    fcv* y = reinterpret_cast<fcv*>(Yv) + (int64_t)row * M;
     const int t = threadIdx.x;
     const int j = t & 7;
     const int c = c0 + j;
@@ -697,25 +689,13 @@ void k_fc_cols1024(const double2* __restrict__ S, int64_t stride, const uint64_t
         return ((k1 * 8 + k2a) * FCD_S2 + n2a) * FCD_NCOL + jj;
     };
     {
-        const HannRow h = hann_row(info, row);
-        const double inv = h.scale == 0.0 ? 0.0 : 1.0 / h.scale;
-        const double2* src = S + (int64_t)row * stride + h.first;
-        const bool bad = h.len > M;
+        const HannSupport x = hann_support(S, stride, info, row, M);
         {   // (A): task (j, n2)
             const int n2 = t >> 3;
             fcv v[16];
 #pragma unroll
-            for (int n1 = 0; n1 < 16; ++n1) {
-                const int64_t s = (int64_t)(n2 + 64 * n1) * C + c;
-                fcv x = {0.f, 0.f};
-                if (bad) {
-                    x = (fcv){__int_as_float(0x7fc00000), 0.f};
-                } else if (s < h.len) {
-                    const double2 d = src[s];
-                    x = (fcv){(float)(d.x * inv), (float)(d.y * inv)};
-                }
-                v[n1] = x;
-            }
+            for (int n1 = 0; n1 < 16; ++n1)
+                v[n1] = fc_load_scaled(x, (int64_t)(n2 + 64 * n1) * C + c);
             fc_dft16<-1>(v);
             fc_twiddle_pow<16>(v, -W1024 * (float)n2);
 #pragma unroll
@@ -751,10 +731,7 @@ void k_fc_cols1024(const double2* __restrict__ S, int64_t stride, const uint64_t
 #pragma unroll
             for (int k2b = 0; k2b < 8; ++k2b) {
                 const int fr = k1 + 16 * k2a + 128 * k2b;
-                const uint32_t pp = (uint32_t)c * (uint32_t)fr;   // < C R = M: no reduction
-                float sn, cs;
-                __sincosf(-FC_2PI * ((float)pp * (1.0f / (float)M)), &sn, &cs);
-                y[(int64_t)fr * C + c] = cmulf(w[k2b], (fcv){cs, sn});
+                y[(int64_t)fr * C + c] = cmulf(w[k2b], fc_col_twiddle<-1, M>(c, fr));
             }
         }
     }
@@ -764,29 +741,43 @@ void k_fc_cols1024(const double2* __restrict__ S, int64_t stride, const uint64_t
 // S is zero outside the row's support [first, first + len) (cyclic; efd_hann_extent's bounds),
 // so it is read only there: the support is ~40% of test.sh's grid, and the skipped reads were
 // half of the reduction's HBM bytes (the correction C = Y is nonzero everywhere)
-__device__ __forceinline__ double2 hann_sw(const double2* __restrict__ S,
-                                           const float2* __restrict__ Y, int64_t nf, int64_t k,
-                                           double c, int64_t first, int64_t len, int64_t off) {
+struct HannSrc {
+    const double2* S;   // the row of S and of Y
+    const float2* Y;
+    int64_t nf;
+    double c;           // the correction's weight e / 4 times the row's scale
+    int64_t first, len, off;
+};
+__device__ __forceinline__ HannSrc hann_src(const double2* __restrict__ S, int64_t stride,
+                                            const float2* __restrict__ Y,
+                                            const uint64_t* __restrict__ info, int r, int64_t m,
+                                            int64_t nf) {
+    const HannRow h = hann_row(info, r);
+    return {S + (int64_t)r * stride, Y + (int64_t)r * m, nf, h.scale / (4.0 * (double)(nf - 1)),
+            h.first, h.len, m - nf};
+}
+__device__ __forceinline__ double2 hann_sw(const HannSrc x, int64_t k) {
+    const int64_t nf = x.nf;
     const int64_t kp = k + 1 < nf ? k + 1 : 0, km = k > 0 ? k - 1 : nf - 1;
-    int64_t qp = kp - first, qm = km - first, q0 = k - first;
+    int64_t qp = kp - x.first, qm = km - x.first, q0 = k - x.first;
     qp += qp < 0 ? nf : 0;
     qm += qm < 0 ? nf : 0;
     q0 += q0 < 0 ? nf : 0;
     const double2 z = make_double2(0.0, 0.0);
-    const double2 s = q0 < len ? S[k] : z, sp = qp < len ? S[kp] : z, sm = qm < len ? S[km] : z;
-    const float2 cp = Y[qp + off], cm = Y[qm + off];
-    return make_double2(0.5 * s.x - 0.25 * (sp.x + sm.x) - c * ((double)cp.x - (double)cm.x),
-                        0.5 * s.y - 0.25 * (sp.y + sm.y) - c * ((double)cp.y - (double)cm.y));
+    const double2 s = q0 < x.len ? x.S[k] : z, sp = qp < x.len ? x.S[kp] : z,
+                  sm = qm < x.len ? x.S[km] : z;
+    const float2 cp = x.Y[qp + x.off], cm = x.Y[qm + x.off];
+    return make_double2(0.5 * s.x - 0.25 * (sp.x + sm.x) - x.c * ((double)cp.x - (double)cm.x),
+                        0.5 * s.y - 0.25 * (sp.y + sm.y) - x.c * ((double)cp.y - (double)cm.y));
 }
-// h+ = (a + conj b)/2, hx = i (a - conj b)/2 of the windowed spectrum at k (a) and nf-1-k (b)
-__device__ __forceinline__ void hann_pol(const double2* __restrict__ S,
-                                         const float2* __restrict__ Y, int64_t nf, int64_t k,
-                                         double c, int64_t first, int64_t len, int64_t off,
-                                         double2& vp, double2& vc) {
-    const double2 a = hann_sw(S, Y, nf, k, c, first, len, off);
-    const double2 b = hann_sw(S, Y, nf, nf - 1 - k, c, first, len, off);
+// h+ = (a + conj b)/2, hx = i (a - conj b)/2 of the windowed spectrum at a bin (a) and at its
+// mirror (b)
+__device__ __forceinline__ void pol_split(double2 a, double2 b, double2& vp, double2& vc) {
     vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
     vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
+}
+__device__ __forceinline__ void hann_pol(const HannSrc x, int64_t k, double2& vp, double2& vc) {
+    pol_split(hann_sw(x, k), hann_sw(x, x.nf - 1 - k), vp, vc);
 }
 __global__ void k_hann_polarizations(const double2* __restrict__ S, const float2* __restrict__ Y,
                                      const uint64_t* __restrict__ info, int64_t m, int64_t nf,
@@ -795,12 +786,53 @@ __global__ void k_hann_polarizations(const double2* __restrict__ S, const float2
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t k = k0 + i;
     if (k >= nf) return;
-    const HannRow h = hann_row(info, 0);
-    const double c = h.scale / (4.0 * (double)(nf - 1));
     double2 vp, vc;
-    hann_pol(S, Y, nf, k, c, h.first, h.len, m - nf, vp, vc);
+    hann_pol(hann_src(S, 0, Y, info, 0, m, nf), k, vp, vc);
     hp[i] = vp;
     hc[i] = vc;
+}
+
+// The pair-form logL kernels' shared pieces (k_hann_loglike_partial, k_cosw_loglike_partial).
+// The workgroup's row group and bin chunk: RPT rows per workgroup (rows = RPT x the row groups),
+// the row groups of a chunk on consecutive workgroups of one XCD (workgroup b runs on XCD b mod 8)
+template <int RPT>
+__device__ __forceinline__ void ll_row_group(int rows, int& r0, int& chunk) {
+    const int ngr = rows / RPT;
+    const int j = (int)(blockIdx.x >> 3);
+    r0 = (j % ngr) * RPT;
+    chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
+}
+// efd_loglike's terms of one bin (d - h w, product rounded then difference) for both channels
+__device__ __forceinline__ void ll_term(double2 d0, double2 d1, double w0, double w1, double2 vp,
+                                        double2 vc, double& acc) {
+#pragma clang fp contract(off)
+    const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
+    const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
+    acc = fma(x0, x0, fma(y0, y0, acc));
+    acc = fma(x1, x1, fma(y1, y1, acc));
+}
+// the workgroup's sum of each of its RPT accumulators: a butterfly over each wave, then the NW
+// waves in turn (fixed order); thread q < RPT stores row r0 + q's (HALVE: the local form's 1/2)
+// at part[(r0 + q) step + at] when the workgroup has a chunk (ok)
+template <int RPT, int NW, bool HALVE>
+__device__ __forceinline__ void ll_store(const double* acc, double* __restrict__ part, int r0,
+                                         int step, int at, bool ok) {
+    __shared__ double red[RPT][NW];
+#pragma unroll
+    for (int q = 0; q < RPT; ++q) {
+        double a = acc[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x < RPT && ok) {
+        const int q = threadIdx.x;
+        double t = red[q][0];
+#pragma unroll
+        for (int wv = 1; wv < NW; ++wv) t += red[q][wv];
+        part[(int64_t)(r0 + q) * step + at] = HALVE ? 0.5 * t : t;
+    }
 }
 // the windowed templates' log-likelihood partials of every row: efd_loglike's terms (d - h w,
 // product rounded then difference) for both channels of every bin [k0, nf). One workgroup per
@@ -820,19 +852,11 @@ __global__ __launch_bounds__(256) void k_hann_loglike_partial(
     const uint64_t* __restrict__ info, int64_t m, int64_t nf, int64_t k0,
     const double2* __restrict__ d, const double* __restrict__ w, int rows, int nchunk,
     double* __restrict__ part) {
-#pragma clang fp contract(off)
-    const int ngr = rows / RPT;
-    const int j = (int)(blockIdx.x >> 3);
-    const int r0 = (j % ngr) * RPT, chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
-    double c[RPT];
-    int64_t first[RPT], len[RPT];
+    int r0, chunk;
+    ll_row_group<RPT>(rows, r0, chunk);
+    HannSrc x[RPT];
 #pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        const HannRow h = hann_row(info, r0 + q);
-        c[q] = h.scale / (4.0 * (double)(nf - 1));
-        first[q] = h.first;
-        len[q] = h.len;
-    }
+    for (int q = 0; q < RPT; ++q) x[q] = hann_src(S, stride, Y, info, r0 + q, m, nf);
     const int64_t nb = nf - k0;
     double acc[RPT];
 #pragma unroll
@@ -843,28 +867,11 @@ __global__ __launch_bounds__(256) void k_hann_loglike_partial(
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
             double2 vp, vc;
-            hann_pol(S + (int64_t)(r0 + q) * stride, Y + (int64_t)(r0 + q) * m, nf, k0 + i, c[q],
-                     first[q], len[q], m - nf, vp, vc);
-            const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
-            const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
-            acc[q] = fma(x0, x0, fma(y0, y0, acc[q]));
-            acc[q] = fma(x1, x1, fma(y1, y1, acc[q]));
+            hann_pol(x[q], k0 + i, vp, vc);
+            ll_term(d0, d1, w0, w1, vp, vc, acc[q]);
         }
     }
-    // a butterfly over each wave, then the 4 waves in turn (fixed order)
-    __shared__ double red[RPT][4];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        double a = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPT && chunk < nchunk) {
-        const int q = threadIdx.x;
-        part[(int64_t)(r0 + q) * nchunk + chunk] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
-    }
+    ll_store<RPT, 4, false>(acc, part, r0, nchunk, chunk, chunk < nchunk);
 }
 
 // ---- Cosine-sum windows (efd_cosw_*; fdutils.CosineWindowConvolution): scipy's symmetric
@@ -958,10 +965,8 @@ __device__ __forceinline__ double2 cosw_sw(const double2* s, const float2* y, in
 template <int J>
 __device__ __forceinline__ void cosw_pol(const CoswTile<J>& t, int x, const CoswCoef& cf,
                                          const double* g, double2& vp, double2& vc) {
-    const double2 a = cosw_sw<J>(t.s[0], t.y[0], x + J, cf, g);
-    const double2 b = cosw_sw<J>(t.s[1], t.y[1], COSW_TILE - 1 - x + J, cf, g);
-    vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
+    pol_split(cosw_sw<J>(t.s[0], t.y[0], x + J, cf, g),
+              cosw_sw<J>(t.s[1], t.y[1], COSW_TILE - 1 - x + J, cf, g), vp, vc);
 }
 template <int J>
 __global__ __launch_bounds__(COSW_TILE) void k_cosw_polarizations(
@@ -996,9 +1001,8 @@ __global__ __launch_bounds__(COSW_TILE) void k_cosw_loglike_partial(
     double* __restrict__ part) {
 #pragma clang fp contract(off)
     __shared__ CoswTile<J> t[RPT];
-    const int ngr = rows / RPT;
-    const int j = (int)(blockIdx.x >> 3);
-    const int r0 = (j % ngr) * RPT, chunk = (int)(blockIdx.x & 7) + 8 * (j / ngr);
+    int r0, chunk;
+    ll_row_group<RPT>(rows, r0, chunk);
     double g[RPT][3];
     int64_t first[RPT], len[RPT];
 #pragma unroll
@@ -1039,28 +1043,12 @@ __global__ __launch_bounds__(COSW_TILE) void k_cosw_loglike_partial(
             for (int q = 0; q < RPT; ++q) {
                 double2 vp, vc;
                 cosw_pol<J>(t[q], threadIdx.x, cf, g[q], vp, vc);
-                const double x0 = d0.x - vp.x * w0, y0 = d0.y - vp.y * w0;
-                const double x1 = d1.x - vc.x * w1, y1 = d1.y - vc.y * w1;
-                acc[q] = fma(x0, x0, fma(y0, y0, acc[q]));
-                acc[q] = fma(x1, x1, fma(y1, y1, acc[q]));
+                ll_term(d0, d1, w0, w1, vp, vc, acc[q]);
             }
         }
         __syncthreads();
     }
-    // a butterfly over each wave, then the 4 waves in turn (fixed order)
-    __shared__ double red[RPT][4];
-#pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        double a = acc[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPT && chunk < nchunk) {
-        const int q = threadIdx.x;
-        part[(int64_t)(r0 + q) * nchunk + chunk] = ((red[q][0] + red[q][1]) + red[q][2]) + red[q][3];
-    }
+    ll_store<RPT, 4, false>(acc, part, r0, nchunk, chunk, chunk < nchunk);
 }
 
 // (C) with the windowed logL fused in (efd_hann_loglike_local). Per bin the two channels' terms
@@ -1149,18 +1137,9 @@ __device__ __forceinline__ HannLl hann_ll_ctx(const double2* S, int64_t stride,
     x.emit = emit;
     return x;
 }
-// the workgroup's partial (wave butterflies, then the waves in order): part[row G + cb], halved
-__device__ __forceinline__ void hann_ll_store(double acc, double* red, double* part, int64_t at) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) t += red[wv];
-        part[at] = 0.5 * t;
-    }
-}
+// (the workgroup's partial is the pair form's ll_store over the 8 waves, halved: part[row G +
+// cb]. Its sum starts from the first wave's where this kernel's own epilogue started from 0.0:
+// the same bits, since a wave's sum of squares is never -0.0)
 template <int R, int C>
 __global__ __launch_bounds__(FC_NT) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void k_fc_cols_ll(const double2* __restrict__ S, int64_t stride, const uint64_t* __restrict__ info,
@@ -1168,31 +1147,15 @@ void k_fc_cols_ll(const double2* __restrict__ S, int64_t stride, const uint64_t*
                   const double* __restrict__ wl, int64_t kself, double2 kfix, int rows,
                   double* __restrict__ part, double2* __restrict__ emit) {
 #pragma clang fp contract(off)
-    constexpr int NCOL = FcCols<R>::NCOL, LOGL = FcCols<R>::LOGL;
+    constexpr int NCOL = FcCols<R>::NCOL;
     constexpr int64_t M = (int64_t)R * C;
     constexpr int NQ = R * NCOL / FC_NT;
-    static_assert(R * NCOL % FC_NT == 0, "whole rounds of elements per thread");
     constexpr int G = C / NCOL;
-    static_assert(G % 8 == 0, "column blocks: a multiple of the 8 XCDs");
     __shared__ fcv sm[R * FcColIdx<NCOL>::STRIDE];
-    __shared__ double red[FC_NT / 64];
-    const fcv* Y = reinterpret_cast<const fcv*>(Yv);
     const FcColIdx<NCOL> idx;
-    const int q8 = (int)(blockIdx.x >> 3);
-    const int row = q8 % rows, cb = (int)(blockIdx.x & 7) * (G / 8) + q8 / rows;
+    const int row = (int)(blockIdx.x >> 3) % rows, cb = fc_col_block<G>(rows);
     const int c0 = cb * NCOL;
-    const fcv* y = Y + (int64_t)row * M;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int i = threadIdx.x + q * FC_NT;
-        const int e = i / NCOL, j = i % NCOL;
-        const uint32_t p = (uint32_t)(c0 + j) * (uint32_t)e;
-        float sn, cs;
-        __sincosf(FC_2PI * ((float)p * (1.0f / (float)M)), &sn, &cs);
-        sm[idx(j, e)] = cmulf(y[(int64_t)e * C + c0 + j], (fcv){cs, sn});
-    }
-    __syncthreads();
-    fc_fft<1, R, LOGL>(sm, idx);
+    fc_cols_inverse<R, C>(sm, reinterpret_cast<const fcv*>(Yv) + (int64_t)row * M, c0);
     const HannLl x = hann_ll_ctx(S, stride, info, row, M, nf, dl, kself, kfix, emit);
     const int offi = (int)(M - nf);
     // the elements' data (dl, wl) requested QH at a time before any of them is used: QH loads
@@ -1228,7 +1191,7 @@ void k_fc_cols_ll(const double2* __restrict__ S, int64_t stride, const uint64_t*
         }
     }
     if (emit != nullptr) return;
-    hann_ll_store(acc, red, part, (int64_t)row * G + cb);
+    ll_store<1, FC_NT / 64, true>(&acc, part, row, G, cb, true);
 }
 
 }  // namespace
@@ -1283,52 +1246,70 @@ static int hann_pipeline(const double* S, int64_t stride, int64_t nf, int32_t ro
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
+// The table of four-step splits m = R x C: f(FcSplit<R, C>) for the split of m, false when m has
+// none. The row length C is 8192 but at m = 2^24, 1024 x 16384 (the column kernels read 128 B
+// segments, r05z; the 2048 x 8192 split measured 1.08 against 0.73 ms of column passes and was
+// deleted in round 6). The lag kernel's spectrum is laid out [f_r][f_c] for the same C.
+template <int RR, int CC>
+struct FcSplit {
+    static constexpr int R = RR, C = CC, NCOL = FcCols<RR>::NCOL;
+};
+template <class F>
+static bool fc_split(int64_t m, F f) {
+    switch (m) {
+        case (int64_t)256 * FC_C: f(FcSplit<256, FC_C>{}); return true;
+        case (int64_t)512 * FC_C: f(FcSplit<512, FC_C>{}); return true;
+        case (int64_t)1024 * FC_C: f(FcSplit<1024, FC_C>{}); return true;
+        case (int64_t)1024 * FC_C16: f(FcSplit<1024, FC_C16>{}); return true;
+        case (int64_t)4096 * FC_C: f(FcSplit<4096, FC_C>{}); return true;
+        default: return false;
+    }
+}
 static int hann_pipeline_m(const double* S, int64_t stride, int64_t nf, int32_t rows,
                            const uint64_t* info, int64_t m, const float* kfp, float* Y,
                            const HannLocal* ll, hipStream_t st) {
-    if (m == ((int64_t)1 << 24))
-        return hann_pipeline<(1 << 24) / FC_C16, FC_C16>(S, stride, nf, rows, info, kfp, Y, ll, st);
-    switch (m / FC_C) {   // R = 2048 is m = 2^24, the 1024 x 16384 split above
-        case 256: return hann_pipeline<256, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 512: return hann_pipeline<512, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 1024: return hann_pipeline<1024, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        case 4096: return hann_pipeline<4096, FC_C>(S, stride, nf, rows, info, kfp, Y, ll, st);
-        default: return fail(EFD_ERR_ARG, "efd_hann_convolve: no four-step split for this m");
-    }
+    int rc = EFD_OK;
+    if (!fc_split(m, [&](auto s) {
+            using T = decltype(s);
+            rc = hann_pipeline<T::R, T::C>(S, stride, nf, rows, info, kfp, Y, ll, st);
+        }))
+        return fail(EFD_ERR_ARG, "efd_hann_convolve: no four-step split for this m");
+    return rc;
 }
 
-template <int J>
-static void cosw_launch_pol(int64_t blocks, hipStream_t st, const double* S, const float* Y,
-                            const uint64_t* info, int64_t m, int64_t nf, int64_t k0,
-                            const CoswCoef& cf, double* hp, double* hc) {
-    hipLaunchKernelGGL(k_cosw_polarizations<J>, dim3((unsigned)blocks), dim3(COSW_TILE), 0, st,
-                       (const double2*)S, (const float2*)Y, info, m, nf, k0, cf, (double2*)hp,
-                       (double2*)hc);
+// f(std::integral_constant<int, J>) for the stencil width J = nterm - 1 in 1..3 (cosw_coef has
+// checked nterm)
+template <class F>
+static void cosw_width(int32_t nterm, F f) {
+    switch (nterm - 1) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{}); break;
+    }
 }
-template <int J>
-static void cosw_launch_ll(int rpt, int np, hipStream_t st, const double* S, int64_t stride,
-                           const float* Y, const uint64_t* info, int64_t m, int32_t rows,
-                           int64_t nf, int64_t k0, const CoswCoef& cf, const double* d,
-                           const double* w, double* scratch) {
-    hipLaunchKernelGGL((rpt == 2 ? k_cosw_loglike_partial<J, 2> : k_cosw_loglike_partial<J, 1>),
-                       dim3((unsigned)(np * (rows / rpt))), dim3(COSW_TILE), 0, st,
-                       (const double2*)S, stride, (const float2*)Y, info, m, nf, k0, cf,
-                       (const double2*)d, w, (int)rows, np, scratch);
+// the pair-form logL kernels' launch shape over nb bins, 256 a chunk. np chunks: a multiple of 8
+// (one per XCD in turn), at most EFD_LOGLIKE_SCRATCH per row. rpt rows a workgroup: two when the
+// rows pair up (d and w read once for both: 362 -> 318 us, r05zr), one for an odd row count.
+struct PairShape {
+    int np, rpt;
+    unsigned blocks;
+};
+static PairShape pair_shape(int64_t nb, int32_t rows) {
+    static_assert(EFD_LOGLIKE_SCRATCH % 8 == 0, "chunks: whole rounds of the 8 XCDs");
+    static_assert(COSW_TILE == 256, "one chunk size for both stencils");
+    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH, ((nb + 255) / 256 + 7) / 8 * 8);
+    const int rpt = (rows % 2 == 0) ? 2 : 1;
+    return {np, rpt, (unsigned)(np * (rows / rpt))};
 }
 
 extern "C" {
 
-static bool hann_rows_ok(const char* fn, const void* S, int64_t stride, int64_t nf,
-                         int32_t rows) {
-    if (!S || nf < 3 || rows < 1 || rows > 65535 || stride < nf) {
-        fail(EFD_ERR_ARG, std::string(fn) + ": bad arguments");
-        return false;
-    }
-    return true;
+static bool hann_rows_ok(const void* S, int64_t stride, int64_t nf, int32_t rows) {
+    return S && nf >= 3 && rows >= 1 && rows <= 65535 && stride >= nf;
 }
 int efd_hann_extent(const double* S, int64_t stride, int64_t nf, int32_t rows,
                     const int32_t* lanes, uint64_t* info, void* stream) {
-    if (!hann_rows_ok("efd_hann_extent", S, stride, nf, rows) || !info)
+    if (!hann_rows_ok(S, stride, nf, rows) || !info)
         return fail(EFD_ERR_ARG, "efd_hann_extent: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_hann_info_init, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, info,
@@ -1346,7 +1327,7 @@ int efd_hann_extent(const double* S, int64_t stride, int64_t nf, int32_t rows,
 }
 int efd_hann_stage(const double* S, int64_t stride, int64_t nf, int32_t rows,
                    const uint64_t* info, int64_t m, float* Y, void* stream) {
-    if (!hann_rows_ok("efd_hann_stage", S, stride, nf, rows) || !info || !Y || m < nf)
+    if (!hann_rows_ok(S, stride, nf, rows) || !info || !Y || m < nf)
         return fail(EFD_ERR_ARG, "efd_hann_stage: bad arguments");
     const int64_t blocks = std::min<int64_t>(4096, (m + 255) / 256);
     hipLaunchKernelGGL(k_hann_stage, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0,
@@ -1354,40 +1335,34 @@ int efd_hann_stage(const double* S, int64_t stride, int64_t nf, int32_t rows,
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
-// the four-step split's row length C for a transform length m (the lag kernel's spectrum is
-// laid out [f_r][f_c], R = m / C): 16384 at m = 2^24 (1024 x 16384: the column kernels read
-// 128 B segments, r05z; the 2048 x 8192 split measured 1.08 against 0.73 ms of column passes and
-// was deleted in round 6), else 8192
+// the four-step split's row length C for a transform length m (fc_split; 8192 where m has none)
 int efd_hann_four_step_cols(int64_t m) {
-    return m == ((int64_t)1 << 24) ? FC_C16 : FC_C;
+    int c = FC_C;
+    fc_split(m, [&](auto s) { c = decltype(s)::C; });
+    return c;
 }
 static bool hann_four_step_m(int64_t m, int64_t nf) {
     return m >= nf && m >= ((int64_t)1 << 21) && m <= ((int64_t)1 << 25) && (m & (m - 1)) == 0;
 }
 int efd_hann_convolve(const double* S, int64_t stride, int64_t nf, int32_t rows,
                       const uint64_t* info, int64_t m, const float* kfp, float* Y, void* stream) {
-    if (!hann_rows_ok("efd_hann_convolve", S, stride, nf, rows) || !info || !kfp || !Y ||
+    if (!hann_rows_ok(S, stride, nf, rows) || !info || !kfp || !Y ||
         !hann_four_step_m(m, nf))
         return fail(EFD_ERR_ARG, "efd_hann_convolve: bad arguments (m: a power of two in "
                                  "[2^21, 2^25], >= nf)");
     return hann_pipeline_m(S, stride, nf, rows, info, m, kfp, Y, nullptr, (hipStream_t)stream);
 }
 int efd_hann_loglike_local_partials(int64_t m) {
-    if (m == ((int64_t)1 << 24)) return FC_C16 / FcCols<(1 << 24) / FC_C16>::NCOL;
-    switch (m / FC_C) {
-        case 256: return FC_C / FcCols<256>::NCOL;
-        case 512: return FC_C / FcCols<512>::NCOL;
-        case 1024: return FC_C / FcCols<1024>::NCOL;
-        case 4096: return FC_C / FcCols<4096>::NCOL;
-        default: return 0;
-    }
+    int np = 0;   // the split's column blocks
+    fc_split(m, [&](auto s) { np = decltype(s)::C / decltype(s)::NCOL; });
+    return np;
 }
 int efd_hann_loglike_local(const double* S, int64_t stride, int64_t nf, int32_t rows,
                            const uint64_t* info, int64_t m, const float* kfd, float* Y,
                            const double* dl, const double* wl, int64_t kself, double* out,
                            double* scratch, double* emit, void* stream) {
     const int np = hann_four_step_m(m, nf) ? efd_hann_loglike_local_partials(m) : 0;
-    if (!hann_rows_ok("efd_hann_loglike_local", S, stride, nf, rows) || !info || !kfd || !Y ||
+    if (!hann_rows_ok(S, stride, nf, rows) || !info || !kfd || !Y ||
         !wl || np == 0 || kself < -1 || kself >= nf ||
         (emit ? rows != 1 : (!dl || !out || !scratch || rows > HANN_ROWS_MAX)))
         return fail(EFD_ERR_ARG, "efd_hann_loglike_local: bad arguments (m: a power of two in "
@@ -1428,25 +1403,17 @@ int efd_hann_polarizations(const double* S, const float* Y, const uint64_t* info
 int efd_hann_loglike(const double* S, int64_t stride, const float* Y, const uint64_t* info,
                      int64_t m, int32_t rows, int64_t nf, int64_t k0, const double* d,
                      const double* w, double* out, double* scratch, void* stream) {
-    if (!hann_rows_ok("efd_hann_loglike", S, stride, nf, rows) || !Y || !info || !d || !w ||
+    if (!hann_rows_ok(S, stride, nf, rows) || !Y || !info || !d || !w ||
         !out || !scratch || m < nf || k0 < 0 || k0 >= nf || rows > HANN_ROWS_MAX)
         return fail(EFD_ERR_ARG, "efd_hann_loglike: bad arguments (rows <= 16)");
-    const int64_t nb = nf - k0;
-    const int threads = 256;
-    // chunks: a multiple of 8 (one per XCD in turn), at most EFD_LOGLIKE_SCRATCH per row
-    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH,
-                                          ((nb + threads - 1) / threads + 7) / 8 * 8);
+    const PairShape sh = pair_shape(nf - k0, rows);
     hipStream_t st = (hipStream_t)stream;
-    static_assert(EFD_LOGLIKE_SCRATCH % 8 == 0, "chunks: whole rounds of the 8 XCDs");
-    // two rows a workgroup when the rows pair up (d and w read once for both: 362 -> 318 us,
-    // r05zr; an odd row count takes one row a workgroup)
-    const int rpt = (rows % 2 == 0) ? 2 : 1;
-    hipLaunchKernelGGL(rpt == 2 ? k_hann_loglike_partial<2> : k_hann_loglike_partial<1>,
-                       dim3((unsigned)(np * (rows / rpt))), dim3(threads), 0, st,
-                       (const double2*)S, stride, (const float2*)Y, info, m, nf, k0,
-                       (const double2*)d, w, (int)rows, np, scratch);
+    hipLaunchKernelGGL(sh.rpt == 2 ? k_hann_loglike_partial<2> : k_hann_loglike_partial<1>,
+                       dim3(sh.blocks), dim3(256), 0, st, (const double2*)S, stride,
+                       (const float2*)Y, info, m, nf, k0, (const double2*)d, w, (int)rows, sh.np,
+                       scratch);
     HIP_TRY(hipGetLastError());
-    efdhip::launch_loglike_final(rows, scratch, np, out, st);
+    efdhip::launch_loglike_final(rows, scratch, sh.np, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
@@ -1473,11 +1440,11 @@ int efd_cosw_polarizations(const double* S, const float* Y, const uint64_t* info
     if (cnt == 0) return EFD_OK;
     const int64_t blocks = (cnt + COSW_TILE - 1) / COSW_TILE;
     hipStream_t st = (hipStream_t)stream;
-    switch (nterm - 1) {
-        case 1: cosw_launch_pol<1>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-        case 2: cosw_launch_pol<2>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-        default: cosw_launch_pol<3>(blocks, st, S, Y, info, m, nf, k0, cf, hp, hc); break;
-    }
+    cosw_width(nterm, [&](auto j) {
+        hipLaunchKernelGGL(k_cosw_polarizations<decltype(j)::value>, dim3((unsigned)blocks),
+                           dim3(COSW_TILE), 0, st, (const double2*)S, (const float2*)Y, info, m,
+                           nf, k0, cf, (double2*)hp, (double2*)hc);
+    });
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
@@ -1486,33 +1453,23 @@ int efd_cosw_loglike(const double* S, int64_t stride, const float* Y, const uint
                      int32_t nterm, const double* d, const double* w, double* out,
                      double* scratch, void* stream) {
     CoswCoef cf;
-    if (!hann_rows_ok("efd_cosw_loglike", S, stride, nf, rows) || !Y || !info || !d || !w ||
+    if (!hann_rows_ok(S, stride, nf, rows) || !Y || !info || !d || !w ||
         !out || !scratch || !cosw_coef(a, nterm, nf, cf) || m < nf || k0 < 0 || k0 >= nf ||
         rows > HANN_ROWS_MAX)
         return fail(EFD_ERR_ARG, "efd_cosw_loglike: bad arguments (rows <= 16, 2 <= nterm <= 4, "
                                  "nf >= 2 (nterm - 1) + 1)");
-    const int64_t nb = nf - k0;
-    // efd_hann_loglike's chunks and row grouping
-    const int np = (int)std::min<int64_t>(EFD_LOGLIKE_SCRATCH,
-                                          ((nb + COSW_TILE - 1) / COSW_TILE + 7) / 8 * 8);
+    const PairShape sh = pair_shape(nf - k0, rows);
     hipStream_t st = (hipStream_t)stream;
-    const int rpt = (rows % 2 == 0) ? 2 : 1;
-    switch (nterm - 1) {
-        case 1:
-            cosw_launch_ll<1>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-        case 2:
-            cosw_launch_ll<2>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-        default:
-            cosw_launch_ll<3>(rpt, np, st, S, stride, Y, info, m, rows, nf, k0, cf, d, w,
-                              scratch);
-            break;
-    }
+    cosw_width(nterm, [&](auto j) {
+        constexpr int J = decltype(j)::value;
+        hipLaunchKernelGGL((sh.rpt == 2 ? k_cosw_loglike_partial<J, 2>
+                                        : k_cosw_loglike_partial<J, 1>),
+                           dim3(sh.blocks), dim3(COSW_TILE), 0, st, (const double2*)S, stride,
+                           (const float2*)Y, info, m, nf, k0, cf, (const double2*)d, w, (int)rows,
+                           sh.np, scratch);
+    });
     HIP_TRY(hipGetLastError());
-    efdhip::launch_loglike_final(rows, scratch, np, out, st);
+    efdhip::launch_loglike_final(rows, scratch, sh.np, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

@@ -48,6 +48,12 @@ _TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "LISA_
 _SPLINE = None
 
 
+def _ptr(t):
+    """The device address of t's first element (of its real view when t is complex)."""
+    import torch
+    return torch.view_as_real(t).data_ptr() if t.is_complex() else t.data_ptr()
+
+
 def _spline():
     global _SPLINE
     if _SPLINE is None:
@@ -236,16 +242,15 @@ class HannConvolution:
         S = self._rows(S)
         rows, n = int(S.shape[0]), self.n
         st = torch.cuda.current_stream(S.device).cuda_stream
-        sp = torch.view_as_real(S).data_ptr()
+        sp = _ptr(S)
         m, info, Y = self._forward_setup(S, lib, lanes, support)
-        yp = torch.view_as_real(Y).data_ptr()
+        yp = _ptr(Y)
         if self._four(m):
             kfp = self.kernel_spectrum(m, four=True)
-            _lib.check(lib.efd_hann_convolve(sp, n, n, rows, info.data_ptr(), m,
-                                             torch.view_as_real(kfp).data_ptr(), yp, st),
+            _lib.check(lib.efd_hann_convolve(sp, n, n, rows, _ptr(info), m, _ptr(kfp), yp, st),
                        "efd_hann_convolve", lib)
             return Y, info, m
-        _lib.check(lib.efd_hann_stage(sp, n, n, rows, info.data_ptr(), m, yp, st),
+        _lib.check(lib.efd_hann_stage(sp, n, n, rows, _ptr(info), m, yp, st),
                    "efd_hann_stage", lib)
         plan = self._plans.get((m, rows))
         if plan is None:
@@ -273,19 +278,26 @@ class HannConvolution:
         C = torch.gather(Y, 1, q).to(torch.complex128) * scale[:, None]
         return C[0] if one else C
 
+    # the stencil that reads S and Y: the library's entry points (efd_<STENCIL>_polarizations,
+    # efd_<STENCIL>_loglike) and the arguments they take after k0
+    STENCIL = "hann"
+
+    def _stencil_args(self):
+        return ()
+
     def polarizations_batch(self, S, outs, k0, lib, lanes=None, support=None):
         """polarizations for every row of S ([B][n], contiguous): one transform pair over the
-        rows and one efd_hann_polarizations per row into outs[i] = (hp, hc)."""
+        rows and one efd_<STENCIL>_polarizations per row into outs[i] = (hp, hc)."""
         from . import _lib
         torch = require_gpu()
         S = self._rows(S)
         Y, info, m = self.transform(S, lib, lanes, support)
         st = torch.cuda.current_stream(S.device).cuda_stream
+        name = f"efd_{self.STENCIL}_polarizations"
         for i, (hp, hc) in enumerate(outs):
-            _lib.check(lib.efd_hann_polarizations(
-                torch.view_as_real(S[i]).data_ptr(), torch.view_as_real(Y[i]).data_ptr(),
-                info[i].data_ptr(), m, self.n, k0, torch.view_as_real(hp).data_ptr(),
-                torch.view_as_real(hc).data_ptr(), st), "efd_hann_polarizations", lib)
+            _lib.check(getattr(lib, name)(_ptr(S[i]), _ptr(Y[i]), _ptr(info[i]), m, self.n, k0,
+                                          *self._stencil_args(), _ptr(hp), _ptr(hc), st),
+                       name, lib)
         return outs
 
     def polarizations(self, S, hp, hc, k0, lib):
@@ -309,7 +321,7 @@ class HannConvolution:
         return int((k_hi - k_lo)[live].max())
 
     def loglike_batch(self, S, d, w, k0, out, scratch, lib, lanes=None, support=None):
-        """efd_hann_loglike: the logL of every row's windowed template against d, w
+        """efd_<STENCIL>_loglike: the logL of every row's windowed template against d, w
         (efd_loglike's [2][n - k0] layout) into out (float64 device [rows]); scratch holds
         rows * EFD_LOGLIKE_SCRATCH doubles."""
         from . import _lib
@@ -318,10 +330,10 @@ class HannConvolution:
         rows = int(S.shape[0])
         Y, info, m = self.transform(S, lib, lanes, support)
         st = torch.cuda.current_stream(S.device).cuda_stream
-        _lib.check(lib.efd_hann_loglike(
-            torch.view_as_real(S).data_ptr(), self.n, torch.view_as_real(Y).data_ptr(),
-            info.data_ptr(), m, rows, self.n, k0, torch.view_as_real(d).data_ptr(),
-            w.data_ptr(), out.data_ptr(), scratch.data_ptr(), st), "efd_hann_loglike", lib)
+        name = f"efd_{self.STENCIL}_loglike"
+        _lib.check(getattr(lib, name)(_ptr(S), self.n, _ptr(Y), _ptr(info), m, rows, self.n, k0,
+                                      *self._stencil_args(), _ptr(d), _ptr(w), _ptr(out),
+                                      _ptr(scratch), st), name, lib)
         return out
 
     # local logL data (efd_hann_loglike_local) --------------------------------------------
@@ -369,22 +381,32 @@ class HannConvolution:
         """dl = wl S_w over the grid (and dl[n] = dl[kself]) for one row S: the local data of an
         injection made with this arithmetic (efd_hann_loglike_local's emit), whose logL against
         a template of the same spectrum and transform length is exactly 0."""
-        from . import _lib
-        torch = require_gpu()
         S = self._rows(S)
         if S.shape[0] != 1:
             raise ValueError("local_emit: one row")
+        return self._local(S, lib, lanes, support, None, wl, kself)
+
+    def _local(self, S, lib, lanes, support, dl, wl, kself, out=None, scratch=None):
+        """The efd_hann_loglike_local call on the rows of S: their logL against dl into out
+        (returns True), or with dl None its emit form (returns the new dl). None, with nothing
+        done, when the transform length is not the four-step's."""
+        from . import _lib
+        torch = require_gpu()
         m, info, Y = self._forward_setup(S, lib, lanes, support)
         if not self._four(m):
             return None
-        dl = torch.zeros(self.n + 1, dtype=torch.complex128, device=S.device)
+        if dl is None:
+            done = torch.zeros(self.n + 1, dtype=torch.complex128, device=S.device)
+            tail = (None, _ptr(wl), int(kself), None, None, _ptr(done))
+        else:
+            done = True
+            tail = (_ptr(dl), _ptr(wl), int(kself), _ptr(out), _ptr(scratch), None)
         st = torch.cuda.current_stream(S.device).cuda_stream
         _lib.check(lib.efd_hann_loglike_local(
-            torch.view_as_real(S).data_ptr(), self.n, self.n, 1, info.data_ptr(), m,
-            torch.view_as_real(self.kernel_spectrum(m, four=True, diff=True)).data_ptr(),
-            torch.view_as_real(Y).data_ptr(), None, wl.data_ptr(), int(kself), None, None,
-            torch.view_as_real(dl).data_ptr(), st), "efd_hann_loglike_local", lib)
-        return dl
+            _ptr(S), self.n, self.n, int(S.shape[0]), _ptr(info), m,
+            _ptr(self.kernel_spectrum(m, four=True, diff=True)), _ptr(Y), *tail, st),
+            "efd_hann_loglike_local", lib)
+        return done
 
     def _forward_setup(self, S, lib, lanes, support):
         """efd_hann_extent, the transform length m and the Y buffer for the rows of S."""
@@ -399,9 +421,9 @@ class HannConvolution:
         if lanes is not None:
             if tuple(lanes.shape) != (rows, 2) or lanes.dtype != torch.int32:
                 raise ValueError("lanes: int32 [rows][2]")
-            lp = lanes.data_ptr()
-        _lib.check(lib.efd_hann_extent(torch.view_as_real(S).data_ptr(), n, n, rows, lp,
-                                       info.data_ptr(), st), "efd_hann_extent", lib)
+            lp = _ptr(lanes)
+        _lib.check(lib.efd_hann_extent(_ptr(S), n, n, rows, lp, _ptr(info), st),
+                   "efd_hann_extent", lib)
         if support is None:
             ext = info[:, 1:3].cpu().numpy()          # first (-1: empty row), last + 1
             live = ext[:, 1] > 0
@@ -419,29 +441,25 @@ class HannConvolution:
         (no correction array written or read back); scratch holds rows *
         EFD_HANN_LOCAL_PARTIALS doubles. Returns False (nothing done) when the transform length
         is not the four-step's: the caller takes loglike_batch."""
-        from . import _lib
-        torch = require_gpu()
-        S = self._rows(S)
-        rows = int(S.shape[0])
-        m, info, Y = self._forward_setup(S, lib, lanes, support)
-        if not self._four(m):
-            return False
         dl, wl, kself = local
-        st = torch.cuda.current_stream(S.device).cuda_stream
-        _lib.check(lib.efd_hann_loglike_local(
-            torch.view_as_real(S).data_ptr(), self.n, self.n, rows, info.data_ptr(), m,
-            torch.view_as_real(self.kernel_spectrum(m, four=True, diff=True)).data_ptr(),
-            torch.view_as_real(Y).data_ptr(), torch.view_as_real(dl).data_ptr(), wl.data_ptr(),
-            int(kself), out.data_ptr(), scratch.data_ptr(), None, st),
-            "efd_hann_loglike_local", lib)
-        return True
+        return self._local(self._rows(S), lib, lanes, support, dl, wl, kself, out,
+                           scratch) is not None
+
+    # the window's cosine-sum coefficients a_0..a_J (COSINE_WINDOWS below)
+    coeffs = (0.5, 0.5)
 
     def __call__(self, S):
+        """The first-order form in torch: S_w = a_0 S + sum_j b_j [(S[k+j] + S[k-j]) + j e
+        (C[k+j] - C[k-j])], b_j = (-1)^j a_j / 2 (Hann: 1/2 S - 1/4 (..) - 1/4 e (..))."""
         torch = require_gpu()
         C = self.correction(S)
-        Sp, Sm = torch.roll(S, -1, dims=-1), torch.roll(S, 1, dims=-1)
-        Cd = torch.roll(C, -1, dims=-1) - torch.roll(C, 1, dims=-1)
-        return 0.5 * S - 0.25 * (Sp + Sm) - (0.25 * self.eps) * Cd
+        out = self.coeffs[0] * S
+        for j in range(1, len(self.coeffs)):
+            b = (-1) ** j * 0.5 * self.coeffs[j]
+            out = out + b * (torch.roll(S, -j, dims=-1) + torch.roll(S, j, dims=-1))
+            out = out + (b * j * self.eps) * (torch.roll(C, -j, dims=-1)
+                                              - torch.roll(C, j, dims=-1))
+        return out
 
 
 # scipy.signal.windows' symmetric cosine-sum windows, w[n] = sum_j (-1)^j a_j cos(2 pi j n /
@@ -509,36 +527,10 @@ class CosineWindowConvolution(HannConvolution):
         return (int(n) >= 2 * (len(coeffs) - 1) + 1
                 and 10.0 * cls.q(coeffs) / float(n) ** 2 <= cls.TOL)
 
-    def polarizations_batch(self, S, outs, k0, lib, lanes=None, support=None):
-        """polarizations for every row of S ([B][n], contiguous): one transform pair over the
-        rows and one efd_cosw_polarizations per row into outs[i] = (hp, hc)."""
-        from . import _lib
-        torch = require_gpu()
-        S = self._rows(S)
-        Y, info, m = self.transform(S, lib, lanes, support)
-        st = torch.cuda.current_stream(S.device).cuda_stream
-        for i, (hp, hc) in enumerate(outs):
-            _lib.check(lib.efd_cosw_polarizations(
-                torch.view_as_real(S[i]).data_ptr(), torch.view_as_real(Y[i]).data_ptr(),
-                info[i].data_ptr(), m, self.n, k0, self._a, len(self.coeffs),
-                torch.view_as_real(hp).data_ptr(), torch.view_as_real(hc).data_ptr(), st),
-                "efd_cosw_polarizations", lib)
-        return outs
+    STENCIL = "cosw"
 
-    def loglike_batch(self, S, d, w, k0, out, scratch, lib, lanes=None, support=None):
-        """efd_cosw_loglike: HannConvolution.loglike_batch with this window's stencil."""
-        from . import _lib
-        torch = require_gpu()
-        S = self._rows(S)
-        rows = int(S.shape[0])
-        Y, info, m = self.transform(S, lib, lanes, support)
-        st = torch.cuda.current_stream(S.device).cuda_stream
-        _lib.check(lib.efd_cosw_loglike(
-            torch.view_as_real(S).data_ptr(), self.n, torch.view_as_real(Y).data_ptr(),
-            info.data_ptr(), m, rows, self.n, k0, self._a, len(self.coeffs),
-            torch.view_as_real(d).data_ptr(), w.data_ptr(), out.data_ptr(), scratch.data_ptr(),
-            st), "efd_cosw_loglike", lib)
-        return out
+    def _stencil_args(self):
+        return (self._a, len(self.coeffs))
 
     def local_ok(self, d, w, k0):
         return False
@@ -548,17 +540,6 @@ class CosineWindowConvolution(HannConvolution):
 
     def loglike_local(self, S, local, out, scratch, lib, lanes=None, support=None):
         raise ValueError("the local logL form is the Hann window's only")
-
-    def __call__(self, S):
-        torch = require_gpu()
-        C = self.correction(S)
-        out = self.coeffs[0] * S
-        for j in range(1, len(self.coeffs)):
-            b = (-1) ** j * 0.5 * self.coeffs[j]
-            out = out + b * (torch.roll(S, -j, dims=-1) + torch.roll(S, j, dims=-1))
-            out = out + (b * j * self.eps) * (torch.roll(C, -j, dims=-1)
-                                              - torch.roll(C, j, dims=-1))
-        return out
 
 
 def windowed_spectrum(S, mult):
@@ -997,8 +978,7 @@ class get_fd_waveform_fromTD:
             Z.copy_(torch.fft.fft(Z, dim=-1))
             self.info.update(transform="torch.fft", rows=rows, n=n, plan_work_bytes=None)
             return Z
-        plan(torch.view_as_real(Z).data_ptr(), _hipfft.FORWARD,
-             torch.cuda.current_stream(Z.device).cuda_stream)
+        plan(_ptr(Z), _hipfft.FORWARD, torch.cuda.current_stream(Z.device).cuda_stream)
         self.info.update(transform="hipfft", rows=rows, n=n, plan_work_bytes=plan.work_bytes())
         return Z
 
@@ -1037,9 +1017,8 @@ class get_fd_waveform_fromTD:
             raise ValueError(f"out: contiguous complex128 [{rows}][2][{nb}] on {Z.device}")
         lib = _lib.load()
         _lib.check(lib.efd_td_split(
-            torch.view_as_real(Z).data_ptr(), int(Z.stride(0)), self.num_samples, rows,
-            float(self.dt), None if self._keep is None else self._keep.data_ptr(),
-            torch.view_as_real(out).data_ptr(), 2 * nb,
+            _ptr(Z), int(Z.stride(0)), self.num_samples, rows, float(self.dt),
+            None if self._keep is None else _ptr(self._keep), _ptr(out), 2 * nb,
             torch.cuda.current_stream(Z.device).cuda_stream), "efd_td_split", lib)
 
     def fill(self, out, *params, **kwargs):
@@ -1097,9 +1076,8 @@ class get_fd_waveform_fromTD:
         for g0 in range(0, B, G):
             Z = self._spectra(params[g0:g0 + G], kwargs)
             _lib.check(lib.efd_td_split_loglike(
-                torch.view_as_real(Z).data_ptr(), int(Z.stride(0)), self.num_samples, len(Z),
-                float(self.dt), torch.view_as_real(d).data_ptr(), w.data_ptr(),
-                out[g0:g0 + len(Z)].data_ptr(), scratch.data_ptr(),
+                _ptr(Z), int(Z.stride(0)), self.num_samples, len(Z), float(self.dt), _ptr(d),
+                _ptr(w), _ptr(out[g0:g0 + len(Z)]), _ptr(scratch),
                 torch.cuda.current_stream(Z.device).cuda_stream), "efd_td_split_loglike", lib)
             self.waveform_generator.check_td_batch()
         return out

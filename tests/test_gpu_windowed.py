@@ -277,6 +277,109 @@ def test_hann_loglike_local(n, m):
         assert float(zero[0]) == 0.0
 
 
+def _ptr(t):
+    return torch.view_as_real(t).data_ptr() if t.is_complex() else t.data_ptr()
+
+
+@pytest.mark.parametrize("dk", [0, 7])
+def test_hann_loglike_row_grouping_bitwise(dk):
+    """efd_hann_loglike on four rows in one call (two rows a workgroup) against the first three
+    in another (one row a workgroup), on the same transformed rows (Y held fixed: a batched
+    transform may round a row differently in another batch): the three logL are bitwise the
+    same, so a row's partial depends neither on the row grouping nor on the other rows. Rows of
+    different supports, one scaled by 1e-21 and one all zero; k0 the self-mirror bin n // 2
+    (dk = 0) and seven bins above it."""
+    from emri_frequencydomainwaveforms_amd import _lib
+    from emri_frequencydomainwaveforms_amd.fdutils import HannConvolution
+    lib = _lib.load()
+    n = 200001
+    k0 = n // 2 + dk
+    nb = n - k0
+    rng = np.random.default_rng(11)
+    S = rng.normal(size=(4, n)) + 1j * rng.normal(size=(4, n))
+    S[0, : n // 4] = S[0, 3 * n // 4:] = 0.0
+    S[1, : 2 * n // 5] = S[1, 3 * n // 5:] = 0.0
+    S[1] *= 1e-21
+    S[2] = 0.0
+    S[3, : n // 3] = S[3, 2 * n // 3:] = 0.0
+    St = torch.as_tensor(S, device="cuda")
+    d = torch.as_tensor(rng.normal(size=(2, nb)) + 1j * rng.normal(size=(2, nb)), device="cuda")
+    w = torch.as_tensor(rng.uniform(0.5, 2.0, size=(2, nb)), device="cuda")
+    scr = torch.empty(4 * _lib.EFD_LOGLIKE_SCRATCH, dtype=torch.float64, device="cuda")
+    Y, info, m = HannConvolution(n, St.device).transform(St, lib)
+    outs = []
+    for rows in (4, 3):
+        o = torch.full((rows,), np.nan, dtype=torch.float64, device="cuda")
+        _lib.check(lib.efd_hann_loglike(_ptr(St), n, _ptr(Y), _ptr(info), m, rows, n, k0, _ptr(d),
+                                        _ptr(w), _ptr(o), _ptr(scr), None), "efd_hann_loglike", lib)
+        torch.cuda.synchronize()
+        outs.append(o.cpu().numpy())
+    # (beside this data the 1e-21 row's logL may round to the all-zero row's, the data-only term)
+    assert np.all(np.isfinite(outs[0])) and len({outs[0][0], outs[0][2], outs[0][3]}) == 3
+    assert outs[0][:3].tobytes() == outs[1].tobytes()
+
+
+def test_hann_local_rows_independent_bitwise():
+    """efd_hann_loglike_local on three rows at once and on each row alone, every call on the
+    same transform length (m = 2^21, chosen by the support given): a row's logL has the same
+    bytes, so its partials depend on its row alone (rows of different supports, one all
+    zero)."""
+    from emri_frequencydomainwaveforms_amd import _lib
+    from emri_frequencydomainwaveforms_amd.fdutils import HannConvolution
+    lib = _lib.load()
+    n = 1000001
+    k0 = (n - 1) // 2
+    nb = n - k0
+    rng = np.random.default_rng(5)
+    S = torch.zeros((3, n), dtype=torch.complex128, device="cuda")
+    for r, (a, b) in enumerate([(0.45, 0.55), (0.43, 0.56)]):
+        lo_, hi_ = int(a * n), int(b * n)
+        S[r, lo_:hi_] = torch.as_tensor((rng.normal(size=hi_ - lo_)
+                                         + 1j * rng.normal(size=hi_ - lo_)) * 1e-21, device="cuda")
+    d = torch.as_tensor((rng.normal(size=(2, nb)) + 1j * rng.normal(size=(2, nb))) * 1e-20,
+                        device="cuda")
+    w1 = rng.uniform(0.5, 2.0, size=nb)
+    w = torch.as_tensor(np.stack([w1, w1]), device="cuda")
+    hcv = HannConvolution(n, S.device)
+    support = int(0.14 * n)
+    assert hcv.size_for(n, support) == 1 << 21
+    local = hcv.local_data(d, w, k0)
+    scr = torch.empty(3 * _lib.EFD_HANN_LOCAL_PARTIALS, dtype=torch.float64, device="cuda")
+    out = torch.full((3,), np.nan, dtype=torch.float64, device="cuda")
+    assert hcv.loglike_local(S, local, out, scr, lib, support=support)
+    together = out.cpu().numpy()
+    assert np.all(np.isfinite(together)) and len(set(together.tolist())) == 3
+    for r in range(3):
+        one = torch.full((1,), np.nan, dtype=torch.float64, device="cuda")
+        assert hcv.loglike_local(S[r:r + 1].contiguous(), local, one, scr, lib, support=support)
+        assert one.cpu().numpy().tobytes() == together[r:r + 1].tobytes()
+
+
+def test_hann_call_is_cosine_sum_form():
+    """HannConvolution's windowed spectrum in torch is the general cosine-sum expression with
+    the coefficients (1/2, 1/2): equal, element for element, to the three-term Hann formula
+    written out here from correction(S) (b = -1/4: every term is the Hann term with its sign in
+    the coefficient, x + (-y) = x - y and (-1/4 . 1) e = -(1/4 e) exactly) and to
+    CosineWindowConvolution with those coefficients."""
+    from emri_frequencydomainwaveforms_amd.fdutils import (CosineWindowConvolution,
+                                                           HannConvolution)
+    n = 1001
+    rng = np.random.default_rng(n)
+    S = rng.normal(size=(2, n)) + 1j * rng.normal(size=(2, n))
+    S[:, : n // 5] = 0.0
+    S[1] *= 1e-21
+    St = torch.as_tensor(S, device="cuda")
+    hcv = HannConvolution(n, St.device)
+    got = hcv(St)
+    C = hcv.correction(St)
+    Sp, Sm = torch.roll(St, -1, dims=-1), torch.roll(St, 1, dims=-1)
+    Cd = torch.roll(C, -1, dims=-1) - torch.roll(C, 1, dims=-1)
+    written = 0.5 * St - 0.25 * (Sp + Sm) - (0.25 * hcv.eps) * Cd
+    general = CosineWindowConvolution(n, St.device, (0.5, 0.5))(St)
+    assert float(got.abs().max()) > 0.0
+    assert torch.equal(got, written) and torch.equal(got, general)
+
+
 @pytest.mark.parametrize("n,support,rows,m", [
     (1000001, (0.4, 0.9), 3, 1 << 21), (2000001, (0.3, 0.9), 2, 1 << 22),
     (4000001, (0.3, 0.9), 2, 1 << 23), (12623261, (0.43, 0.57), 2, 1 << 24),
