@@ -5,8 +5,9 @@ source is compiled to an object under build/, all of them at once, and one link 
                          -ffp-contract=off each (the host twins, efd_*_cpu: the mode sum's and the
                          reductions'; AVX-512 is on both this container's Sapphire Rapids and the
                          GPU box's EPYC 9575F)
-  csrc/emrifd_host.cpp -> g++ -O3 -fopenmp: the host upstream stand-ins (trajectory, p0 solve) in C++
-  and the walker batches' staging
+  csrc/emrifd_host.cpp -> g++ -O3 -fopenmp: the host upstream stand-ins (trajectory, p0 solve) in C++,
+  the walker batches' staging and the PSD table of the noise-weighted mode selection
+  (csrc/emrifd_psd.h: its NaN and sign guards need a unit built without -ffast-math)
   csrc/emrifd_modes.cpp -> g++ -O3 -ffast-math -fopenmp (libmvec; knots over threads for one-at-a-time
                           calls): amplitudes, mode selection
   csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode

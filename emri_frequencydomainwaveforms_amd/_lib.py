@@ -102,6 +102,10 @@ EXPORTED_SYMBOLS = (
     "efd_host_set_threads",
     "efd_modes_workspace_bytes",
     "efd_modes_select_batch",
+    "efd_psd_eval",
+    "efd_psd_eval_cpu",
+    "efd_host_modes_weighted",
+    "efd_modes_select_batch_weighted",
 )
 
 
@@ -202,6 +206,25 @@ class ModesWalker(ctypes.Structure):
         ("ylm_m_out", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p),
         ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class PsdTable(ctypes.Structure):
+    """Mirror of `efd_psd_table` (include/emrifd.h)."""
+
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("c", ctypes.c_void_p),
+        ("n", ctypes.c_int32),
+    ]
+
+
+class ModesWeight(ctypes.Structure):
+    """Mirror of `efd_modes_weight` (include/emrifd.h)."""
+
+    _fields_ = [
+        ("f_phi", ctypes.c_void_p),
+        ("f_r", ctypes.c_void_p),
     ]
 
 
@@ -403,6 +426,19 @@ def load(path=None):
         lib.efd_modes_select_batch.restype = ctypes.c_int
         lib.efd_modes_select_batch.argtypes = [ctypes.POINTER(ModesTable),
                                                ctypes.POINTER(ModesWalker), i32, vp]
+    if hasattr(lib, "efd_psd_eval"):   # the noise-weighted mode selection
+        for name in ("efd_psd_eval", "efd_psd_eval_cpu"):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = [ctypes.POINTER(PsdTable), vp, i64, vp, vp]
+        lib.efd_host_modes_weighted.restype = ctypes.c_int
+        lib.efd_host_modes_weighted.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, dbl,
+                                                vp, vp, ctypes.POINTER(PsdTable), vp,
+                                                ctypes.POINTER(i32), vp, i64]
+        lib.efd_modes_select_batch_weighted.restype = ctypes.c_int
+        lib.efd_modes_select_batch_weighted.argtypes = [ctypes.POINTER(ModesTable),
+                                                        ctypes.POINTER(ModesWalker),
+                                                        ctypes.POINTER(ModesWeight),
+                                                        ctypes.POINTER(PsdTable), i32, vp]
     _ = dbl
     if path is None:
         _lib = lib

@@ -17,6 +17,12 @@ the union over time.
 The same model and selection also run on the device for batched callers
 (csrc/emrifd_modes_device.inc: efd_modes_select_batch): `device_select`,
 `SyntheticTeukolskyAmplitude.select_batch_device` and `ModeSelector(m0mask, use_gpu=True)`.
+
+Noise-weighted selection (FEW's `ModeSelector(sensitivity_fn=...)`, as recalled): both branch
+powers of mode k at knot i are divided by the PSD at |m_k f_phi[i] + n_k f_r[i]| before the cut,
+so eps is a fraction of noise-weighted power. numpy defines it (`ModeSelector.__call__`); the
+native routes (efd_host_modes_weighted, efd_modes_select_batch_weighted) evaluate the PSD from a
+piecewise-cubic table (`psd_table`, `PsdTable`).
 """
 
 import ctypes
@@ -46,7 +52,63 @@ def _f64(x):
     return torch.view_as_real(x).reshape(-1) if x.is_complex() else x
 
 
-def device_select(table, nmodes, walkers, device, stream=None, state=None, prof=None):
+class PsdTable:
+    """A PSD as a piecewise cubic in scipy's PPoly layout (x [n] ascending, c [4][n - 1]) for
+    the native selections: `host` is the efd_psd_table over this object's arrays, `device(dev)`
+    the one over their copies on a device (uploaded once per table and device)."""
+
+    def __init__(self, x, c):
+        from . import _lib
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        c = np.asarray(c, dtype=np.float64)
+        if x.ndim != 1 or c.ndim != 2 or not 1 <= c.shape[0] <= 4 or c.shape[1] != len(x) - 1:
+            raise ValueError("PsdTable: x [n] and c [k <= 4][n - 1] (scipy's PPoly layout)")
+        if not 2 <= len(x) <= 4096 or not np.all(np.diff(x) > 0):
+            raise ValueError("PsdTable: 2 <= n <= 4096 breakpoints, strictly ascending")
+        # a lower order is a cubic with zero leading coefficients
+        self.x = x
+        self.c = np.ascontiguousarray(np.concatenate([np.zeros((4 - c.shape[0], c.shape[1])), c]))
+        self.host = _lib.PsdTable(self.x.ctypes.data, self.c.ctypes.data, len(x))
+        self._dev = {}
+
+    def device(self, device):
+        import torch
+
+        from . import _lib
+        key = (device.type, device.index)
+        if key not in self._dev:
+            t = [torch.from_numpy(a).to(device) for a in (self.x, self.c)]
+            torch.cuda.current_stream(device).synchronize()
+            self._dev[key] = (_lib.PsdTable(t[0].data_ptr(), t[1].data_ptr(), len(self.x)), t)
+        return self._dev[key][0]
+
+    def ppoly(self):
+        from scipy.interpolate import PPoly
+        return PPoly(self.c, self.x, extrapolate=True)
+
+
+def psd_table(sensitivity_fn):
+    """The PsdTable of a sensitivity function the native selections can evaluate:
+    fdutils.get_sensitivity (its module spline) or any object with PPoly-shaped .x and .c
+    (scipy's CubicSpline, PPoly); None for other callables."""
+    from . import fdutils
+    if sensitivity_fn is fdutils.get_sensitivity:
+        sensitivity_fn = fdutils._spline()
+    x, c = getattr(sensitivity_fn, "x", None), getattr(sensitivity_fn, "c", None)
+    if x is None or c is None:
+        return None
+    try:
+        return PsdTable(x, c)
+    except (ValueError, TypeError):
+        return None
+
+
+NO_TABLE = ("the sensitivity_fn has no piecewise-cubic table the device can evaluate: pass "
+            "fdutils.get_sensitivity, or a scipy.interpolate.CubicSpline / PPoly of the PSD "
+            "(e.g. CubicSpline(f, sensitivity_fn(f)))")
+
+
+def device_select(table, nmodes, walkers, device, stream=None, state=None, prof=None, psd=None):
     """efd_modes_select_batch for 1..EFD_BATCH_MAX walkers on `stream` (a torch stream; default
     the current one), then one efd_download of every walker's nkeep, status and keep and one
     stream synchronisation (the mode sum's K is a host argument).
@@ -55,7 +117,9 @@ def device_select(table, nmodes, walkers, device, stream=None, state=None, prof=
     device), ylm_p, ylm_m (float64 views of complex [nmodes]), eps, include_minus_m, teuk
     (float64 view of complex [nt][nmodes], or None: the stand-in model) and want_amp. state: a
     dict the caller keeps per stream (the pinned download buffer lives there). prof: a pair of
-    torch timing events recorded around efd_modes_select_batch's launches alone.
+    torch timing events recorded around efd_modes_select_batch's launches alone. psd: a PsdTable;
+    then the call is efd_modes_select_batch_weighted, and the walkers that carry f_phi and f_r
+    (float64 [nt] on the device, Hz) are selected on noise-weighted power.
 
     Returns one dict per walker: K, keep (device int32 [K]), keep_host (numpy int32 [K]), amp
     (float64 view of complex [nt][K], or None), m, n (int32 [K]), ylm_p, ylm_m (float64 [2 K]):
@@ -112,10 +176,21 @@ def device_select(table, nmodes, walkers, device, stream=None, state=None, prof=
         if w.get("want_amp", True):
             a.amp, a.amp_cap = base + offs_amp[i], nt * nmodes
     st = strm.cuda_stream
+    if psd is not None:
+        wts = (_lib.ModesWeight * n)()
+        for i, w in enumerate(walkers):
+            if w.get("f_phi") is not None:
+                wts[i].f_phi, wts[i].f_r = w["f_phi"].data_ptr(), w["f_r"].data_ptr()
+        dpsd = psd.device(device)
     if prof is not None:   # (begin, end) torch events around the three launches alone
         prof[0].record(strm)
-    _lib.check(lib.efd_modes_select_batch(ctypes.byref(table), ws, n, st),
-               "efd_modes_select_batch", lib)
+    if psd is not None:
+        _lib.check(lib.efd_modes_select_batch_weighted(ctypes.byref(table), ws, wts,
+                                                       ctypes.byref(dpsd), n, st),
+                   "efd_modes_select_batch_weighted", lib)
+    else:
+        _lib.check(lib.efd_modes_select_batch(ctypes.byref(table), ws, n, st),
+                   "efd_modes_select_batch", lib)
     if prof is not None:
         prof[1].record(strm)
     hb = state.get("ints")
@@ -218,7 +293,8 @@ class SyntheticTeukolskyAmplitude:
         return cache[key]
 
     def select_batch_device(self, p_list, e_list, ylms_list, eps, include_minus_m=True,
-                            device=None, stream=None, state=None, want_amp=True, prof=None):
+                            device=None, stream=None, state=None, want_amp=True, prof=None,
+                            f_phi_list=None, f_r_list=None, psd=None):
         """ModeSelector(eps) and the kept modes' amplitudes of several walkers on the device
         (efd_modes_select_batch, the stand-in model evaluated in the kernels): select() without
         the host. p_list, e_list: each walker's knots (float64 [nt], device tensors or numpy);
@@ -227,7 +303,10 @@ class SyntheticTeukolskyAmplitude:
 
         Returns one (keep, K, views) per walker: keep the kept indices (device int32 [K]), views
         a dict of amp, m, n, ylm_p, ylm_m (and keep_host, nt), ready to be
-        summation.DeviceInputs fields. prof: device_select's event pair."""
+        summation.DeviceInputs fields. prof: device_select's event pair.
+
+        psd (a PsdTable) with f_phi_list, f_r_list (each walker's knot frequencies in Hz, as p;
+        an entry None leaves that walker unweighted): the noise-weighted selection."""
         import torch
         dev = device or torch.device("cuda", torch.cuda.current_device())
         table, _ = self.device_table(dev)
@@ -253,17 +332,32 @@ class SyntheticTeukolskyAmplitude:
             walkers.append(dict(p=dev_t(p_list[i], np.float64), e=dev_t(e_list[i], np.float64),
                                 ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=float(eps[i]),
                                 include_minus_m=include_minus_m, teuk=None, want_amp=want_amp))
-        res = device_select(table, K, walkers, dev, strm, state, prof)
+            if psd is not None and f_phi_list is not None and f_phi_list[i] is not None:
+                walkers[-1].update(f_phi=dev_t(f_phi_list[i], np.float64),
+                                   f_r=dev_t(f_r_list[i], np.float64))
+        res = device_select(table, K, walkers, dev, strm, state, prof, psd=psd)
         return [(r["keep"], r["K"], r) for r in res]
 
-    def select(self, p, e, ylms, eps, lib=None):
+    def select(self, p, e, ylms, eps, lib=None, f_phi=None, f_r=None, psd=None):
         """(keep, teuk): ModeSelector(eps) over this model's modes and the kept modes' complex
         amplitudes [N_t][K], in one native call (csrc/emrifd_host.cpp: efd_host_modes) when the
         library is available, else through __call__ + ModeSelector (numpy). ylms: the GetYlms
-        output [Y_lm..., (-1)^l Y_l-m...] over the whole mode list."""
-        if lib is None or not hasattr(lib, "efd_host_modes"):
+        output [Y_lm..., (-1)^l Y_l-m...] over the whole mode list.
+
+        psd (a PsdTable) with f_phi, f_r (the knot frequencies in Hz): the noise-weighted
+        selection (efd_host_modes_weighted); the kept set may then be empty."""
+        weighted = psd is not None
+        if weighted and (f_phi is None or f_r is None):
+            raise ValueError("the noise-weighted selection needs f_phi and f_r")
+        if lib is None or not hasattr(lib, "efd_host_modes_weighted" if weighted
+                                      else "efd_host_modes"):
             A = self(p, e)
-            keep = ModeSelector(self.m0mask)(A, ylms, None, eps=eps)
+            if weighted:
+                keep = ModeSelector(self.m0mask, sensitivity_fn=psd.ppoly())(
+                    A, ylms, (self.l_arr, self.m_arr, self.n_arr), eps=eps,
+                    mode_freqs=(f_phi, f_r))
+            else:
+                keep = ModeSelector(self.m0mask)(A, ylms, None, eps=eps)
             return keep, np.ascontiguousarray(A[:, keep])
         p = np.ascontiguousarray(p, dtype=np.float64)
         e = np.ascontiguousarray(e, dtype=np.float64)
@@ -274,13 +368,22 @@ class SyntheticTeukolskyAmplitude:
         nkeep = ctypes.c_int32(0)
         nt = len(p)
         cap = 2 * nt * K   # np.empty: untouched pages cost nothing
+        if weighted:
+            f_phi = np.ascontiguousarray(f_phi, dtype=np.float64)
+            f_r = np.ascontiguousarray(f_r, dtype=np.float64)
+            if f_phi.shape != (nt,) or f_r.shape != (nt,):
+                raise ValueError("f_phi and f_r must hold one value per knot")
         for _ in range(2):
             teuk = np.empty(cap // 2, dtype=np.complex128)
-            rc = lib.efd_host_modes(p.ctypes.data, e.ctypes.data, nt, self.l_arr.ctypes.data,
-                                    self.m_arr.ctypes.data, self.n_arr.ctypes.data,
-                                    self._phase0.ctypes.data, self._jitter.ctypes.data, K,
-                                    yp.ctypes.data, ym.ctypes.data, float(eps), keep.ctypes.data,
-                                    ctypes.byref(nkeep), teuk.ctypes.data, cap)
+            head = (p.ctypes.data, e.ctypes.data, nt, self.l_arr.ctypes.data,
+                    self.m_arr.ctypes.data, self.n_arr.ctypes.data, self._phase0.ctypes.data,
+                    self._jitter.ctypes.data, K, yp.ctypes.data, ym.ctypes.data, float(eps))
+            tail = (keep.ctypes.data, ctypes.byref(nkeep), teuk.ctypes.data, cap)
+            if weighted:
+                rc = lib.efd_host_modes_weighted(*head, f_phi.ctypes.data, f_r.ctypes.data,
+                                                 ctypes.byref(psd.host), *tail)
+            else:
+                rc = lib.efd_host_modes(*head, *tail)
             if rc == 0:
                 k = nkeep.value
                 return keep[:k].astype(np.int64), teuk[:nt * k].reshape(nt, k)
@@ -295,17 +398,39 @@ RomanAmplitude = SyntheticTeukolskyAmplitude
 
 
 class ModeSelector:
-    """Keep the modes carrying (1 - eps) of the power (few.utils.modeselector.ModeSelector)."""
+    """Keep the modes carrying (1 - eps) of the power (few.utils.modeselector.ModeSelector).
 
-    def __init__(self, m0mask, use_gpu=False):
+    sensitivity_fn: a PSD S(f) (array in, array out). The branch powers of mode k at knot i are
+    then divided by S(|m_k f_phi[i] + n_k f_r[i]|) before the cut (weight 0 where S is not
+    finite or not > 0), so eps is a fraction of noise-weighted power."""
+
+    def __init__(self, m0mask, sensitivity_fn=None, use_gpu=False):
         self.m0mask = np.asarray(m0mask, dtype=bool)
         self.num_m_1_p = len(self.m0mask)
         self.use_gpu = bool(use_gpu)
+        self.sensitivity_fn = sensitivity_fn
+        # what the native routes evaluate (None: only numpy can call sensitivity_fn)
+        self.psd_table = psd_table(sensitivity_fn) if sensitivity_fn is not None else None
         self._table = {}
 
-    def _device_call(self, teuk_modes, ylms, eps):
+    @staticmethod
+    def _frequencies(fund_freq_args, mode_freqs):
+        """(f_phi, f_r) in Hz at the knots, from mode_freqs or FEW's fund_freq_args."""
+        if mode_freqs is not None:
+            return mode_freqs
+        if fund_freq_args is None:
+            raise ValueError("the noise-weighted selection needs mode_freqs=(f_phi, f_r) or "
+                             "fund_freq_args=(M, a, p, e, x)")
+        from .constants import MTSUN_SI
+        from .frequencies import get_fundamental_frequencies
+        M, a, p, e, x = fund_freq_args
+        om_phi, _, om_r = get_fundamental_frequencies(a, p, e, x)
+        return om_phi / (2.0 * np.pi * M * MTSUN_SI), om_r / (2.0 * np.pi * M * MTSUN_SI)
+
+    def _device_call(self, teuk_modes, ylms, eps, modeinds=None, freqs=None):
         """The selection on the device (efd_modes_select_batch with the amplitudes given):
-        complex128 device tensors in, the kept indices out as a device int32 tensor."""
+        complex128 device tensors in, the kept indices out as a device int32 tensor. freqs:
+        (f_phi, f_r) of the noise-weighted selection (device tensors or numpy)."""
         import torch
 
         from . import _lib
@@ -314,37 +439,84 @@ class ModeSelector:
         if K != len(self.m0mask) or ylms.numel() != 2 * K:
             raise ValueError("teuk_modes [N_t, K] and ylms [2 K] must match m0mask")
         key = (dev.type, dev.index)
+        if freqs is not None:
+            # the weights need the modes' own m and n
+            mh = np.ascontiguousarray(modeinds[1], dtype=np.int32)
+            nh = np.ascontiguousarray(modeinds[2], dtype=np.int32)
+            if mh.shape != (K,) or nh.shape != (K,) or not np.array_equal(mh != 0, self.m0mask):
+                raise ValueError("modeinds (l, m, n) must hold [K] arrays with m != 0 as m0mask")
+            key = key + (mh.tobytes(), nh.tobytes())
         if key not in self._table:
             # the selection reads m != 0 only; l, n, phase0 and jitter belong to the stand-in
             # model, which a call with the amplitudes given never evaluates
-            m = torch.from_numpy(self.m0mask.astype(np.int32)).to(dev)
+            m = torch.from_numpy(self.m0mask.astype(np.int32) if freqs is None else mh).to(dev)
             zi = torch.zeros(K, dtype=torch.int32, device=dev)
+            nn = zi if freqs is None else torch.from_numpy(nh).to(dev)
             zd = torch.zeros(K, dtype=torch.float64, device=dev)
-            self._table[key] = (_lib.ModesTable(zi.data_ptr(), m.data_ptr(), zi.data_ptr(),
-                                                zd.data_ptr(), zd.data_ptr(), K), (m, zi, zd))
-        table, (_, _, zd) = self._table[key]
+            self._table[key] = (_lib.ModesTable(zi.data_ptr(), m.data_ptr(), nn.data_ptr(),
+                                                zd.data_ptr(), zd.data_ptr(), K), (m, zi, zd, nn))
+        table = self._table[key][0]
         y = _f64(ylms.to(torch.complex128).contiguous())
         pe = torch.ones(nt, dtype=torch.float64, device=dev)   # unused with teuk given
         w = dict(p=pe, e=pe, ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=float(eps),
                  teuk=_f64(teuk_modes.to(torch.complex128).contiguous()), want_amp=False)
-        return device_select(table, K, [w], dev)[0]["keep"].clone()
+        if freqs is not None:
+            f = [torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x,
+                                 dtype=torch.float64, device=dev).contiguous() for x in freqs]
+            if f[0].shape != (nt,) or f[1].shape != (nt,):
+                raise ValueError("f_phi and f_r must hold one value per knot")
+            w.update(f_phi=f[0], f_r=f[1])
+        return device_select(table, K, [w], dev, psd=self.psd_table if freqs is not None
+                             else None)[0]["keep"].clone()
 
-    def __call__(self, teuk_modes, ylms, modeinds, eps=1e-5):
+    def __call__(self, teuk_modes, ylms, modeinds, fund_freq_args=None, eps=1e-5,
+                 mode_freqs=None):
         """teuk_modes [N_t, K]; ylms [K + K] (+m then partner); returns kept mode indices (with
-        use_gpu: device tensors in, a device int32 tensor out)."""
+        use_gpu: device tensors in, a device int32 tensor out).
+
+        With a sensitivity_fn: modeinds = (l, m, n) arrays [K] are required, and the knot
+        frequencies come from mode_freqs=(f_phi, f_r) (Hz, [N_t] each) or from FEW's
+        fund_freq_args=(M, a, p, e, x). A knot whose weighted total is 0 or not finite keeps
+        nothing, so the result can be empty."""
+        weighted = self.sensitivity_fn is not None
+        if weighted:
+            if modeinds is None:
+                raise ValueError("the noise-weighted selection needs modeinds=(l, m, n)")
+            f_phi, f_r = self._frequencies(fund_freq_args, mode_freqs)
         if self.use_gpu:
-            return self._device_call(teuk_modes, ylms, eps)
+            if weighted and self.psd_table is None:
+                raise ValueError("ModeSelector(use_gpu=True): " + NO_TABLE)
+            return self._device_call(teuk_modes, ylms, eps, modeinds,
+                                     (f_phi, f_r) if weighted else None)
         K = teuk_modes.shape[1]
         ylm_p, ylm_m = ylms[:K], ylms[K:]
         # m = 0 modes have no separate partner branch (their +-n mirrors are separate modes)
         partner = np.conj(teuk_modes[:, self.m0mask]) * ylm_m[self.m0mask][None, :]
         power = np.abs(np.concatenate([teuk_modes * ylm_p[None, :], partner], axis=1)) ** 2
+        if weighted:
+            m = np.asarray(modeinds[1], dtype=np.float64)
+            n = np.asarray(modeinds[2], dtype=np.float64)
+            f_phi = np.asarray(f_phi, dtype=np.float64)
+            f_r = np.asarray(f_r, dtype=np.float64)
+            if m.shape != (K,) or n.shape != (K,) or f_phi.shape != power.shape[:1] \
+                    or f_r.shape != power.shape[:1]:
+                raise ValueError("modeinds [K] and mode_freqs [N_t] must match teuk_modes")
+            F = np.abs(m[None, :] * f_phi[:, None] + n[None, :] * f_r[:, None])
+            S = np.asarray(self.sensitivity_fn(F), dtype=np.float64)
+            ok = np.isfinite(S) & (S > 0.0)
+            W = np.where(ok, 1.0 / np.where(ok, S, 1.0), 0.0)
+            # the partner's frequency is -F: one weight serves both branches of a mode
+            power = power * np.concatenate([W, W[:, self.m0mask]], axis=1)
         partner_idx = np.nonzero(self.m0mask)[0]
         inds_sort = np.argsort(power, axis=1)[:, ::-1]
         power = np.take_along_axis(power, inds_sort, axis=1)
         cumsum = np.cumsum(power, axis=1)
         keep = np.ones(cumsum.shape, dtype=bool)
         keep[:, 1:] = cumsum[:, :-1] < cumsum[:, -1][:, None] * (1.0 - eps)
+        if weighted:
+            # nothing can be ranked at a knot whose total is 0 or not finite: it keeps nothing
+            total = cumsum[:, -1]
+            keep[~(np.isfinite(total) & (total > 0.0)), :] = False
         picked = inds_sort[keep]
         # fold partner picks back onto their +m mode (no m != 0 mode: no partner to fold)
         if partner_idx.size:

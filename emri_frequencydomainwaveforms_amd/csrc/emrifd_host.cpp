@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/emrifd.h"
+#include "emrifd_psd.h"
 
 namespace efdhost {
 
@@ -247,9 +248,49 @@ int integrate(double p0, double e0, double pp0, double pr0, double q, double tau
     return (int)ts.size();
 }
 
+// -- the PSD table of the noise-weighted mode selection (emrifd_psd.h; this unit is built without
+// -ffast-math and with -ffp-contract=off: the guards below hold and every operation rounds on
+// its own, as in the device form, emrifd_modes_device.inc: psd_eval_dev)
+int psd_check(const efd_psd_table* psd) {
+    if (!psd || !psd->x || !psd->c || psd->n < 2 || psd->n > 4096) return EFD_ERR_ARG;
+    for (int i = 1; i < psd->n; ++i)
+        if (!(psd->x[i] > psd->x[i - 1])) return EFD_ERR_ARG;
+    return EFD_OK;
+}
+
+double psd_eval(const efd_psd_table& psd, double f) {
+    const int n = psd.n;
+    // #{j : x[j] <= f}; a NaN compares false everywhere and lands on the last piece, as NaN
+    const int cnt = (int)(std::upper_bound(psd.x, psd.x + n, f) - psd.x);
+    const int i = std::min(std::max(cnt - 1, 0), n - 2);
+    const double s = f - psd.x[i];
+    const double* c = psd.c + i;
+    const int st = n - 1;
+    return ((c[0] * s + c[st]) * s + c[2 * st]) * s + c[3 * st];
+}
+
+void psd_weights(const efd_psd_table& psd, double f_phi, double f_r, const int32_t* m,
+                 const int32_t* n, int nm, double* w) {
+    for (int k = 0; k < nm; ++k) {
+        const double F = std::fabs((double)m[k] * f_phi + (double)n[k] * f_r);
+        const double S = psd_eval(psd, F);
+        w[k] = (std::isfinite(S) && S > 0.0) ? 1.0 / S : 0.0;
+    }
+}
+
+bool psd_total_ok(double total) { return std::isfinite(total) && total > 0.0; }
+
 }  // namespace efdhost
 
 extern "C" {
+
+int efd_psd_eval_cpu(const efd_psd_table* psd, const double* f, int64_t nf, double* out,
+                     void* /*stream*/) {
+    if (efdhost::psd_check(psd) != EFD_OK || nf < 0 || (nf > 0 && (!f || !out)))
+        return EFD_ERR_ARG;
+    for (int64_t j = 0; j < nf; ++j) out[j] = efdhost::psd_eval(*psd, f[j]);
+    return EFD_OK;
+}
 
 int efd_host_trajectory(double M, double mu, double p0, double e0, double Phi_phi0, double Phi_r0,
                         double T, double rtol, double atol, int32_t max_len, double* t, double* p,

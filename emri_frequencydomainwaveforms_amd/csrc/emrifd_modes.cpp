@@ -14,6 +14,11 @@
 //                                (few.utils.modeselector as recalled, notebook :125-127)
 // The selection bins the candidate powers by their top 16 bits instead of sorting all ~7,700 per
 // knot.
+//   ModeSelector(sensitivity_fn) efd_host_modes_weighted: both branch powers of mode k at knot i
+//                                times 1 / S(|m_k f_phi[i] + n_k f_r[i]|) before the cut (FEW's
+//                                noise-weighted selection as recalled). The PSD table and every
+//                                NaN / sign guard are emrifd_host.cpp's (emrifd_psd.h): this unit's
+//                                -ffast-math makes isnan / isfinite unreliable here.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -23,6 +28,7 @@
 #include <omp.h>
 
 #include "../../include/emrifd.h"
+#include "emrifd_psd.h"
 
 namespace {
 constexpr double LN10 = 2.302585092994045684017991454684364208;
@@ -51,14 +57,19 @@ extern "C" int efd_host_set_threads(int32_t n) {
     return EFD_OK;
 }
 
-extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, const int32_t* l,
-                              const int32_t* m, const int32_t* n, const double* phase0,
-                              const double* jitter, int32_t nmodes, const double* ylm_p,
-                              const double* ylm_m, double eps, int32_t* keep, int32_t* nkeep,
-                              double* teuk, int64_t teuk_cap) {
+namespace {
+// efd_host_modes (WT = false) and efd_host_modes_weighted (WT = true: the branch powers of mode k
+// at knot i times 1 / S(|m_k f_phi[i] + n_k f_r[i]|), emrifd_psd.h) share this body
+template <bool WT>
+int host_modes(const double* p, const double* e, int32_t nt, const int32_t* l, const int32_t* m,
+               const int32_t* n, const double* phase0, const double* jitter, int32_t nmodes,
+               const double* ylm_p, const double* ylm_m, double eps, const double* f_phi,
+               const double* f_r, const efd_psd_table* psd, int32_t* keep, int32_t* nkeep,
+               double* teuk, int64_t teuk_cap) {
     if (!p || !e || !l || !m || !n || !phase0 || !jitter || !ylm_p || !ylm_m || !keep ||
         !nkeep || nt < 1 || nmodes < 1)
         return EFD_ERR_ARG;
+    if (WT && (!f_phi || !f_r || efdhost::psd_check(psd) != EFD_OK)) return EFD_ERR_ARG;
     const int nm = nmodes;
     std::vector<double> c1(nm), dn(nm), dm(nm), hl(nm), yp2(nm), ym2(nm);
     std::vector<int32_t> partner_of;   // power index nm + j -> mode (the -m partners)
@@ -79,7 +90,7 @@ extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, cons
 #pragma omp parallel num_threads(nth) if (nth > 1)
     {
     std::vector<unsigned char> kept_l(nm, 0);
-    std::vector<double> mag(nm), pw(np_), hs;
+    std::vector<double> mag(nm), pw(np_), hs, wgt(WT ? nm : 0);
     std::vector<int32_t> cand(np_), idx(np_), cut(np_), hc;
     std::vector<uint16_t> key(np_);
 #pragma omp for schedule(static)
@@ -91,6 +102,11 @@ extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, cons
             const int k = partner_of[j];
             pw[nm + j] = mag[k] * mag[k] * ym2[k];
         }
+        if (WT) {   // one weight per (knot, mode) serves both branches
+            efdhost::psd_weights(*psd, f_phi[i], f_r[i], m, n, nm, wgt.data());
+            for (int k = 0; k < nm; ++k) pw[k] *= wgt[k];
+            for (size_t j = 0; j < partner_of.size(); ++j) pw[nm + j] *= wgt[partner_of[j]];
+        }
         // keep the largest while the sum before them is < (1 - eps) total: the kept set is the
         // top-c, c = min{c : sum of the top c >= threshold}. The c-th largest exceeds
         // eps total / np (the bottom np - c + 1 sum to more than eps total), so only the powers
@@ -100,6 +116,9 @@ extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, cons
         // whole, and only that bin is sorted. (Round 4 binned every power by its exponent:
         // 2.4x the time, the histogram's read-modify-write chains and the crossing bin's sort.)
         for (int k = 0; k < np_; ++k) total += pw[k];
+        // weighted only: nothing can be ranked at a knot whose total is 0 or not finite, so it
+        // keeps nothing (the unweighted fall-back below would break a tie among zeros)
+        if (WT && !efdhost::psd_total_ok(total)) continue;
         double need = total * (1.0 - eps);
         const double floor_ = eps * total / (double)np_;
         int nc = 0;
@@ -201,4 +220,25 @@ extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, cons
     }
     }
     return EFD_OK;
+}
+}  // namespace
+
+extern "C" int efd_host_modes(const double* p, const double* e, int32_t nt, const int32_t* l,
+                              const int32_t* m, const int32_t* n, const double* phase0,
+                              const double* jitter, int32_t nmodes, const double* ylm_p,
+                              const double* ylm_m, double eps, int32_t* keep, int32_t* nkeep,
+                              double* teuk, int64_t teuk_cap) {
+    return host_modes<false>(p, e, nt, l, m, n, phase0, jitter, nmodes, ylm_p, ylm_m, eps,
+                             nullptr, nullptr, nullptr, keep, nkeep, teuk, teuk_cap);
+}
+
+extern "C" int efd_host_modes_weighted(const double* p, const double* e, int32_t nt,
+                                       const int32_t* l, const int32_t* m, const int32_t* n,
+                                       const double* phase0, const double* jitter, int32_t nmodes,
+                                       const double* ylm_p, const double* ylm_m, double eps,
+                                       const double* f_phi, const double* f_r,
+                                       const efd_psd_table* psd, int32_t* keep, int32_t* nkeep,
+                                       double* teuk, int64_t teuk_cap) {
+    return host_modes<true>(p, e, nt, l, m, n, phase0, jitter, nmodes, ylm_p, ylm_m, eps, f_phi,
+                            f_r, psd, keep, nkeep, teuk, teuk_cap);
 }

@@ -1,5 +1,6 @@
 // emrifd_modes_device.inc -- amplitudes and ModeSelector(eps) on the device for batched callers
-// (included by emrifd_prepare.hip; efd_modes_select_batch, efd_modes_workspace_bytes).
+// (included by emrifd_prepare.hip; efd_modes_select_batch, efd_modes_select_batch_weighted,
+// efd_modes_workspace_bytes, efd_psd_eval).
 //
 // The device form of emrifd_modes.cpp / amplitude.py: at every trajectory knot the branch powers
 // |A_k|^2 |Y_k|^2 (every mode) and |A_k|^2 |Y_{l,-m}|^2 (modes with m != 0) are sorted
@@ -15,10 +16,19 @@
 //   k_modes_amp      (knot, walker) x lanes over K: the kept modes' complex amplitudes [nt][K]
 // Fixed-order reductions and scans, no atomics: bitwise reproducible. With teuk == NULL the
 // amplitudes are the STAND-IN model of emrifd_modes.cpp (not FEW physics), in plain FP64.
+//
+// Noise-weighted selection (k_modes_select<true>): both branch powers of mode k at knot i are
+// multiplied by 1 / S(|m_k f_phi[i] + n_k f_r[i]|) where the PSD table's S is finite and > 0 and
+// by 0 elsewhere; one interval search and one cubic per (knot, mode). The table's breakpoints are
+// staged in s_key, which nothing else uses until the candidates are compacted (no LDS added);
+// -DEFD_MODES_PSD_L2 searches them through L2 instead. A weighted knot whose total is 0 or not
+// finite keeps nothing. k_modes_select<false> is the unweighted kernel, unchanged.
+
+#include <type_traits>
 
 namespace {
 
-constexpr int MODES_MAX = 4096;            // modes; 2 MODES_MAX branch powers at most
+constexpr int MODES_MAX = 4096;           // modes; 2 MODES_MAX branch powers at most
 constexpr int MODES_NT = 1024;             // threads of k_modes_select and k_modes_compact
 constexpr int MODES_PER = MODES_MAX / MODES_NT;   // modes per thread
 constexpr int MODES_WAVES = MODES_NT / 64;
@@ -57,7 +67,45 @@ struct ModesBatch {
     ModesDesc d[EFD_BATCH_MAX];
 };
 
+// the weighted selection's extra kernel argument: the PSD table and each walker's knot
+// frequencies (both NULL: that walker is selected unweighted)
+struct ModesWeights {
+    const double* x;   // [n]
+    const double* c;   // [4][n - 1]
+    int32_t n;
+    efd_modes_weight w[EFD_BATCH_MAX];
+};
+struct ModesNoWeights {};
+
 __host__ __device__ inline int modes_stride(int nmodes) { return (nmodes + 3) & ~3; }
+
+// S(f) of a PPoly-layout table (include/emrifd.h; emrifd_host.cpp: psd_eval, the same bits:
+// every product and sum rounded on its own: contraction is off in these two functions). x: the
+// breakpoints, in LDS or global memory
+__device__ inline double psd_eval_dev(const double* x, const double* c, int n, double f) {
+#pragma clang fp contract(off)
+    int lo = 0, hi = n;   // -> #{j : x[j] <= f} (NaN: n)
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (f < x[mid]) hi = mid; else lo = mid + 1;
+    }
+    const int i = min(max(lo - 1, 0), n - 2);
+    const double s = f - x[i];
+    const int st = n - 1;
+    double r = c[i];
+    r = r * s + c[st + i];
+    r = r * s + c[2 * st + i];
+    return r * s + c[3 * st + i];
+}
+
+// 1 / S(|m f_phi + n f_r|) where S is finite and > 0, else 0
+__device__ inline double psd_weight_dev(const double* x, const double* c, int n, int m, int nn,
+                                        double f_phi, double f_r) {
+#pragma clang fp contract(off)
+    const double F = fabs((double)m * f_phi + (double)nn * f_r);
+    const double S = psd_eval_dev(x, c, n, F);
+    return (isfinite(S) && S > 0.0) ? 1.0 / S : 0.0;
+}
 
 // |A_lmn(p, e)| of the stand-in model (emrifd_modes.cpp: magnitudes)
 __device__ inline double standin_mag(int l, int m, int n, double jit, double p, double e) {
@@ -124,7 +172,9 @@ __device__ inline bool modes_before(double ka, uint16_t ia, double kb, uint16_t 
     return ka > kb || (ka == kb && ia < ib);
 }
 
-__global__ __launch_bounds__(MODES_NT) void k_modes_select(const ModesBatch B) {
+template <bool WT>
+__global__ __launch_bounds__(MODES_NT) void k_modes_select(
+    const ModesBatch B, const typename std::conditional<WT, ModesWeights, ModesNoWeights>::type W) {
     const ModesDesc& d = B.d[blockIdx.z];
     const int i = blockIdx.x;
     if (i >= d.nt) return;
@@ -138,6 +188,25 @@ __global__ __launch_bounds__(MODES_NT) void k_modes_select(const ModesBatch B) {
     // branch powers of this thread's modes k = tid + j MODES_NT: the +m branch (index k) and,
     // for m != 0, the partner (index MODES_MAX + k; the order of numpy's nm + rank numbering)
     const double p = d.p[i], e = d.e[i];
+    // this walker's knot frequencies when it is weighted (block-uniform)
+    bool weighted = false;
+    double f_phi = 0.0, f_r = 0.0;
+    const double* psd_x = nullptr;
+    if constexpr (WT) {
+        const efd_modes_weight& wt = W.w[blockIdx.z];
+        weighted = wt.f_phi != nullptr;
+        if (weighted) {
+            f_phi = wt.f_phi[i];
+            f_r = wt.f_r[i];
+#ifdef EFD_MODES_PSD_L2
+            psd_x = W.x;
+#else
+            for (int q = tid; q < W.n; q += MODES_NT) s_key[q] = W.x[q];
+            psd_x = s_key;
+            __syncthreads();   // (s_key is next written after modes_block_sum's barriers)
+#endif
+        }
+    }
     double pw[2 * MODES_PER];
     double part = 0.0;
     int npart = 0;
@@ -147,10 +216,16 @@ __global__ __launch_bounds__(MODES_NT) void k_modes_select(const ModesBatch B) {
         pw[2 * j] = pw[2 * j + 1] = -1.0;   // absent: below every floor
         if (k < nm) {
             const double a2 = modes_power(B, d, i, k, p, e);
+            double wk = 1.0;   // one weight per (knot, mode) serves both branches
+            if constexpr (WT)
+                if (weighted)
+                    wk = psd_weight_dev(psd_x, W.c, W.n, B.m[k], B.n[k], f_phi, f_r);
             pw[2 * j] = a2 * abs2(d.ylm_p, k);
+            if constexpr (WT) pw[2 * j] *= wk;
             part += pw[2 * j];
             if (B.m[k] != 0) {
                 pw[2 * j + 1] = a2 * abs2(d.ylm_m, k);
+                if constexpr (WT) pw[2 * j + 1] *= wk;
                 part += pw[2 * j + 1];
                 ++npart;
             }
@@ -161,6 +236,14 @@ __global__ __launch_bounds__(MODES_NT) void k_modes_select(const ModesBatch B) {
     int np_ = 0;
     modes_block_excl(npart, s_redi, &np_);
     np_ += nm;
+    if constexpr (WT) {
+        // weighted only: nothing can be ranked at a knot whose total is 0 or not finite, so it
+        // keeps nothing (block-uniform: total is the same value in every thread)
+        if (weighted && !(isfinite(total) && total > 0.0)) {
+            for (int k = tid; k < B.stride; k += MODES_NT) d.flags[(size_t)i * B.stride + k] = 0;
+            return;
+        }
+    }
     const double need = total * (1.0 - d.eps);
     // the c-th largest of the kept top-c exceeds eps total / np (the np - c + 1 powers from it
     // down sum to more than eps total): only powers above half that floor are candidates (the
@@ -300,9 +383,15 @@ size_t efd_modes_workspace_bytes(int32_t nt, int32_t nmodes) {
     return (size_t)nt * modes_stride(nmodes);
 }
 
-int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w, int32_t count,
-                           void* stream) {
-    const std::string F("efd_modes_select_batch");
+}  // extern "C"
+
+namespace {
+
+// efd_modes_select_batch (wt == NULL) and efd_modes_select_batch_weighted
+int modes_select(const char* fname, const efd_modes_table* tab, const efd_modes_walker* w,
+                 const efd_modes_weight* wt, const efd_psd_table* psd, int32_t count,
+                 void* stream) {
+    const std::string F(fname);
     if (!tab || !w) return fail(EFD_ERR_ARG, F + ": NULL argument");
     if (count < 1 || count > EFD_BATCH_MAX)
         return fail(EFD_ERR_ARG, F + ": count out of range [1, EFD_BATCH_MAX]");
@@ -310,6 +399,18 @@ int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w
         return fail(EFD_ERR_ARG, F + ": NULL mode table");
     if (tab->nmodes < 1 || tab->nmodes > MODES_MAX)
         return fail(EFD_ERR_ARG, F + ": nmodes out of range [1, 4096]");
+    ModesWeights W{};
+    if (wt) {
+        if (!psd || !psd->x || !psd->c) return fail(EFD_ERR_ARG, F + ": NULL PSD table");
+        if (psd->n < 2 || psd->n > MODES_MAX)
+            return fail(EFD_ERR_ARG, F + ": PSD table n out of range [2, 4096]");
+        W.x = psd->x; W.c = psd->c; W.n = psd->n;
+        for (int i = 0; i < count; ++i) {
+            if ((wt[i].f_phi == nullptr) != (wt[i].f_r == nullptr))
+                return fail(EFD_ERR_ARG, F + ": f_phi and f_r are both set or both NULL");
+            W.w[i] = wt[i];
+        }
+    }
     ModesBatch B{};
     B.l = tab->l; B.m = tab->m; B.n = tab->n; B.phase0 = tab->phase0; B.jitter = tab->jitter;
     B.nmodes = tab->nmodes;
@@ -350,7 +451,13 @@ int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w
     }
     hipStream_t st = (hipStream_t)stream;
     const unsigned nz = (unsigned)count;
-    hipLaunchKernelGGL(k_modes_select, dim3(ntmax, 1, nz), dim3(MODES_NT), 0, st, B);
+    // (a weighted call runs the weighted instantiation for every walker, so a walker's outputs
+    // never depend on its companions)
+    if (wt)
+        hipLaunchKernelGGL(k_modes_select<true>, dim3(ntmax, 1, nz), dim3(MODES_NT), 0, st, B, W);
+    else
+        hipLaunchKernelGGL(k_modes_select<false>, dim3(ntmax, 1, nz), dim3(MODES_NT), 0, st, B,
+                           ModesNoWeights{});
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_modes_compact, dim3(nz), dim3(MODES_NT), 0, st, B);
     HIP_TRY(hipGetLastError());
@@ -359,6 +466,42 @@ int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w
                            B);
         HIP_TRY(hipGetLastError());
     }
+    return EFD_OK;
+}
+
+__global__ __launch_bounds__(256) void k_psd_eval(const double* x, const double* c, int n,
+                                                  const double* f, int64_t nf, double* out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < nf) out[j] = psd_eval_dev(x, c, n, f[j]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w, int32_t count,
+                           void* stream) {
+    return modes_select("efd_modes_select_batch", tab, w, nullptr, nullptr, count, stream);
+}
+
+int efd_modes_select_batch_weighted(const efd_modes_table* tab, const efd_modes_walker* w,
+                                    const efd_modes_weight* wt, const efd_psd_table* psd,
+                                    int32_t count, void* stream) {
+    return modes_select("efd_modes_select_batch_weighted", tab, w, wt, psd, count, stream);
+}
+
+int efd_psd_eval(const efd_psd_table* psd, const double* f, int64_t nf, double* out,
+                 void* stream) {
+    const std::string F("efd_psd_eval");
+    if (!psd || !psd->x || !psd->c || psd->n < 2 || psd->n > MODES_MAX || nf < 0 ||
+        (nf > 0 && (!f || !out)))
+        return fail(EFD_ERR_ARG, F + ": bad arguments (2 <= n <= 4096)");
+    if (nf == 0) return EFD_OK;
+    const int64_t nb = (nf + 255) / 256;
+    if (nb > 0x7fffffff) return fail(EFD_ERR_ARG, F + ": nf out of range");
+    hipLaunchKernelGGL(k_psd_eval, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, psd->x,
+                       psd->c, psd->n, f, nf, out);
+    HIP_TRY(hipGetLastError());
     return EFD_OK;
 }
 

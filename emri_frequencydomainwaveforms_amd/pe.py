@@ -48,7 +48,8 @@ class PESetup:
 
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
-          window=None, start_cov=None, template="fd", injectFD=None, upstream="host"):
+          window=None, start_cov=None, template="fd", injectFD=None, upstream="host",
+          mode_selector_kwargs=None):
     """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
     generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
     not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
@@ -72,7 +73,9 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     happens to trigger it (tools/api_trace.py, tools/gc_cycles.py).
     upstream: "host" (default) or "device": the likelihood's walkers take their amplitudes and
     mode selection on the device (Likelihood.device_upstream; only the trajectories stay on the
-    host), where the template can pipeline on a symmetric grid. The injection is the same."""
+    host), where the template can pipeline on a symmetric grid. The injection is the same.
+    mode_selector_kwargs: passed to both generators, e.g. dict(sensitivity_fn=get_sensitivity)
+    for the noise-weighted mode selection (amplitude.ModeSelector)."""
     if template not in ("fd", "td"):
         raise ValueError("template: 'fd' or 'td'")
     if upstream not in ("host", "device"):
@@ -105,7 +108,8 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     injection = tc.both_transforms(truth6[None, :])[0]
 
     few = GenerateEMRIWaveform("FastSchwarzschildEccentricFlux", sum_kwargs=SUM_KW,
-                               use_gpu=True, return_list=True, caustic=caustic)
+                               use_gpu=True, return_list=True, caustic=caustic,
+                               mode_selector_kwargs=mode_selector_kwargs)
     kw = dict(T=Tobs, dt=dt, eps=eps)
     sig = few(*injection, mask_positive=True, **kw)
     frequency = few.waveform_generator.create_waveform.frequency
@@ -150,7 +154,7 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
         # the TD generator (td_gen_list, emri_pe.py:95-110) and its DFT template (:262, :266)
         td = GenerateEMRIWaveform("FastSchwarzschildEccentricFlux",
                                   sum_kwargs=dict(pad_output=True, odd_len=True), use_gpu=True,
-                                  return_list=True)
+                                  return_list=True, mode_selector_kwargs=mode_selector_kwargs)
         gen_td = get_fd_waveform_fromTD(td, pos, dt, window=window)
         if template == "td":
             gen, few = gen_td, td

@@ -14,7 +14,8 @@ the stand-ins of trajectory.py / amplitude.py (NOT FEW physics; SURVEY.md sectio
 The FD summation itself runs in libemrifd.so on the GPU.
 The batched calls (generate_batch, spectrum_batch, the likelihood) can also take the amplitudes
 and the mode selection on the GPU (upstream="device": efd_modes_select_batch); the trajectory
-then is the only host part.
+then is the only host part. mode_selector_kwargs=dict(sensitivity_fn=...) makes eps a fraction of
+noise-weighted power on either route (amplitude.ModeSelector; FEW's kwarg as recalled).
 `use_gpu` selects the return type (torch tensors on the GPU, or numpy copies); the compute
 always runs on the GPU -- there is no CPU fallback.
 
@@ -58,7 +59,8 @@ class FastSchwarzschildEccentricFlux:
     descriptor = "eccentric"
 
     def __init__(self, inspiral_kwargs=None, amplitude_kwargs=None, sum_kwargs=None,
-                 Ylm_kwargs=None, use_gpu=False, caustic="uniform", **kwargs):
+                 Ylm_kwargs=None, use_gpu=False, caustic="uniform", mode_selector_kwargs=None,
+                 **kwargs):
         sum_kwargs = dict(sum_kwargs or {})
         # FEW's default output_type is "td" (InterpolatedModeSum); "fd" selects the FD sum
         self.output_type = sum_kwargs.pop("output_type", "td")
@@ -68,7 +70,11 @@ class FastSchwarzschildEccentricFlux:
         self.inspiral_generator = EMRIInspiral(func="SchwarzEccFlux", **(inspiral_kwargs or {}))
         self.amplitude_generator = RomanAmplitude(**(amplitude_kwargs or {}))
         self.ylm_gen = GetYlms(assume_positive_m=True, **(Ylm_kwargs or {}))
-        self.mode_selector = ModeSelector(self.amplitude_generator.m0mask)
+        # mode_selector_kwargs=dict(sensitivity_fn=...): eps cuts noise-weighted power (the host
+        # selector is numpy's; the native routes take its PSD table, amplitude.psd_table)
+        ms_kwargs = dict(mode_selector_kwargs or {})
+        ms_kwargs.pop("use_gpu", None)
+        self.mode_selector = ModeSelector(self.amplitude_generator.m0mask, **ms_kwargs)
         if self.output_type == "fd":
             sum_kwargs.setdefault("caustic", caustic)
             self.create_waveform = FDInterpolatedModeSum(use_gpu=use_gpu, **sum_kwargs)
@@ -134,7 +140,18 @@ class FastSchwarzschildEccentricFlux:
             t, p, e, Phi_phi, Phi_r, f_phi, f_r = self.inspiral_generator.with_frequencies(
                 M, mu, 0.0, p0, e0, 1.0, Phi_phi0=Phi_phi0, Phi_r0=Phi_r0, T=T)
             ylms_all = self._ylms(theta, phi)
-            keep, teuk = amp.select(p, e, ylms_all, eps, lib=lib)
+            sel = self.mode_selector
+            if sel.sensitivity_fn is None:
+                keep, teuk = amp.select(p, e, ylms_all, eps, lib=lib)
+            elif sel.psd_table is not None:
+                keep, teuk = amp.select(p, e, ylms_all, eps, lib=lib, f_phi=f_phi, f_r=f_r,
+                                        psd=sel.psd_table)
+            else:   # a callable with no table: numpy's selector (correct, and slow)
+                A = amp(p, e)
+                keep = sel(A, ylms_all, (amp.l_arr, amp.m_arr, amp.n_arr), eps=eps,
+                           mode_freqs=(f_phi, f_r))
+                teuk = np.ascontiguousarray(A[:, keep])
+            _check_kept(keep)
             K = amp.num_teuk_modes
             ylms = np.concatenate([ylms_all[:K][keep], ylms_all[K:][keep]])
             if not include_minus_m:
@@ -169,7 +186,12 @@ class FastSchwarzschildEccentricFlux:
         else:
             teuk_all = amp(p, e)
             ylms_all = self.ylm_gen(amp.l_arr, amp.m_arr, theta, phi)
-            keep = self.mode_selector(teuk_all, ylms_all, None, eps=eps)
+            if self.mode_selector.sensitivity_fn is None:
+                keep = self.mode_selector(teuk_all, ylms_all, None, eps=eps)
+            else:
+                keep = self.mode_selector(teuk_all, ylms_all, (amp.l_arr, amp.m_arr, amp.n_arr),
+                                          fund_freq_args=(M, 0.0, p, e, 0.0), eps=eps)
+                _check_kept(keep)
             teuk = teuk_all[:, keep]
             K = amp.num_teuk_modes
             ylms = np.concatenate([ylms_all[:K][keep], ylms_all[K:][keep]])
@@ -237,6 +259,11 @@ class FastSchwarzschildEccentricFlux:
         state = state if state is not None else {}
         amp = self.amplitude_generator
         table, _ = amp.device_table(dev)
+        weighted = self.mode_selector.sensitivity_fn is not None
+        psd = self.mode_selector.psd_table if weighted else None
+        if weighted and psd is None:
+            from .amplitude import NO_TABLE
+            raise ValueError("upstream='device': " + NO_TABLE)
         ys = [self._ylms_device(c[4], c[5], dev) for c in calls]
         futures = futures if futures is not None else self.trajectories_async(calls)
         trajs = [f.result() for f in futures]
@@ -269,8 +296,12 @@ class FastSchwarzschildEccentricFlux:
             fields.append(v)
             walkers.append(dict(p=v[1], e=v[2], ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=c[10],
                                 include_minus_m=include_minus_m, teuk=None))
+            if weighted:   # the uploaded knot frequencies: the weighting costs no transfer
+                walkers[-1].update(f_phi=v[5], f_r=v[6])
         from .amplitude import device_select
-        res = device_select(table, K, walkers, dev, strm, state)   # (synchronises strm)
+        res = device_select(table, K, walkers, dev, strm, state, psd=psd)   # (synchronises strm)
+        for r in res:
+            _check_kept(r["keep_host"])
         out, modes = [], []
         for v, r in zip(fields, res):
             out.append(DeviceInputs(t=v[0], phi_phi=v[3], phi_r=v[4], f_phi=v[5], f_r=v[6],
@@ -462,6 +493,13 @@ class FastSchwarzschildEccentricFlux:
         hp, hc = self.create_waveform.polarizations(S, mask_positive)
         out = torch.stack([hp, hc])
         return out if self.use_gpu else out.cpu().numpy()
+
+
+def _check_kept(keep):
+    """The noise-weighted selection can keep nothing (every weight 0); the mode sum cannot."""
+    if len(keep) == 0:
+        raise ValueError("the mode selection kept no mode: the sensitivity_fn is not finite and "
+                         "positive at any harmonic's frequency")
 
 
 def _nbytes(d):

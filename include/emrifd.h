@@ -752,6 +752,62 @@ size_t efd_modes_workspace_bytes(int32_t nt, int32_t nmodes);
 int efd_modes_select_batch(const efd_modes_table* tab, const efd_modes_walker* w, int32_t count,
                            void* stream);
 
+/*
+ * Noise-weighted mode selection (not part of the reference's interface; FEW's ModeSelector with a
+ * sensitivity_fn, as recalled): before the cut both branch powers of mode k at knot i are
+ * multiplied by W[i][k] = 1 / S(F), F = |m_k f_phi[i] + n_k f_r[i]| (the partner's frequency is
+ * -F: the same weight), where S(F) is finite and > 0, and by 0 elsewhere. eps is then a fraction
+ * of the noise-weighted power. A knot whose weighted total is 0 or not finite keeps nothing (the
+ * unweighted selection always keeps a knot's largest branch; here that would be a tie-break among
+ * zeros), so the kept set can be empty.
+ *
+ * The PSD is a piecewise cubic in scipy's PPoly layout: x[n] strictly ascending breakpoints,
+ * c[4][n - 1] row-major (c[j (n - 1) + i] the coefficient of s^(3 - j) on piece i),
+ *   S(f) = ((c0 s + c1) s + c2) s + c3,  s = f - x[i],
+ *   i = clamp(#{j : x[j] <= f} - 1, 0, n - 2)   (searchsorted(x, f, 'right') - 1),
+ * so the end pieces extrapolate as PPoly(extrapolate=True) does, and NaN gives NaN. Every
+ * product and sum is rounded on its own (no fused multiply-add): efd_psd_eval and
+ * efd_psd_eval_cpu return the same bits.
+ */
+typedef struct efd_psd_table {
+    const double* x;          /* [n] breakpoints, strictly ascending                          */
+    const double* c;          /* [4][n - 1] coefficients, highest power first                 */
+    int32_t n;                /* 2 <= n <= 4096                                               */
+} efd_psd_table;
+
+/* out[j] = S(f[j]), j < nf. efd_psd_eval: x, c, f and out are device memory, one launch on
+ * `stream`, asynchronous (x's order is the caller's to guarantee). efd_psd_eval_cpu: host memory,
+ * synchronous, `stream` ignored; x not strictly ascending is EFD_ERR_ARG. nf = 0 does nothing. */
+int efd_psd_eval(const efd_psd_table* psd, const double* f, int64_t nf, double* out, void* stream);
+int efd_psd_eval_cpu(const efd_psd_table* psd, const double* f, int64_t nf, double* out,
+                     void* stream);
+
+/* efd_host_modes with the noise weighting above: f_phi, f_r [nt] (Hz, efd_host_trajectory's) and
+ * a host efd_psd_table. Any efd_host_set_threads count gives the same results; *nkeep may be 0. */
+int efd_host_modes_weighted(const double* p, const double* e, int32_t nt, const int32_t* l,
+                            const int32_t* m, const int32_t* n, const double* phase0,
+                            const double* jitter, int32_t nmodes, const double* ylm_p,
+                            const double* ylm_m, double eps, const double* f_phi,
+                            const double* f_r, const efd_psd_table* psd, int32_t* keep,
+                            int32_t* nkeep, double* teuk, int64_t teuk_cap);
+
+/* One walker's knot frequencies for efd_modes_select_batch_weighted: [nt] each, device memory;
+ * both NULL = this walker is selected unweighted (exactly as by efd_modes_select_batch). */
+typedef struct efd_modes_weight {
+    const double* f_phi;
+    const double* f_r;
+} efd_modes_weight;
+
+/* efd_modes_select_batch with the noise weighting above formed inside the selection kernel (one
+ * interval search and one cubic per (knot, mode), serving both branches): still three launches,
+ * no allocation, no host synchronisation, no atomics, bitwise reproducible, each walker's outputs
+ * bitwise those of its own count = 1 call. wt[count]; psd holds device pointers. wt = NULL (then
+ * psd may be NULL), or every walker's frequencies NULL, is efd_modes_select_batch. With teuk
+ * given, the table's m and n must be the modes' (the unweighted call reads m != 0 only). */
+int efd_modes_select_batch_weighted(const efd_modes_table* tab, const efd_modes_walker* w,
+                                    const efd_modes_weight* wt, const efd_psd_table* psd,
+                                    int32_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
