@@ -12,11 +12,14 @@ source is compiled to an object under build/, all of them at once, and one link 
                           calls): amplitudes, mode selection
   csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode
                          sum, its preparation, the window path, the channel split and reductions)
+                         and emrifd_traj.hip (UPSTREAM_HIP_UNITS: the device trajectories and p0
+                         solve, upstream of that chain)
                          -> hipcc --offload-arch=gfx950 -c each; all share csrc/emrifd_common.h,
                          the first two also csrc/emrifd_layout.h (no relocatable device code);
                          emrifd_prepare.hip includes csrc/emrifd_modes_device.inc (amplitudes and
-                         mode selection on the device)
-  link                -> hipcc -shared over the eight objects, with libgomp and libmvec
+                         mode selection on the device); emrifd_traj.hip includes
+                         csrc/traj_costab.inc (the host's cosine table)
+  link                -> hipcc -shared over the nine objects, with libgomp and libmvec
 """
 
 import glob
@@ -29,6 +32,9 @@ SRC = os.path.join(CSRC, "emrifd.hip")
 # the HIP translation units, the mode sum (SRC) first, then its preparation: the two longest
 HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_prepare.hip"), os.path.join(CSRC, "emrifd_window.hip"),
              os.path.join(CSRC, "emrifd_reduce.hip")]
+# the HIP units upstream of that chain (the same flags; they share emrifd_common.h only)
+UPSTREAM_HIP_UNITS = [os.path.join(CSRC, "emrifd_traj.hip")]
+ALL_HIP_UNITS = HIP_UNITS + UPSTREAM_HIP_UNITS
 CPU_SRC = os.path.join(CSRC, "emrifd_cpu.cpp")
 REDUCE_CPU_SRC = os.path.join(CSRC, "emrifd_reduce_cpu.cpp")
 HOST_SRC = os.path.join(CSRC, "emrifd_host.cpp")
@@ -101,8 +107,8 @@ def build(force=False, verbose=False, extra=()):
     os.makedirs(OBJDIR, exist_ok=True)
     gxx = ["g++", "-O3", f"-march={CPU_ARCH}", "-fPIC", "-std=c++17", "-fopenmp"]
     bid = [f'-DEFD_BUILD_ID="{sid}"'] if not extra else []
-    # the longest compile (the mode sum) first; eight compilers at once, one per source
-    cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in HIP_UNITS]
+    # the longest compile (the mode sum) first; nine compilers at once, one per source
+    cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in ALL_HIP_UNITS]
     cmds += [[*gxx, "-ffp-contract=off", "-c", s, "-o", obj_path(s)]
              for s in (CPU_SRC, REDUCE_CPU_SRC, HOST_SRC)]
     cmds += [[*gxx, "-ffast-math", "-c", MODES_SRC, "-o", obj_path(MODES_SRC)]]
@@ -114,7 +120,7 @@ def build(force=False, verbose=False, extra=()):
     failed = [cmd for cmd, p in zip(cmds, procs) if p.wait() != 0]   # (waits for every one)
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])
-    link = link_cmd(HOST_OBJS + [obj_path(s) for s in HIP_UNITS], OUT + ".tmp")
+    link = link_cmd(HOST_OBJS + [obj_path(s) for s in ALL_HIP_UNITS], OUT + ".tmp")
     if verbose:
         print(" ".join(link), flush=True)
     subprocess.run(link, check=True)

@@ -30,6 +30,14 @@ EFD_PAIR_MAX_ROWS = 64
 EFD_PAIR_SCRATCH = 655360   # the pair statistics' scratch doubles (1024 chunks x 64 rows x 10)
 EFD_WINDOW_MAX_ROWS = 16   # efd_window_rows' windows per call
 EFD_MODES_AMP_OVERFLOW = 1   # efd_modes_select_batch's status bit: amp capacity too small
+EFD_TRAJ_MAX_LEN = 1024   # efd_traj_batch's longest knot slab
+# efd_traj_batch's and efd_traj_p_at_t_batch's per-source status words
+EFD_TRAJ_OK = 0
+EFD_TRAJ_BAD_SOURCE = 1
+EFD_TRAJ_TOO_LONG = 2
+EFD_TRAJ_STEP_FAILED = 3
+EFD_TRAJ_STEP_CAP = 4
+EFD_TRAJ_NO_BRACKET = 5
 
 # every symbol include/emrifd.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -106,6 +114,8 @@ EXPORTED_SYMBOLS = (
     "efd_psd_eval_cpu",
     "efd_host_modes_weighted",
     "efd_modes_select_batch_weighted",
+    "efd_traj_batch",
+    "efd_traj_p_at_t_batch",
 )
 
 
@@ -226,6 +236,13 @@ class ModesWeight(ctypes.Structure):
         ("f_phi", ctypes.c_void_p),
         ("f_r", ctypes.c_void_p),
     ]
+
+
+class TrajSource(ctypes.Structure):
+    """Mirror of `efd_traj_source` (include/emrifd.h)."""
+
+    _fields_ = [(f, ctypes.c_double) for f in ("M", "mu", "p0", "e0", "Phi_phi0", "Phi_r0", "T",
+                                               "rtol", "atol")]
 
 
 class EFDError(RuntimeError):
@@ -439,6 +456,11 @@ def load(path=None):
                                                         ctypes.POINTER(ModesWalker),
                                                         ctypes.POINTER(ModesWeight),
                                                         ctypes.POINTER(PsdTable), i32, vp]
+    if hasattr(lib, "efd_traj_batch"):   # trajectories and the p0 solve on the device
+        lib.efd_traj_batch.restype = ctypes.c_int
+        lib.efd_traj_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+        lib.efd_traj_p_at_t_batch.restype = ctypes.c_int
+        lib.efd_traj_p_at_t_batch.argtypes = [vp, i32, dbl, dbl, vp, vp, vp]
     _ = dbl
     if path is None:
         _lib = lib

@@ -409,6 +409,9 @@ class Likelihood:
     # amplitudes and mode selection on the device (pe.setup(upstream="device")): get_ll's
     # pipelined templates on symmetric grids take _get_ll_device; False keeps the host upstream
     device_upstream = False
+    # with device_upstream: the walkers' trajectories on the device too, all of a call's in one
+    # launch ahead of the first group (pe.setup(trajectory="device"); efd_traj_batch)
+    device_trajectory = False
 
     def _get_ll_device(self, tm, params, kwargs, out):
         """The fused likelihood with the upstream's amplitudes and mode selection on the device:
@@ -418,6 +421,8 @@ class Likelihood:
         K and efd_modesum_prepare_batch) and one efd_modesum_sum_loglike_ex with the tile
         constants write the group's log-likelihoods into its slice of out; a group's device
         chain runs beside the next group's trajectories and selection. One copy out per batch.
+        With device_trajectory the trajectories of all walkers are integrated on the device in
+        one launch on the current stream first (no pool, no packed upload).
         Returns the log-likelihoods on the host, or None, before queueing anything, when the
         template is not a GenerateEMRIWaveform on a symmetric grid or the call names an
         explicit mode list (the caller then takes the host upstream's path)."""
@@ -448,7 +453,11 @@ class Likelihood:
                                   order=(ctypes.c_void_p * len(gst))(*gst))
         gst = D["gst"]
         calls, scales = few.device_calls(params, T, eps)
-        futs = few.waveform_generator.trajectories_async(calls)
+        on_device = self.device_trajectory
+        # the trajectories: on the prefetch pool, or (device_trajectory) all of them in one
+        # launch on the current stream, which the slots' streams are ordered after below
+        futs = few.waveform_generator.trajectories_async(calls) if not on_device else []
+        trajs = few.device_trajectories(st, calls) if on_device else None
         _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
                                         D["order"], len(gst)), "efd_stream_order", lib)
         pin = D.get("pin")
@@ -460,7 +469,9 @@ class Likelihood:
             for gidx, g0 in enumerate(range(0, n, G)):
                 slot = gidx % 2
                 jobs = few.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
-                                        futs[g0:g0 + G], freq, k0, None, include_minus_m)
+                                        None if on_device else futs[g0:g0 + G], freq, k0, None,
+                                        include_minus_m,
+                                        trajs[g0:g0 + G] if on_device else None)
                 tc = self._tile_constants(freq, k0, st["streams"][slot], D)
                 sum_batch_loglike(jobs, self._d, self._w_templ, out[g0:g0 + len(jobs)],
                                   stream=gst[slot], tile_const=tc)

@@ -146,14 +146,23 @@ class ModeByModeStudy:
         self.timing = None
 
     # ---- the driver's get_p_at_t step (:196-213) ----------------------------------------------
-    def fixed_inspiral(self, params, Tobs=None):
+    def fixed_inspiral(self, params, Tobs=None, device=False):
         """params [B][14] with p0 replaced by the value whose inspiral plunges after 0.99 Tobs
         years (trajectory.get_p_at_t, the driver's tolerances); a source the root search
-        refuses keeps its p0 and fails in run() as the driver's would."""
-        from .trajectory import EMRIInspiral, get_p_at_t
+        refuses keeps its p0 and fails in run() as the driver's would. device=True: every
+        source's root solve at once on the device (trajectory.get_p_at_t_batch, one wavefront
+        per source) instead of one host solve after the other."""
+        from .trajectory import EMRIInspiral, get_p_at_t, get_p_at_t_batch
         Tobs = self.Tobs if Tobs is None else float(Tobs)
         out = np.array(params, dtype=np.float64).reshape(-1, 14)
         traj = EMRIInspiral(func="SchwarzEccFlux")
+        if device:
+            p0, _ = get_p_at_t_batch(traj, Tobs * 0.99, out[:, [0, 1, 4]], xtol=2e-12,
+                                     rtol=8.881784197001252e-16, device=self.device,
+                                     state=self._buf.setdefault("p0_state", {}))
+            ok = ~np.isnan(p0)
+            out[ok, 3] = p0[ok]
+            return out
         for row in out:
             try:
                 row[3] = get_p_at_t(traj, Tobs * 0.99, [row[0], row[1], 0.0, row[4], 1.0],

@@ -49,7 +49,7 @@ class PESetup:
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
           window=None, start_cov=None, template="fd", injectFD=None, upstream="host",
-          mode_selector_kwargs=None):
+          mode_selector_kwargs=None, trajectory="host"):
     """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
     generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
     not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
@@ -74,6 +74,9 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     upstream: "host" (default) or "device": the likelihood's walkers take their amplitudes and
     mode selection on the device (Likelihood.device_upstream; only the trajectories stay on the
     host), where the template can pipeline on a symmetric grid. The injection is the same.
+    trajectory: "host" (default) or "device" (with upstream="device" only): the walkers'
+    trajectories are integrated on the device as well, all of a likelihood call's in one launch
+    (Likelihood.device_trajectory; efd_traj_batch). The injection is the same.
     mode_selector_kwargs: passed to both generators, e.g. dict(sensitivity_fn=get_sensitivity)
     for the noise-weighted mode selection (amplitude.ModeSelector)."""
     if template not in ("fd", "td"):
@@ -82,6 +85,10 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
         raise ValueError("upstream: 'host' or 'device'")
     if upstream == "device" and template != "fd":
         raise ValueError("upstream='device' is the FD template's")
+    if trajectory not in ("host", "device"):
+        raise ValueError("trajectory: 'host' or 'device'")
+    if trajectory == "device" and upstream != "device":
+        raise ValueError("trajectory='device' needs upstream='device'")
     if template == "td" and downsample:
         raise ValueError("Cannot run downsampling with time domain template")   # emri_pe.py:326
     from .fdutils import get_fd_waveform_fromFD, get_fd_waveform_fromTD, get_sensitivity
@@ -163,7 +170,9 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
                       transpose_params=False, subset=like_subset, f_arr=f_like, use_gpu=True)
     if upstream == "device":
         like.device_upstream = True
+        like.device_trajectory = trajectory == "device"
     info["upstream"] = upstream
+    info["trajectory"] = trajectory
     data = (gen_fd if inject_fd else gen_td)(*injection, **kw)
     like.inject_signal(data_stream=data, noise_fn=[get_sensitivity, get_sensitivity],
                        noise_kwargs=[{}, {}])

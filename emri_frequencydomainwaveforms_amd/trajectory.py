@@ -17,6 +17,10 @@ Two backends with the same equations and integrator: "native" (csrc/emrifd_host.
 libemrifd.so: scipy RK45's Dormand-Prince tableau, step control, dense output and event root
 restated in C++, ~1 ms per trajectory, releases the GIL) and "python" (scipy.solve_ivp with the
 numpy right-hand side, ~50-100 ms). "auto" takes the native one when the library is built.
+
+For batched callers the same integrator also runs on the device, one wavefront per source
+(csrc/emrifd_traj.hip; opt-in): EMRIInspiral.device_batch, device_trajectories and
+get_p_at_t_batch below. The native host forms are its reference.
 """
 
 import ctypes
@@ -29,6 +33,7 @@ from .constants import MTSUN_SI, YRSID_SI
 from .frequencies import get_fundamental_frequencies
 
 DIST_TO_SEPARATRIX = 0.1
+EFD_TRAJ_MAX_LEN = 1024   # efd_traj_batch's longest knot slab (include/emrifd.h)
 
 
 def _pn_rhs(tau, y, q):
@@ -145,6 +150,135 @@ class EMRIInspiral:
     def plunge_time(self, M, mu, a, p0, e0, x0=1.0, T_max=100.0):
         t = self(M, mu, a, p0, e0, x0, T=T_max)[0]
         return t[-1]
+
+    def device_batch(self, sources, device=None, stream=None, state=None):
+        """The trajectories of any number of sources on the device, one wavefront each
+        (efd_traj_batch; opt-in, for batched callers): `sources` are (M, mu, p0, e0, Phi_phi0,
+        Phi_r0, T) tuples. One packed pinned upload of the sources, one launch, one download of
+        nt and status and one synchronisation of `stream` (a torch stream; default the current
+        one) for the whole batch. Returns (views, nt): per source with_frequencies' seven
+        arrays (t, p, e, Phi_phi, Phi_r, f_phi, f_r) as float64 device views of its nt knots,
+        and nt as a numpy int32 array. state: a dict the caller keeps per stream (the pinned
+        buffers). A source the kernel refuses raises what the native host path raises for that
+        condition."""
+        src = np.array([tuple(float(v) for v in s) for s in sources], dtype=np.float64)
+        src = src.reshape(-1, 7)
+        L = min(int(self.max_init_len), EFD_TRAJ_MAX_LEN)
+        knots, nt, status = device_trajectories(src, self.rtol, self.atol, L, device, stream, state)
+        for i, st in enumerate(status.tolist()):
+            if st == 0:
+                continue
+            if st == 1 and src[i, 2] - (6.0 + 2.0 * src[i, 3]) <= DIST_TO_SEPARATRIX:
+                raise ValueError("initial p0 lies inside the separatrix buffer")
+            if st == 2:
+                raise ValueError("trajectory longer than max_init_len")
+            raise RuntimeError(f"trajectory integration failed (source {i}: device status {st})")
+        return [[knots[i, k, :n] for k in range(7)] for i, n in enumerate(nt.tolist())], nt
+
+
+def _pack_sources(src9, device, stream, state):
+    """The [B][9] efd_traj_source rows on the device: one pinned copy on `stream`."""
+    import torch
+
+    from . import _lib
+    lib = _lib.load()
+    B = len(src9)
+    pin = state.get("traj_src")
+    if pin is None or pin.numel() < 9 * B:
+        pin = state["traj_src"] = torch.empty(max(9 * B, 9 * 64), dtype=torch.float64,
+                                              pin_memory=True)
+    pin.numpy()[:9 * B] = src9.reshape(-1)
+    with torch.cuda.stream(stream):
+        dsrc = torch.empty(9 * B, dtype=torch.float64, device=device)
+    _lib.check(lib.efd_upload(dsrc.data_ptr(), pin.data_ptr(), 72 * B, stream.cuda_stream),
+               "efd_upload", lib)
+    return lib, dsrc
+
+
+def _stream_of(device, stream):
+    import torch
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    return dev, (stream if stream is not None else torch.cuda.current_stream(dev))
+
+
+def device_trajectories(sources, rtol, atol, max_len, device=None, stream=None, state=None,
+                        prof=None):
+    """efd_traj_batch on `sources` ([B][7] host rows M, mu, p0, e0, Phi_phi0, Phi_r0, T) with no
+    judgement of the outcome: returns (knots, nt, status), knots a float64 device tensor
+    [B][7][max_len] (zero-filled first; source i's arrays are knots[i, k, :nt[i]]), nt and status
+    numpy int32 [B] (nt is 0 where status is not 0). One upload, one launch, one download, one
+    synchronisation of `stream`. prof: a pair of torch events recorded around the launch alone."""
+    import torch
+    dev, strm = _stream_of(device, stream)
+    state = state if state is not None else {}
+    src = np.asarray(sources, dtype=np.float64).reshape(-1, 7)
+    B = len(src)
+    src9 = np.concatenate([src, np.full((B, 1), float(rtol)), np.full((B, 1), float(atol))], axis=1)
+    lib, dsrc = _pack_sources(src9, dev, strm, state)
+    with torch.cuda.stream(strm):
+        knots = torch.zeros((B, 7, int(max_len)), dtype=torch.float64, device=dev)
+        ints = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+    from . import _lib
+    if prof is not None:
+        prof[0].record(strm)
+    _lib.check(lib.efd_traj_batch(dsrc.data_ptr(), B, int(max_len), knots.data_ptr(),
+                                  ints.data_ptr(), ints.data_ptr() + 4 * B, strm.cuda_stream),
+               "efd_traj_batch", lib)
+    if prof is not None:
+        prof[1].record(strm)
+    host = _download_ints(lib, ints, strm, state)
+    return knots, host[:B].copy(), host[B:].copy()
+
+
+def _download_ints(lib, ints, strm, state):
+    import torch
+
+    from . import _lib
+    n = ints.numel()
+    hb = state.get("traj_ints")
+    if hb is None or hb.numel() < n:
+        hb = state["traj_ints"] = torch.empty(max(n, 128), dtype=torch.int32, pin_memory=True)
+    _lib.check(lib.efd_download(hb.data_ptr(), ints.data_ptr(), 4 * n, strm.cuda_stream),
+               "efd_download", lib)
+    strm.synchronize()
+    return hb.numpy()[:n]
+
+
+def get_p_at_t_batch(traj, t_out, rows, xtol=2e-12, rtol=8.881784197001252e-16, device=None,
+                     stream=None, state=None, prof=None):
+    """get_p_at_t for many sources at once on the device (efd_traj_p_at_t_batch, one wavefront
+    per source, every Brent evaluation an integration to (2 t_out + 1) yr): `rows` are (M, mu,
+    e0) per source, t_out a scalar or one value per row [yr], traj an EMRIInspiral (its rtol and
+    atol). The default bracket of get_p_at_t. Returns (p0, refused): p0 float64 [B] as numpy with
+    NaN where the search was refused (what get_p_at_t raises ValueError for), and those rows'
+    indices."""
+    import torch
+    dev, strm = _stream_of(device, stream)
+    state = state if state is not None else {}
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 3)
+    B = len(rows)
+    src9 = np.zeros((B, 9))
+    src9[:, 0], src9[:, 1], src9[:, 3] = rows[:, 0], rows[:, 1], rows[:, 2]
+    src9[:, 6] = np.broadcast_to(np.asarray(t_out, dtype=np.float64), (B,))
+    src9[:, 7], src9[:, 8] = traj.rtol, traj.atol
+    if B == 0:
+        return np.empty(0), np.empty(0, dtype=np.int64)
+    lib, dsrc = _pack_sources(src9, dev, strm, state)
+    with torch.cuda.stream(strm):
+        out = torch.zeros(2 * B, dtype=torch.float64, device=dev)   # p0 [B] | status as int32
+    from . import _lib
+    if prof is not None:
+        prof[0].record(strm)
+    _lib.check(lib.efd_traj_p_at_t_batch(dsrc.data_ptr(), B, float(xtol), float(rtol),
+                                         out.data_ptr(), out.data_ptr() + 8 * B,
+                                         strm.cuda_stream), "efd_traj_p_at_t_batch", lib)
+    if prof is not None:
+        prof[1].record(strm)
+    host = _download_ints(lib, out.view(torch.int32), strm, state)
+    p0 = host[:2 * B].view(np.float64).copy()
+    status = host[2 * B:3 * B]
+    p0[status != 0] = np.nan
+    return p0, np.flatnonzero(status != 0)
 
 
 def get_p_at_t(traj_module, t_out, traj_args, index_of_p=3, index_of_a=2, index_of_e=4,

@@ -14,7 +14,8 @@ the stand-ins of trajectory.py / amplitude.py (NOT FEW physics; SURVEY.md sectio
 The FD summation itself runs in libemrifd.so on the GPU.
 The batched calls (generate_batch, spectrum_batch, the likelihood) can also take the amplitudes
 and the mode selection on the GPU (upstream="device": efd_modes_select_batch); the trajectory
-then is the only host part. mode_selector_kwargs=dict(sensitivity_fn=...) makes eps a fraction of
+then is the only host part, and with trajectory="device" beside it (efd_traj_batch) none is
+left. mode_selector_kwargs=dict(sensitivity_fn=...) makes eps a fraction of
 noise-weighted power on either route (amplitude.ModeSelector; FEW's kwarg as recalled).
 `use_gpu` selects the return type (torch tensors on the GPU, or numpy copies); the compute
 always runs on the GPU -- there is no CPU fallback.
@@ -232,8 +233,16 @@ class FastSchwarzschildEccentricFlux:
             self._ylm_dev[key] = y
         return y
 
+    def device_trajectories(self, calls, device=None, stream=None, state=None):
+        """The trajectories of `calls` (prepare() argument tuples, any number) on the device in
+        one launch (EMRIInspiral.device_batch): per call the seven device views (t, p, e,
+        Phi_phi, Phi_r, f_phi, f_r), device_inputs_batch's `trajs`."""
+        return self.inspiral_generator.device_batch(
+            [(c[0], c[1], c[2], c[3], c[7], c[8], c[9]) for c in calls], device=device,
+            stream=stream, state=state)[0]
+
     def device_inputs_batch(self, calls, include_minus_m=True, device=None, stream=None,
-                            state=None, futures=None):
+                            state=None, futures=None, trajs=None):
         """summation.DeviceInputs of 1..EFD_BATCH_MAX sources with the amplitudes and the mode
         selection made on the device (efd_modes_select_batch): prepare() for batched callers,
         with only the trajectory on the host. `calls` are prepare() argument tuples (M, mu, p0,
@@ -247,7 +256,11 @@ class FastSchwarzschildEccentricFlux:
         fields are views into the upload and the selection's output buffers: no amplitude array
         crosses PCIe. The mode table is uploaded once per generator, Ylm once per viewing
         angle. state: a dict the caller keeps per stream (pinned buffers). last_modes holds the
-        last walker's (l, m, n), last_modes_batch every walker's."""
+        last walker's (l, m, n), last_modes_batch every walker's.
+
+        trajs (device_trajectories' views of these calls, made earlier on a stream that
+        `stream` is ordered after): the seven arrays are those views instead; no trajectory
+        runs on the host and nothing is packed or uploaded here."""
         torch = require_gpu()
         from .summation import DeviceInputs
         calls = [tuple(c) for c in calls]
@@ -265,6 +278,39 @@ class FastSchwarzschildEccentricFlux:
             from .amplitude import NO_TABLE
             raise ValueError("upstream='device': " + NO_TABLE)
         ys = [self._ylms_device(c[4], c[5], dev) for c in calls]
+        if trajs is not None:
+            views = [list(v) for v in trajs]
+            if len(views) != n or any(int(v[0].numel()) < 2 for v in views):
+                raise ValueError("trajs: one trajectory of at least 2 knots per call")
+        else:
+            views = self._upload_trajectories(calls, futures, dev, strm, state)
+        K = amp.num_teuk_modes
+        walkers, fields = [], []
+        for v, y, c in zip(views, ys, calls):                 # v: t p e Pphi Pr fphi fr
+            fields.append(v)
+            walkers.append(dict(p=v[1], e=v[2], ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=c[10],
+                                include_minus_m=include_minus_m, teuk=None))
+            if weighted:   # the uploaded knot frequencies: the weighting costs no transfer
+                walkers[-1].update(f_phi=v[5], f_r=v[6])
+        from .amplitude import device_select
+        res = device_select(table, K, walkers, dev, strm, state, psd=psd)   # (synchronises strm)
+        for r in res:
+            _check_kept(r["keep_host"])
+        out, modes = [], []
+        for v, r in zip(fields, res):
+            out.append(DeviceInputs(t=v[0], phi_phi=v[3], phi_r=v[4], f_phi=v[5], f_r=v[6],
+                                    amp=r["amp"], m=r["m"], n=r["n"], ylm_p=r["ylm_p"],
+                                    ylm_m=r["ylm_m"], nt=r["nt"], K=r["K"]))
+            keep = r["keep_host"]
+            modes.append((amp.l_arr[keep], amp.m_arr[keep], amp.n_arr[keep]))
+        self.last_modes_batch = modes
+        self.last_modes = modes[-1]
+        return out
+
+    def _upload_trajectories(self, calls, futures, dev, strm, state):
+        """device_inputs_batch's host trajectories (futures, or started here) in one packed
+        pinned upload on strm: per call the seven device views."""
+        torch = require_gpu()
         futures = futures if futures is not None else self.trajectories_async(calls)
         trajs = [f.result() for f in futures]
         # one packed upload: walker i's seven arrays, nt doubles each, from a 256-B boundary
@@ -288,30 +334,8 @@ class FastSchwarzschildEccentricFlux:
         lib = _lib.load()
         _lib.check(lib.efd_upload(dbuf.data_ptr(), pin.data_ptr(), 8 * off, strm.cuda_stream),
                    "efd_upload", lib)
-        K = amp.num_teuk_modes
-        walkers, fields = [], []
-        for tr, o, y, c in zip(trajs, offs, ys, calls):
-            nt = len(tr[0])
-            v = [dbuf[o + k * nt:o + (k + 1) * nt] for k in range(7)]   # t p e Pphi Pr fphi fr
-            fields.append(v)
-            walkers.append(dict(p=v[1], e=v[2], ylm_p=y[:2 * K], ylm_m=y[2 * K:], eps=c[10],
-                                include_minus_m=include_minus_m, teuk=None))
-            if weighted:   # the uploaded knot frequencies: the weighting costs no transfer
-                walkers[-1].update(f_phi=v[5], f_r=v[6])
-        from .amplitude import device_select
-        res = device_select(table, K, walkers, dev, strm, state, psd=psd)   # (synchronises strm)
-        for r in res:
-            _check_kept(r["keep_host"])
-        out, modes = [], []
-        for v, r in zip(fields, res):
-            out.append(DeviceInputs(t=v[0], phi_phi=v[3], phi_r=v[4], f_phi=v[5], f_r=v[6],
-                                    amp=r["amp"], m=r["m"], n=r["n"], ylm_p=r["ylm_p"],
-                                    ylm_m=r["ylm_m"], nt=r["nt"], K=r["K"]))
-            keep = r["keep_host"]
-            modes.append((amp.l_arr[keep], amp.m_arr[keep], amp.n_arr[keep]))
-        self.last_modes_batch = modes
-        self.last_modes = modes[-1]
-        return out
+        return [[dbuf[o + k * len(tr[0]):o + (k + 1) * len(tr[0])] for k in range(7)]
+                for tr, o in zip(trajs, offs)]
 
     def prefetch(self, calls, wait=True, concurrency=None):
         """Run the host upstream of several sources at once: `calls` are prepare() argument
@@ -510,6 +534,18 @@ def _nbytes(d):
 UPSTREAMS = ("host", "device")
 
 
+TRAJECTORIES = ("host", "device")
+
+
+def _check_trajectory(trajectory, upstream):
+    """The batched calls' `trajectory` argument: "host" (the default: the native call on the
+    prefetch pool) or "device" (efd_traj_batch), which needs upstream="device"."""
+    if trajectory not in TRAJECTORIES:
+        raise ValueError(f"trajectory must be one of {TRAJECTORIES}, got {trajectory!r}")
+    if trajectory == "device" and upstream != "device":
+        raise ValueError("trajectory='device' needs upstream='device'")
+
+
 def _check_upstream(upstream, kwargs):
     """The batched calls' `upstream` argument: "host" (the default route) or "device"; explicit
     mode lists keep the host route."""
@@ -646,7 +682,7 @@ class GenerateEMRIWaveform:
     BATCH_GROUP = 16
 
     def generate_batch(self, params, out, T=1.0, dt=10.0, eps=1e-5, f_arr=None, upstream="host",
-                       **kwargs):
+                       trajectory="host", **kwargs):
         """[h+, hx] over f >= 0 of every row of params (B x 14, FEW's order) into out
         (complex128 [B][2][N_pos] on the device): the vectorised form of B calls
         `self(*row, T=T, dt=dt, eps=eps, mask_positive=True)` with return_list=True (bitwise
@@ -662,19 +698,28 @@ class GenerateEMRIWaveform:
         selection of each group run on the device (device_inputs_batch) and feed the same
         preparation and sum. The kept modes are the host route's; the amplitudes agree with it
         to rounding (1e-14 max|A|), so the templates agree to the mode sum's response to that,
-        not bitwise. Not with an explicit mode_selection list."""
+        not bitwise. Not with an explicit mode_selection list.
+
+        trajectory="device" (with upstream="device" only): the trajectories of all rows are
+        integrated on the device in one launch ahead of the first group (efd_traj_batch) and
+        the groups read their knots in place; no host trajectory, no packed upload. The device
+        integration places its knots as another valid integration would, so the templates
+        differ from the host trajectory's by the mode sum's response to that."""
         torch = require_gpu()
         _check_upstream(upstream, kwargs)
+        _check_trajectory(trajectory, upstream)
         npos = self._batch_grid(T, dt, f_arr)[1]
         B = len(np.asarray(params, dtype=np.float64).reshape(-1, 14))
         if tuple(out.shape) != (B, 2, npos) or out.dtype != torch.complex128:
             raise ValueError(f"out must be complex128 [{B}][2][{npos}]")
         return self._run_batch(params, out, lambda j: dict(hp=torch.view_as_real(out[j, 0]),
                                                            hc=torch.view_as_real(out[j, 1])),
-                               T, dt, eps, f_arr, kwargs, upstream=upstream)
+                               T, dt, eps, f_arr, kwargs, upstream=upstream,
+                               trajectory=trajectory)
 
     def spectrum_batch(self, params, out, T=1.0, dt=10.0, eps=1e-5, f_arr=None, lanes=None,
-                       check=True, lanes_host=None, upstream="host", **kwargs):
+                       check=True, lanes_host=None, upstream="host", trajectory="host",
+                       **kwargs):
         """The two-sided spectra S = h+ - i hx of every row of params into the rows of out
         (complex128 [B][N], contiguous rows, on the device): generate_batch's device groups
         with the sum writing S (the windowed templates' input, fdutils.HannConvolution); bitwise
@@ -684,9 +729,11 @@ class GenerateEMRIWaveform:
         calls check_batch() once its own work on the spectra is queued. lanes_host (pinned int32
         [B][2], with lanes): the lane ranges are gathered right after each group's preparation
         and copied there on a side stream, beside the sum; lanes_ready() waits for those copies
-        only, so the host can read them while the sums run. upstream: as generate_batch."""
+        only, so the host can read them while the sums run. upstream, trajectory: as
+        generate_batch."""
         torch = require_gpu()
         _check_upstream(upstream, kwargs)
+        _check_trajectory(trajectory, upstream)
         n = self._batch_grid(T, dt, f_arr)[0]
         B = len(np.asarray(params, dtype=np.float64).reshape(-1, 14))
         if (out.dim() != 2 or tuple(out.shape) != (B, n) or out.dtype != torch.complex128
@@ -701,7 +748,7 @@ class GenerateEMRIWaveform:
             raise ValueError(f"lanes_host must be pinned int32 [{B}][2] beside lanes")
         return self._run_batch(params, out, lambda j: dict(out=torch.view_as_real(out[j])),
                                T, dt, eps, f_arr, kwargs, lanes=lanes, check=check,
-                               lanes_host=lanes_host, upstream=upstream)
+                               lanes_host=lanes_host, upstream=upstream, trajectory=trajectory)
 
     def lanes_ready(self):
         """Wait for the last spectrum_batch's lane-range copies into lanes_host (each group's
@@ -735,11 +782,11 @@ class GenerateEMRIWaveform:
         return int(freq.numel()), int(freq.numel()) - cw._k0
 
     def _run_batch(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes=None,
-                   check=True, lanes_host=None, upstream="host"):
+                   check=True, lanes_host=None, upstream="host", trajectory="host"):
         torch = require_gpu()
         if upstream == "device":
             return self._run_batch_device(params, out, outputs, T, dt, eps, f_arr, kwargs,
-                                          lanes, check, lanes_host)
+                                          lanes, check, lanes_host, trajectory)
         from .summation import BatchPreparer, sum_batch
         cw = self.waveform_generator.create_waveform
         params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
@@ -841,16 +888,17 @@ class GenerateEMRIWaveform:
         return calls, scales
 
     def device_group(self, st, slot, calls, scales, futures, freq, k0, outputs=None,
-                     include_minus_m=True):
+                     include_minus_m=True, trajs=None):
         """One group of at most EFD_BATCH_MAX walkers on slot `slot` of _device_state's st:
         device_inputs_batch and efd_modesum_prepare_batch on the slot's stream. Returns the
-        (engine, launch_kwargs) jobs for sum_batch / sum_batch_loglike on that stream."""
+        (engine, launch_kwargs) jobs for sum_batch / sum_batch_loglike on that stream. trajs:
+        the group's device trajectories (device_trajectories), in place of futures."""
         torch = require_gpu()
         from .summation import prepare_batch
         gs = st["streams"][slot]
         inps = self.waveform_generator.device_inputs_batch(
             calls, include_minus_m=include_minus_m, device=st["device"], stream=gs,
-            state=st["sel"][slot], futures=futures)
+            state=st["sel"][slot], futures=futures, trajs=trajs)
         jobs = [(eng, dict(dict(inp=inp, freq=freq, out=None, grid_symmetric=True, scale=sc,
                                 k0=k0), **(outputs(i) if outputs is not None else {})))
                 for i, (eng, inp, sc) in enumerate(zip(st["engines"][slot], inps, scales))]
@@ -877,8 +925,14 @@ class GenerateEMRIWaveform:
                                             st["streams"][slot].cuda_stream) != _lib.EFD_OK:
                 raise _lib.EFDError(f"efd_modesum: {_lib.last_error(lib)}")
 
+    def device_trajectories(self, st, calls):
+        """The device trajectories of all of a call's rows, launched once on the current stream
+        ahead of the first group (the caller orders the slots' streams after it)."""
+        return self.waveform_generator.device_trajectories(
+            calls, device=st["device"], state=st.setdefault("traj", {}))
+
     def _run_batch_device(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes, check,
-                          lanes_host):
+                          lanes_host, trajectory="host"):
         import ctypes
         torch = require_gpu()
         from .summation import sum_batch
@@ -893,7 +947,9 @@ class GenerateEMRIWaveform:
         include_minus_m = bool(kwargs.get("include_minus_m", True))
         st = self._device_state(out.device, cw.caustic)
         calls, scales = self.device_calls(params, T, eps)
-        futs = gen.trajectories_async(calls)
+        on_device = trajectory == "device"
+        futs = gen.trajectories_async(calls) if not on_device else [None] * B
+        trajs = self.device_trajectories(st, calls) if on_device else [None] * B
         G = min(self.BATCH_GROUP, _lib.EFD_BATCH_MAX)
         cur = torch.cuda.current_stream(out.device)
         for gs in st["streams"]:
@@ -906,8 +962,9 @@ class GenerateEMRIWaveform:
                 gs = st["streams"][slot]
                 used.add(slot)
                 jobs = self.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
-                                         futs[g0:g0 + G], freq, kc,
-                                         lambda i, g0=g0: outputs(g0 + i), include_minus_m)
+                                         None if on_device else futs[g0:g0 + G], freq, kc,
+                                         lambda i, g0=g0: outputs(g0 + i), include_minus_m,
+                                         trajs[g0:g0 + G] if on_device else None)
                 sum_batch(jobs, stream=gs.cuda_stream)
                 if lanes is not None:
                     lib = jobs[0][0].lib
@@ -924,7 +981,8 @@ class GenerateEMRIWaveform:
                         st["lanes_ev_used"].append(lev)
         finally:
             for f in futs:
-                f.cancel()
+                if f is not None:
+                    f.cancel()
             for slot in used:
                 cur.wait_stream(st["streams"][slot])
         if check:

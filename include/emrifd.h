@@ -808,6 +808,51 @@ int efd_modes_select_batch_weighted(const efd_modes_table* tab, const efd_modes_
                                     const efd_modes_weight* wt, const efd_psd_table* psd,
                                     int32_t count, void* stream);
 
+/*
+ * Inspiral trajectories and the p0 solve on the device for batched callers (not part of the
+ * reference's interface; csrc/emrifd_traj.hip). STAND-IN PHYSICS, NOT FEW: efd_host_trajectory's
+ * and efd_host_p_at_t's equations and integrator (scipy RK45's Dormand-Prince 5(4), step control,
+ * dense output, terminal separatrix event, Brent's roots), one wavefront per source: lane i
+ * evaluates node i of the 64-node frequency quadrature. Both calls are asynchronous on `stream`,
+ * allocation-free, without host synchronisation or atomics; they accept any count >= 1, and
+ * each source's outputs are bitwise those of its own count = 1 call. The host forms are the
+ * reference, followed operation for operation (no fused multiply-add, the quadrature summed in
+ * the host's order, correctly rounded powers): the knots are the host's bit for bit until one of
+ * the host's pow calls is not correctly rounded (0.08 % of them), and within rounding after.
+ *
+ * efd_traj_batch: source i's knots into knots[i][7][max_len] (t [s], p, e, Phi_phi, Phi_r, f_phi,
+ *   f_r [Hz], efd_host_trajectory's seven arrays), nt[i] knots, 2 <= max_len <=
+ *   EFD_TRAJ_MAX_LEN. status[i] is written for every source; nt[i] only with EFD_TRAJ_OK. A source
+ *   with another status stores nothing past its max_len knots and leaves the others untouched.
+ * efd_traj_p_at_t_batch: p0[i] whose inspiral plunges after src[i].T = t_out years
+ *   (efd_host_p_at_t with its default bracket; src[i].p0 is ignored), NaN unless status[i] is
+ *   EFD_TRAJ_OK.
+ * EFD_ERR_ARG before any launch: NULL pointers, count < 1, max_len out of range.
+ *
+ * Every device loop is bounded: an integration by 4 EFD_TRAJ_MAX_LEN accepted plus rejected steps,
+ * a root by 100 iterations, the bracket by 7 expansions.
+ */
+typedef struct efd_traj_source {
+    double M, mu, p0, e0, Phi_phi0, Phi_r0, T, rtol, atol;
+} efd_traj_source;
+
+#define EFD_TRAJ_MAX_LEN 1024
+#define EFD_TRAJ_OK 0
+#define EFD_TRAJ_BAD_SOURCE 1   /* not finite, M, mu, T, rtol or atol <= 0, p0 inside the buffer */
+#define EFD_TRAJ_TOO_LONG 2     /* more than max_len knots                                       */
+#define EFD_TRAJ_STEP_FAILED 3  /* step size below the representable minimum (the host's -2)     */
+#define EFD_TRAJ_STEP_CAP 4     /* more than 4 EFD_TRAJ_MAX_LEN steps in one integration         */
+#define EFD_TRAJ_NO_BRACKET 5   /* p0 solve: t_out shorter than the plunge from the buffer, or
+                                 * no upper bracket end below 500                                */
+
+int efd_traj_batch(const efd_traj_source* src /* device [count] */, int32_t count,
+                   int32_t max_len, double* knots /* device [count][7][max_len] */,
+                   int32_t* nt /* device [count] */, int32_t* status /* device [count] */,
+                   void* stream);
+int efd_traj_p_at_t_batch(const efd_traj_source* src /* p0 ignored, T = t_out in years */,
+                          int32_t count, double xtol, double rtol_root,
+                          double* p0 /* device [count] */, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

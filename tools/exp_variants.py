@@ -42,7 +42,7 @@ def build(specs):
     # objects of everything else -- the host objects (twin, upstream) and the window and
     # reduction units -- so it exports the whole ABI
     assert _build.HIP_UNITS[:2] == [SRC, PREP_SRC]
-    objs = _build.HOST_OBJS + [_build.obj_path(s) for s in _build.HIP_UNITS[2:]]
+    objs = _build.HOST_OBJS + [_build.obj_path(s) for s in _build.ALL_HIP_UNITS[2:]]
     _build.build(force=not all(map(os.path.exists, objs)))   # (a library can travel without them)
     os.makedirs(EXP, exist_ok=True)
     jobs = []
