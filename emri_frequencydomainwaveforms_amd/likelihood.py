@@ -209,14 +209,7 @@ class Likelihood:
             for i in range(num_likes):
                 h = self._as_channels(h_all[i])
                 self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
-        elif (self.device_upstream and getattr(tm, "can_pipeline", False) and not args
-              and (host := self._get_ll_device(tm, params, kwargs, out)) is not None):
-            if self.noise_has_been_added:
-                raise NotImplementedError
-            if self.use_gpu and self.return_cupy:
-                return out
-            return host
-        elif (getattr(tm, "can_pipeline", False) and self.fused_likelihood
+        elif (getattr(tm, "can_pipeline", False)
               and (host := self._get_ll_fused(tm, params, args, kwargs, out)) is not None):
             if self.noise_has_been_added:
                 raise NotImplementedError
@@ -310,6 +303,13 @@ class Likelihood:
     # (BatchPreparer.flush_loglike, efd_fused_group); False: the Python steps of round 5
     FUSED_NATIVE_GROUP = True
 
+    # amplitudes and mode selection on the device (pe.setup(upstream="device")): the fused
+    # path's groups are fed by the generator's device_inputs_batch; False keeps the host upstream
+    device_upstream = False
+    # with device_upstream: the walkers' trajectories on the device too, all of a call's in one
+    # launch ahead of the first group (pe.setup(trajectory="device"); efd_traj_batch)
+    device_trajectory = False
+
     def _get_ll_fused(self, tm, params, args, kwargs, out):
         """The pipelined path with the likelihood fused into the mode sum: per group of
         FUSED_GROUP walkers, the template chain collects each walker's host inputs
@@ -318,22 +318,46 @@ class Likelihood:
         group's log-likelihoods into its slice of out (the templates never reach HBM; a
         cross-stream wait between preparation and sum cost ~12 us of idle device per group on
         config 4's chain, tools/chain_timeline.py). A group's next flush is behind its sum in
-        stream order; the streams join once, before the copy out. Returns the log-likelihoods
-        on the host (one synchronisation per batch), or None, before queueing anything, when
-        the template's grid is not symmetric (the caller takes the per-walker path). A walker
-        whose preparation or sum raised a device-side error comes back NaN from the kernel
+        stream order; the streams join once, before the copy out.
+
+        With device_upstream only the feed of a group differs: the walkers' trajectories start
+        on the prefetch pool at once (device_trajectory: all of them in one launch on the
+        current stream instead); per balanced group of at most EFD_BATCH_MAX walkers the
+        generator's device_inputs_batch (packed trajectory upload, efd_modes_select_batch, the
+        read of the group's K) runs on the group's stream and BatchPreparer.flush_device
+        prepares the group from what it left on the device, so a group's device chain runs
+        beside the next group's trajectories and selection. The groups live in the host
+        route's preparer: a Likelihood switched between the routes keeps its workspaces.
+
+        Returns the log-likelihoods on the host (one synchronisation per batch), or None,
+        before queueing anything, when the template's grid is not symmetric, or neither route
+        applies (fused_likelihood off; the device route needs a GenerateEMRIWaveform, keyword
+        waveform arguments and no explicit mode list, and otherwise leaves the walkers to the
+        host route): the caller then takes the per-walker path. A walker whose preparation or
+        sum raised a device-side error comes back NaN from the kernel
         (efd_modesum_sum_loglike), and only then are the groups' status flags read, which
         raises."""
         torch = self.torch
         from .summation import BatchPreparer
-        if not self._fused_grid_ok(tm, kwargs):
+        from .waveform import GenerateEMRIWaveform
+        few = getattr(tm, "waveform_generator", None)
+        device = (self.device_upstream and not args and isinstance(few, GenerateEMRIWaveform)
+                  and kwargs.get("mode_selection") is None)
+        if not (device or self.fused_likelihood) or not self._fused_grid_ok(tm, kwargs):
             return None
-        _prefetch(tm, params, args, kwargs)
+        if device:
+            cw = few.waveform_generator.create_waveform
+            freq, _ = cw._grid(kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("f_arr"))
+            k0 = cw.positive_start()
+            if getattr(tm, "_suffix_k0", k0) != k0:
+                raise ValueError("positive_frequency_mask does not match the generator's grid")
+        else:
+            _prefetch(tm, params, args, kwargs)
         n = len(params)
         if n == 0:
             return np.empty(0, dtype=np.float64)
-        ngroups = -(-n // self.FUSED_GROUP)
-        G = -(-n // ngroups)                       # balanced groups of at most FUSED_GROUP
+        ngroups = -(-n // (_lib.EFD_BATCH_MAX if device else self.FUSED_GROUP))
+        G = -(-n // ngroups)                       # balanced groups of at most that many
         caustic = getattr(getattr(getattr(tm.waveform_generator, "waveform_generator", None),
                                   "create_waveform", None), "caustic", "uniform")
         F = self._fused
@@ -342,10 +366,21 @@ class Likelihood:
                               device=self.device)
             # the group streams' handles, for the orderings below (efd_stream_order: one event
             # record and one stream wait each, in C)
-            gst = [B.stream(gi).cuda_stream for gi in range(len(B.groups))]
-            F = self._fused = dict(prep=B, gst=gst, order=(ctypes.c_void_p * len(gst))(*gst))
+            F = self._fused = dict(prep=B, gst=[B.stream(gi).cuda_stream
+                                                for gi in range(len(B.groups))])
         B, gst = F["prep"], F["gst"]
         lib = B.lib
+        # the device route's trajectories: on the prefetch pool, or all of them in one launch on
+        # the current stream, which the groups' streams are ordered after below
+        futs, trajs = [], None
+        if device:
+            B.restart()
+            calls, scales = few.device_calls(params, kwargs.get("T", 1.0),
+                                             kwargs.get("eps", 1e-5))
+            if self.device_trajectory:
+                trajs = few.device_trajectories(calls, self.device, F.setdefault("traj", {}))
+            else:
+                futs = few.waveform_generator.trajectories_async(calls)
         # the group streams this batch's flushes take (B's rotation from its next group), after
         # the work queued so far on the current stream: one stream wait each
         key = ("ord", gst.index(B.next_flush()[0].cuda_stream), min(ngroups, len(gst)))
@@ -363,25 +398,35 @@ class Likelihood:
         try:
             batch = getattr(tm, "submit_batch", None)
             for g0 in range(0, n, G):
-                if batch is not None:
-                    batch(B, params[g0:g0 + G], *args, **kwargs)
+                g = slice(g0, g0 + G)
+                if device:
+                    sst = B.next_flush()[0]
+                    inps = few.waveform_generator.device_inputs_batch(
+                        calls[g], include_minus_m=bool(kwargs.get("include_minus_m", True)),
+                        device=self.device, stream=sst, state=B.next_select(),
+                        futures=futs[g] if trajs is None else None,
+                        trajs=trajs[g] if trajs is not None else None)
+                    gi, jobs = B.flush_device(inps, freq, scales[g], k0)
                 else:
-                    for i in range(g0, min(n, g0 + G)):
-                        tm.submit(B, None, *params[i], *args, order=False, prepare_only=True,
-                                  **kwargs)
-                # the tile constants are made on the group's stream (once per grid), before the
-                # sum that reads them
-                sst, freq, k0 = B.next_flush()
-                if native:
-                    tc = self._tile_constants(freq, k0, sst, F)
-                    used.append(B.flush_loglike(self._d, self._w_templ, out, tile_const=tc,
-                                                out_off=g0))
-                else:
+                    if batch is not None:
+                        batch(B, params[g], *args, **kwargs)
+                    else:
+                        for i in range(g0, min(n, g0 + G)):
+                            tm.submit(B, None, *params[i], *args, order=False,
+                                      prepare_only=True, **kwargs)
+                    sst, freq, k0 = B.next_flush()
+                    if native:
+                        # the tile constants are made on the group's stream (once per grid),
+                        # before the sum that reads them
+                        tc = self._tile_constants(freq, k0, sst, B)
+                        used.append(B.flush_loglike(self._d, self._w_templ, out, tile_const=tc,
+                                                    out_off=g0))
+                        continue
                     gi, jobs = B.flush()
-                    used.append(gi)
-                    tc = self._tile_constants(freq, k0, sst, F)
-                    B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
-                                  sst.cuda_stream, tile_const=tc)
+                used.append(gi)
+                tc = self._tile_constants(freq, k0, sst, B)
+                B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
+                              sst.cuda_stream, tile_const=tc)
             # the other groups' streams join the last one, which copies out
             last = used[-1]
             for gj in sorted(set(used) - {last}):
@@ -390,13 +435,15 @@ class Likelihood:
             _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, gst[last]),
                        "efd_download", lib)
         finally:
+            for f in futs:
+                f.cancel()
             B.drop_pending()
             # `out` belongs to the current stream: nothing may still write it when it is
             # returned, or freed after an exception
             if sys.exc_info()[0] is not None:
-                # a failure inside a flush (staging, workspace growth, preparation) may leave
-                # a group's upload or preparation queued before that group reached `used`: wait
-                # for every group stream, not only the recorded ones
+                # a failure inside a flush (staging, workspace growth, the selection, the
+                # preparation) may leave a group's work queued before that group reached
+                # `used`: wait for every group stream, not only the recorded ones
                 for gi in range(len(gst)):
                     B.stream(gi).synchronize()
             elif used:
@@ -406,107 +453,15 @@ class Likelihood:
             B.wait()   # device-side errors of the groups' workspaces (sticky across reuse)
         return host
 
-    # amplitudes and mode selection on the device (pe.setup(upstream="device")): get_ll's
-    # pipelined templates on symmetric grids take _get_ll_device; False keeps the host upstream
-    device_upstream = False
-    # with device_upstream: the walkers' trajectories on the device too, all of a call's in one
-    # launch ahead of the first group (pe.setup(trajectory="device"); efd_traj_batch)
-    device_trajectory = False
-
-    def _get_ll_device(self, tm, params, kwargs, out):
-        """The fused likelihood with the upstream's amplitudes and mode selection on the device:
-        the walkers' trajectories start on the prefetch pool at once; per balanced group of at
-        most EFD_BATCH_MAX walkers, on one of two rotating streams, the generator's
-        device_group (packed trajectory upload, efd_modes_select_batch, the read of the group's
-        K and efd_modesum_prepare_batch) and one efd_modesum_sum_loglike_ex with the tile
-        constants write the group's log-likelihoods into its slice of out; a group's device
-        chain runs beside the next group's trajectories and selection. One copy out per batch.
-        With device_trajectory the trajectories of all walkers are integrated on the device in
-        one launch on the current stream first (no pool, no packed upload).
-        Returns the log-likelihoods on the host, or None, before queueing anything, when the
-        template is not a GenerateEMRIWaveform on a symmetric grid or the call names an
-        explicit mode list (the caller then takes the host upstream's path)."""
-        import types
-        torch = self.torch
-        from .summation import sum_batch_loglike
-        few = getattr(tm, "waveform_generator", None)
-        if (not hasattr(few, "device_group") or kwargs.get("mode_selection") is not None
-                or not self._fused_grid_ok(tm, kwargs)):
-            return None
-        cw = few.waveform_generator.create_waveform
-        T, dt, eps = kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("eps", 1e-5)
-        freq, _ = cw._grid(T, dt, kwargs.get("f_arr"))
-        k0 = cw.positive_start()
-        if getattr(tm, "_suffix_k0", k0) != k0:
-            raise ValueError("positive_frequency_mask does not match the generator's grid")
-        n = len(params)
-        if n == 0:
-            return np.empty(0, dtype=np.float64)
-        ngroups = -(-n // _lib.EFD_BATCH_MAX)
-        G = -(-n // ngroups)                       # balanced groups of at most EFD_BATCH_MAX
-        st = few._device_state(self.device, cw.caustic)
-        lib = st["engines"][0][0].lib
-        D = st.get("like")
-        if D is None:
-            gst = [s.cuda_stream for s in st["streams"]]
-            D = st["like"] = dict(prep=types.SimpleNamespace(lib=lib), gst=gst,
-                                  order=(ctypes.c_void_p * len(gst))(*gst))
-        gst = D["gst"]
-        calls, scales = few.device_calls(params, T, eps)
-        on_device = self.device_trajectory
-        # the trajectories: on the prefetch pool, or (device_trajectory) all of them in one
-        # launch on the current stream, which the slots' streams are ordered after below
-        futs = few.waveform_generator.trajectories_async(calls) if not on_device else []
-        trajs = few.device_trajectories(st, calls) if on_device else None
-        _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
-                                        D["order"], len(gst)), "efd_stream_order", lib)
-        pin = D.get("pin")
-        if pin is None or pin.numel() < n:
-            pin = D["pin"] = torch.empty(max(n, 64), dtype=torch.float64, pin_memory=True)
-        include_minus_m = bool(kwargs.get("include_minus_m", True))
-        last = None
-        try:
-            for gidx, g0 in enumerate(range(0, n, G)):
-                slot = gidx % 2
-                jobs = few.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
-                                        None if on_device else futs[g0:g0 + G], freq, k0, None,
-                                        include_minus_m,
-                                        trajs[g0:g0 + G] if on_device else None)
-                tc = self._tile_constants(freq, k0, st["streams"][slot], D)
-                sum_batch_loglike(jobs, self._d, self._w_templ, out[g0:g0 + len(jobs)],
-                                  stream=gst[slot], tile_const=tc)
-                last = slot
-            if ngroups > 1:   # the other slot's stream joins the last one, which copies out
-                _lib.check(lib.efd_stream_order(gst[1 - last], (ctypes.c_void_p * 1)(gst[last]),
-                                                1), "efd_stream_order", lib)
-            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, gst[last]),
-                       "efd_download", lib)
-        finally:
-            for f in futs:
-                f.cancel()
-            # `out` belongs to the current stream: nothing may still write it when it is
-            # returned, or freed after an exception
-            if sys.exc_info()[0] is not None:
-                for s in st["streams"]:
-                    s.synchronize()
-            elif last is not None:
-                st["streams"][last].synchronize()
-        host = pin[:n].numpy().copy()
-        if np.isnan(host).any():
-            few._device_check()   # device-side errors of the slots' workspaces raise
-        else:
-            st["used"] = [0, 0]
-        return host
-
     # tiles no harmonic reaches take a precomputed partial instead of re-reading d and w
     # (efd_loglike_tile_constants; bitwise the same logL)
     fused_tile_constants = True
 
-    def _tile_constants(self, freq, k0, stream, fused):
+    def _tile_constants(self, freq, k0, stream, prep):
         """The fused sum's per-tile constants for (d, w_templ) on this grid, made once on
         `stream`, a group's (ordered after the data's creation: it waits on the current
-        stream). Every stream of fused["order"] is then ordered after `stream`, so any group's
-        later sum may read them."""
+        stream). Every group stream of the BatchPreparer `prep` is then ordered after `stream`,
+        so any group's later sum may read them."""
         if not self.fused_tile_constants:
             return None
         from .summation import loglike_tile_constants
@@ -516,9 +471,10 @@ class Likelihood:
         if tc is None or tc[0] != key:
             tc = self._tile_const = (key, loglike_tile_constants(
                 self._d, self._w_templ, nf, k0, stream.cuda_stream))
-            lib = fused["prep"].lib
-            _lib.check(lib.efd_stream_order(stream.cuda_stream, fused["order"],
-                                            len(fused["order"])), "efd_stream_order", lib)
+            order = [g.stream.cuda_stream for g in prep.groups]
+            _lib.check(prep.lib.efd_stream_order(
+                stream.cuda_stream, (ctypes.c_void_p * len(order))(*order), len(order)),
+                "efd_stream_order", prep.lib)
         return tc[1]
 
     def _fused_grid_ok(self, tm, kwargs):

@@ -81,20 +81,16 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     for the noise-weighted mode selection (amplitude.ModeSelector)."""
     if template not in ("fd", "td"):
         raise ValueError("template: 'fd' or 'td'")
-    if upstream not in ("host", "device"):
-        raise ValueError("upstream: 'host' or 'device'")
+    from .waveform import GenerateEMRIWaveform, _check_trajectory, _check_upstream
+    _check_upstream(upstream, {})
     if upstream == "device" and template != "fd":
         raise ValueError("upstream='device' is the FD template's")
-    if trajectory not in ("host", "device"):
-        raise ValueError("trajectory: 'host' or 'device'")
-    if trajectory == "device" and upstream != "device":
-        raise ValueError("trajectory='device' needs upstream='device'")
+    _check_trajectory(trajectory, upstream)
     if template == "td" and downsample:
         raise ValueError("Cannot run downsampling with time domain template")   # emri_pe.py:326
     from .fdutils import get_fd_waveform_fromFD, get_fd_waveform_fromTD, get_sensitivity
     from .likelihood import Likelihood
     from .trajectory import EMRIInspiral, get_p_at_t
-    from .waveform import GenerateEMRIWaveform
     if start_cov is not None and np.shape(start_cov) != (6, 6):
         raise ValueError(f"start_cov must be 6 x 6, got {np.shape(start_cov)}")
 

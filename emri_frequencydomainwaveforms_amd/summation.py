@@ -599,6 +599,9 @@ class _Group:
         self.pin_done = torch.cuda.Event()
         self.pin_done.record(self.stream)
         self.busy = None      # release()'s event: the group's last sum has read its workspaces
+        # the device upstream's selection state (device_inputs_batch's `state`: its pinned and
+        # output buffers; the group's previous sum reads them on this stream)
+        self.select = {}
         self.used = False
         self.n = 0            # walkers of the group's last flush
         # the walkers' argument structs, with the args** table, the workspace pointer and size
@@ -638,6 +641,8 @@ class BatchPreparer:
     workspaces, rotate: a group is reused after the event its sum recorded (`release`), so
     group i+1's preparation runs beside group i's sum. Per walker the host pays the packing
     copies and one argument struct instead of ~10 launches (efd_modesum_prepare).
+    `flush_device()` feeds the next group from inputs the device upstream left on the device
+    instead; everything behind the feed is the same.
     """
 
     # walkers per flush: up to GROUP_MAX, staged and uploaded together; the preparation and sum
@@ -693,11 +698,32 @@ class BatchPreparer:
         freq, k0 = (p[0][1], p[0][4]) if p else (None, None)
         return self.groups[self._next].stream, freq, k0
 
+    def restart(self):
+        """The next flush takes the first group again. The device upstream starts every batch
+        there, so a batch of one group keeps to one set of workspaces (reuse is ordered by the
+        group's stream and `busy`, as for any rotation)."""
+        self._next = 0
+
+    def next_select(self):
+        """The selection state of the group the next flush rotates to: device_inputs_batch's
+        `state` for the walkers of the next flush_device(), run on next_flush()'s stream."""
+        return self.groups[self._next].select
+
     def workspace_ptrs(self, gi):
         """Group gi's workspace pointer array (void*[group]; its last flush's walkers first)."""
         return self.groups[gi].pw
 
     # -- one batch -----------------------------------------------------------------------------
+    def _rotate(self):
+        """(group index, group) of the next flush: the groups rotate, and the group's stream
+        waits for the sum that last read its workspaces."""
+        gi = self._next
+        self._next = (gi + 1) % len(self.groups)
+        G = self.groups[gi]
+        if G.busy is not None:
+            G.stream.wait_event(G.busy)
+        return gi, G
+
     def _take(self, what):
         """The pending walkers for the next group: (group index, group, walkers, template
         struct). The walkers are checked first (one grid; symmetry, k0 and accumulate agree);
@@ -713,11 +739,7 @@ class BatchPreparer:
                 raise ValueError("flush: the walkers of a group share one frequency grid")
             if s != sym or k != k0 or a != acc:
                 raise ValueError("flush: grid symmetry, k0 and accumulate must agree in a group")
-        gi = self._next
-        self._next = (gi + 1) % len(self.groups)
-        G = self.groups[gi]
-        if G.busy is not None:
-            G.stream.wait_event(G.busy)
+        gi, G = self._rotate()
         G.pin_done.synchronize()
         key = (freq.data_ptr(), nf, sym, acc, k0)
         if G.tmpl is None or G.tmpl[0] != key:
@@ -840,14 +862,37 @@ class BatchPreparer:
         _lib.check(lib.efd_upload(G.dbuf.data_ptr(), G.pin.data_ptr(), total, st.cuda_stream),
                    "efd_upload", lib)
         G.pin_done.record(st)
-        jobs = self._size_each(G, shape, freq, k0, sym)
+        return gi, self._prepare(G, self._size_each(G, shape, freq, k0, sym))
+
+    def flush_device(self, inputs, freq, scales, k0):
+        """flush() for 1..group walkers whose inputs are on the device already: `inputs` are
+        DeviceInputs made on next_flush()'s stream with next_select()'s state
+        (device_inputs_batch), `scales` their complex scales; a symmetric grid, accumulate off.
+        Nothing is staged or uploaded: the groups rotate as for flush(), every engine is sized
+        for its own walker (a grown workspace on the group's stream) and the walkers' argument
+        structs go into the group's array, so the jobs, sum_loglike, workspace_ptrs, last_jobs
+        and wait() are flush()'s. Returns (group index, jobs)."""
+        n = len(inputs)
+        if not 1 <= n <= self.group or len(scales) != n or self._pending:
+            raise ValueError(f"flush_device takes 1..{self.group} walkers, a scale each, and "
+                             "none pending for flush()")
+        gi, G = self._rotate()
+        jobs = self._size_each(G, np.array([(inp.nt, inp.K) for inp in inputs]), freq, k0, True)
+        for i, (inp, sc) in enumerate(zip(inputs, scales)):
+            G.args[i] = G.engines[i]._args(inp, freq, None, True, sc, k0=k0)[0]
+        return gi, self._prepare(G, jobs)
+
+    def _prepare(self, G, jobs):
+        """efd_modesum_prepare_batch over the group's first len(jobs) walkers on its stream;
+        the jobs become the preparer's last."""
+        n, lib, st = len(jobs), self.lib, G.stream.cuda_stream
         for c0, cnt, pa_c, pw_c, pb_c in G.chunks[n]:
-            _lib.check(lib.efd_modesum_prepare_batch(pa_c, pw_c, pb_c, cnt, st.cuda_stream),
+            _lib.check(lib.efd_modesum_prepare_batch(pa_c, pw_c, pb_c, cnt, st),
                        "efd_modesum_prepare_batch", lib)
         G.used = True
         G.n = n
         self._jobs, self._last = jobs, None
-        return gi, jobs
+        return jobs
 
     def flush_loglike(self, d, w, out, tile_const=None, out_off=0):
         """flush() and sum_loglike() of the collected walkers in one native call

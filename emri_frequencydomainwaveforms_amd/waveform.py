@@ -84,6 +84,7 @@ class FastSchwarzschildEccentricFlux:
             self.create_waveform = TDInterpolatedModeSum(use_gpu=use_gpu, **sum_kwargs)
         self.last_modes = None
         self._ylm_cache = {}
+        self._ylm_dev = {}    # _ylms_device's uploads, per viewing angle and device
         self._prefetched = {}
         self._prefetched_bytes = 0
         self._inflight = {}   # prefetch(wait=False): parameters -> the pool's Future
@@ -114,9 +115,8 @@ class FastSchwarzschildEccentricFlux:
         numpy/scipy path below, which serves explicit mode_selection lists)."""
         key = None
         if mode_selection is None:
-            key = (float(M), float(mu), float(p0), float(e0), float(theta), float(phi),
-                   float(dist), float(Phi_phi0), float(Phi_r0), float(T), float(eps),
-                   bool(include_minus_m))
+            key = _prefetch_key((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps),
+                                include_minus_m)
             if self._inflight:
                 with self._lock:
                     fut = self._inflight.pop(key, None)
@@ -223,9 +223,9 @@ class FastSchwarzschildEccentricFlux:
         """_ylms on the device (float64 view of complex [2 K]), uploaded once per viewing angle."""
         torch = require_gpu()
         key = (float(theta), float(phi), dev.type, dev.index)
-        y = self._ylm_dev.get(key) if hasattr(self, "_ylm_dev") else None
+        y = self._ylm_dev.get(key)
         if y is None:
-            if not hasattr(self, "_ylm_dev") or len(self._ylm_dev) > 64:
+            if len(self._ylm_dev) > 64:
                 self._ylm_dev = {}
             host = np.ascontiguousarray(self._ylms(theta, phi), dtype=np.complex128)
             y = torch.from_numpy(host.view(np.float64).copy()).to(dev)
@@ -357,9 +357,9 @@ class FastSchwarzschildEccentricFlux:
         # again: prepare() takes those results. Eviction first, and never of this batch's own
         # entries (which would then be recomputed serially in prepare())
         with self._lock:
-            self._evict_inflight({tuple(float(v) for v in c[:11]) + (True,) for c in calls})
+            self._evict_inflight({_prefetch_key(c) for c in calls})
             calls = [c for c in calls
-                     if (k := tuple(float(v) for v in c[:11]) + (True,)) not in self._inflight
+                     if (k := _prefetch_key(c)) not in self._inflight
                      and k not in self._prefetched]
         if not calls:
             return 0
@@ -400,14 +400,13 @@ class FastSchwarzschildEccentricFlux:
 
             with self._lock:
                 for i, c in enumerate(calls):
-                    self._inflight[tuple(float(v) for v in c[:11]) + (True,)] = \
-                        pool.submit(run_ordered, i, c)
+                    self._inflight[_prefetch_key(c)] = pool.submit(run_ordered, i, c)
             return len(calls)
 
         if not wait:
             with self._lock:
                 for c in calls:
-                    self._inflight[tuple(float(v) for v in c[:11]) + (True,)] = pool.submit(run, c)
+                    self._inflight[_prefetch_key(c)] = pool.submit(run, c)
             return len(calls)
         res = list(pool.map(run, calls))
         with self._lock:
@@ -419,7 +418,7 @@ class FastSchwarzschildEccentricFlux:
                 self._prefetched.clear()
                 self._prefetched_bytes = 0
             for c, r in zip(calls, res):
-                key = tuple(float(v) for v in c[:11]) + (True,)
+                key = _prefetch_key(c)
                 old = self._prefetched.pop(key, None)
                 if old is not None:
                     self._prefetched_bytes -= _nbytes(old)
@@ -526,6 +525,11 @@ def _check_kept(keep):
                          "positive at any harmonic's frequency")
 
 
+def _prefetch_key(c, include_minus_m=True):
+    """The prefetch tables' key of one prepare() argument tuple (M ... eps)."""
+    return tuple(float(v) for v in c[:11]) + (bool(include_minus_m),)
+
+
 def _nbytes(d):
     """Host bytes held by one prepared upstream result (its numpy arrays)."""
     return sum(v.nbytes for v in d.values() if isinstance(v, np.ndarray))
@@ -589,6 +593,7 @@ class GenerateEMRIWaveform:
         self.frame = frame
         self.return_list = return_list
         self._angle_cache = {}
+        self._gen_batch = None   # the batched calls' preparer, events and side stream
 
     def _angles(self, qS, phiS, qK, phiK):
         """(theta, phi, rot) of a sky position and spin orientation: the source-frame viewing
@@ -657,17 +662,13 @@ class GenerateEMRIWaveform:
         # handling per walker)
         pend = getattr(preparer, "_pending", None)
         room = getattr(preparer, "group", 0)
-        for prm in np.asarray(params, dtype=np.float64).reshape(-1, 14).tolist():
-            M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
-            theta, phi, rot = self._angles(qS, phiS, qK, phiK)
-            d = gen.prepare(M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps,
-                            mode_selection, include_minus_m)
-            scale = rot * (mu * MRSUN_SI / (dist * Gpc))   # the spectrum path's rounding
+        for call, scale in zip(*self.device_calls(params, T, eps)):
+            d = gen.prepare(*call, mode_selection, include_minus_m)
             if "_src" in d:
                 # the native upstream recorded its arrays' addresses: the preparer stages them
                 # straight from prepare()'s dict
                 if pend is not None and len(pend) < room:
-                    pend.append((d, freq, True, complex(scale), int(kc), False))
+                    pend.append((d, freq, True, scale, int(kc), False))
                 else:
                     submit(d, freq, True, scale, k0=kc, prepare_only=True)
                 continue
@@ -753,19 +754,15 @@ class GenerateEMRIWaveform:
     def lanes_ready(self):
         """Wait for the last spectrum_batch's lane-range copies into lanes_host (each group's
         event; the sums behind them keep running)."""
-        for name in ("_gen_batch", "_dev_batch"):
-            st = getattr(self, name, None)
-            if st is not None:
-                for ev in st.get("lanes_ev_used", ()):
-                    ev.synchronize()
+        if self._gen_batch is not None:
+            for ev in self._gen_batch["lanes_ev_used"]:
+                ev.synchronize()
 
     def check_batch(self):
         """Synchronise the last batch's groups and raise if a workspace reported a device-side
         error (what spectrum_batch(check=False) skipped)."""
-        st = getattr(self, "_gen_batch", None)
-        if st is not None:
-            st["prep"].wait()
-        self._device_check()
+        if self._gen_batch is not None:
+            self._gen_batch["prep"].wait()
 
     def positive_bins(self, T=1.0, dt=10.0, f_arr=None):
         """N_pos, the f >= 0 bins of the grid generate_batch writes (its out's last dimension)."""
@@ -781,21 +778,38 @@ class GenerateEMRIWaveform:
             raise ValueError("the batched generator needs a symmetric grid")
         return int(freq.numel()), int(freq.numel()) - cw._k0
 
+    def device_calls(self, params, T=1.0, eps=1e-5):
+        """(calls, scales) of the rows of params (B x 14): prepare()'s / device_inputs_batch's
+        argument tuples (M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps) and each
+        row's complex scale (the spectrum path's rounding). a, x0 and Phi_theta0 are ignored for
+        Schwarzschild; the rows are unpacked as Python floats (one tolist(): unpacking numpy
+        rows costs ~5x more a walker)."""
+        calls, scales = [], []
+        for prm in np.asarray(params, dtype=np.float64).reshape(-1, 14).tolist():
+            M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
+            theta, phi, rot = self._angles(qS, phiS, qK, phiK)
+            calls.append((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps))
+            scales.append(complex(rot * (mu * MRSUN_SI / (dist * Gpc))))
+        return calls, scales
+
+    def device_trajectories(self, calls, device, state):
+        """The device trajectories of all of a call's rows, launched once on the current stream
+        ahead of the first group (the caller orders the groups' streams after it). state: a
+        dict the caller keeps (the launch's buffers)."""
+        return self.waveform_generator.device_trajectories(calls, device=device, state=state)
+
     def _run_batch(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes=None,
                    check=True, lanes_host=None, upstream="host", trajectory="host"):
         torch = require_gpu()
-        if upstream == "device":
-            return self._run_batch_device(params, out, outputs, T, dt, eps, f_arr, kwargs,
-                                          lanes, check, lanes_host, trajectory)
         from .summation import BatchPreparer, sum_batch
-        cw = self.waveform_generator.create_waveform
+        gen = self.waveform_generator
+        cw = gen.create_waveform
         params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
         B = len(params)
         if B == 0:
             return out
-        self.prefetch(params, T=T, dt=dt, eps=eps, **kwargs)
         G = min(self.BATCH_GROUP, _lib.EFD_BATCH_MAX)
-        st = getattr(self, "_gen_batch", None)
+        st = self._gen_batch
         if (st is None or st["prep"].caustic != cw.caustic or st["device"] != out.device
                 or st["prep"].group != G):
             st = self._gen_batch = dict(
@@ -806,6 +820,21 @@ class GenerateEMRIWaveform:
                 prep_ev=[torch.cuda.Event(), torch.cuda.Event()],
                 lstream=torch.cuda.Stream(out.device))
         prep = st["prep"]
+        # the upstream of all rows, started before the first group: the host route's on the
+        # prefetch pool; the device route's trajectories on the pool too, or in one launch on
+        # the current stream (the groups' selections then run on their streams)
+        device = upstream == "device"
+        futs, trajs = [], None
+        if not device:
+            self.prefetch(params, T=T, dt=dt, eps=eps, **kwargs)
+        else:
+            prep.restart()
+            freq, kc = cw._grid(T, dt, f_arr)[0], cw._k0
+            calls, scales = self.device_calls(params, T, eps)
+            if trajectory == "device":
+                trajs = self.device_trajectories(calls, out.device, st.setdefault("traj", {}))
+            else:
+                futs = gen.trajectories_async(calls)
         cur = torch.cuda.current_stream(out.device)
         prep.order_after_current()
         # each group's sum on the group's own stream, right behind its preparation (no
@@ -816,14 +845,22 @@ class GenerateEMRIWaveform:
         st["lanes_ev_used"] = []
         try:
             for g0 in range(0, B, G):
-                rows = params[g0:g0 + G]
-                self.submit_batch(prep, rows, T=T, dt=dt, eps=eps, f_arr=f_arr, **kwargs)
-                gi, jobs = prep.flush()
-                # joined at the end however the rest of the group's queueing ends (its
-                # preparation is on the stream already)
-                if gi not in used:
-                    used.append(gi)
-                gs = prep.stream(gi)
+                # joined at the end however the group's queueing ends
+                gs = prep.next_flush()[0]
+                if gs not in used:
+                    used.append(gs)
+                if device:
+                    g = slice(g0, g0 + G)
+                    inps = gen.device_inputs_batch(
+                        calls[g], include_minus_m=bool(kwargs.get("include_minus_m", True)),
+                        device=out.device, stream=gs, state=prep.next_select(),
+                        futures=futs[g] if trajs is None else None,
+                        trajs=trajs[g] if trajs is not None else None)
+                    gi, jobs = prep.flush_device(inps, freq, scales[g], kc)
+                else:
+                    self.submit_batch(prep, params[g0:g0 + G], T=T, dt=dt, eps=eps, f_arr=f_arr,
+                                      **kwargs)
+                    gi, jobs = prep.flush()
                 if lanes_host is not None:
                     pev = st["prep_ev"][gi]
                     pev.record(gs)
@@ -851,142 +888,15 @@ class GenerateEMRIWaveform:
                 ev.record(gs)
                 prep.release(gi, ev)
         finally:
+            for f in futs:
+                f.cancel()
             prep.drop_pending()
-            for gi in used:
-                cur.wait_stream(prep.stream(gi))
+            for gs in used:
+                cur.wait_stream(gs)
             if lanes_host is not None and used:
                 cur.wait_stream(st["lstream"])
         if check:
             prep.wait()   # device-side errors of the groups' workspaces raise here
-        return out
-
-    # -- the batched generator with the amplitudes and the selection on the device ------------
-    def _device_state(self, dev, caustic):
-        """Two rotating group slots for the device upstream: a stream, EFD_BATCH_MAX engines
-        (a workspace each) and the selection's pinned buffers per slot."""
-        torch = require_gpu()
-        st = getattr(self, "_dev_batch", None)
-        if st is None or st["device"] != dev or st["caustic"] != caustic:
-            from .summation import ModeSumEngine
-            st = self._dev_batch = dict(
-                device=dev, caustic=caustic, used=[0, 0],
-                streams=[torch.cuda.Stream(dev) for _ in range(2)],
-                engines=[[ModeSumEngine(caustic) for _ in range(_lib.EFD_BATCH_MAX)]
-                         for _ in range(2)],
-                sel=[{}, {}], lanes_ev=[torch.cuda.Event(), torch.cuda.Event()])
-        return st
-
-    def device_calls(self, params, T=1.0, eps=1e-5):
-        """(calls, scales) of the rows of params (B x 14): device_inputs_batch's argument tuples
-        and each row's complex scale (the spectrum path's rounding)."""
-        calls, scales = [], []
-        for prm in np.asarray(params, dtype=np.float64).reshape(-1, 14).tolist():
-            M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
-            theta, phi, rot = self._angles(qS, phiS, qK, phiK)
-            calls.append((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps))
-            scales.append(complex(rot * (mu * MRSUN_SI / (dist * Gpc))))
-        return calls, scales
-
-    def device_group(self, st, slot, calls, scales, futures, freq, k0, outputs=None,
-                     include_minus_m=True, trajs=None):
-        """One group of at most EFD_BATCH_MAX walkers on slot `slot` of _device_state's st:
-        device_inputs_batch and efd_modesum_prepare_batch on the slot's stream. Returns the
-        (engine, launch_kwargs) jobs for sum_batch / sum_batch_loglike on that stream. trajs:
-        the group's device trajectories (device_trajectories), in place of futures."""
-        torch = require_gpu()
-        from .summation import prepare_batch
-        gs = st["streams"][slot]
-        inps = self.waveform_generator.device_inputs_batch(
-            calls, include_minus_m=include_minus_m, device=st["device"], stream=gs,
-            state=st["sel"][slot], futures=futures, trajs=trajs)
-        jobs = [(eng, dict(dict(inp=inp, freq=freq, out=None, grid_symmetric=True, scale=sc,
-                                k0=k0), **(outputs(i) if outputs is not None else {})))
-                for i, (eng, inp, sc) in enumerate(zip(st["engines"][slot], inps, scales))]
-        st["used"][slot] = max(st["used"][slot], len(jobs))
-        with torch.cuda.stream(gs):   # (a grown workspace is allocated on the slot's stream)
-            prepare_batch(jobs, stream=gs.cuda_stream)
-        return jobs
-
-    def _device_check(self):
-        """Synchronise the device route's slots and raise if a workspace reported a device-side
-        error."""
-        import ctypes
-        st = getattr(self, "_dev_batch", None)
-        if st is None:
-            return
-        for slot, n in enumerate(st["used"]):
-            eng = [e for e in st["engines"][slot][:n] if e._ws is not None]
-            st["used"][slot] = 0
-            if not eng:
-                continue
-            pw = (ctypes.c_void_p * len(eng))(*[e._ws.data_ptr() for e in eng])
-            lib = eng[0].lib
-            if lib.efd_modesum_status_batch(pw, len(eng), None,
-                                            st["streams"][slot].cuda_stream) != _lib.EFD_OK:
-                raise _lib.EFDError(f"efd_modesum: {_lib.last_error(lib)}")
-
-    def device_trajectories(self, st, calls):
-        """The device trajectories of all of a call's rows, launched once on the current stream
-        ahead of the first group (the caller orders the slots' streams after it)."""
-        return self.waveform_generator.device_trajectories(
-            calls, device=st["device"], state=st.setdefault("traj", {}))
-
-    def _run_batch_device(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes, check,
-                          lanes_host, trajectory="host"):
-        import ctypes
-        torch = require_gpu()
-        from .summation import sum_batch
-        gen = self.waveform_generator
-        cw = gen.create_waveform
-        freq, _ = cw._grid(T, dt, f_arr)
-        kc = cw._k0
-        params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
-        B = len(params)
-        if B == 0:
-            return out
-        include_minus_m = bool(kwargs.get("include_minus_m", True))
-        st = self._device_state(out.device, cw.caustic)
-        calls, scales = self.device_calls(params, T, eps)
-        on_device = trajectory == "device"
-        futs = gen.trajectories_async(calls) if not on_device else [None] * B
-        trajs = self.device_trajectories(st, calls) if on_device else [None] * B
-        G = min(self.BATCH_GROUP, _lib.EFD_BATCH_MAX)
-        cur = torch.cuda.current_stream(out.device)
-        for gs in st["streams"]:
-            gs.wait_stream(cur)
-        st["lanes_ev_used"] = []
-        used = set()
-        try:
-            for gidx, g0 in enumerate(range(0, B, G)):
-                slot = gidx % 2
-                gs = st["streams"][slot]
-                used.add(slot)
-                jobs = self.device_group(st, slot, calls[g0:g0 + G], scales[g0:g0 + G],
-                                         None if on_device else futs[g0:g0 + G], freq, kc,
-                                         lambda i, g0=g0: outputs(g0 + i), include_minus_m,
-                                         trajs[g0:g0 + G] if on_device else None)
-                sum_batch(jobs, stream=gs.cuda_stream)
-                if lanes is not None:
-                    lib = jobs[0][0].lib
-                    pw = (ctypes.c_void_p * len(jobs))(*[e._ws.data_ptr() for e, _ in jobs])
-                    _lib.check(lib.efd_modesum_lane_ranges(pw, len(jobs), lanes[g0].data_ptr(),
-                                                           gs.cuda_stream),
-                               "efd_modesum_lane_ranges", lib)
-                    if lanes_host is not None:
-                        _lib.check(lib.efd_download(lanes_host[g0].data_ptr(),
-                                                    lanes[g0].data_ptr(), 8 * len(jobs),
-                                                    gs.cuda_stream), "efd_download", lib)
-                        lev = torch.cuda.Event()
-                        lev.record(gs)
-                        st["lanes_ev_used"].append(lev)
-        finally:
-            for f in futs:
-                if f is not None:
-                    f.cancel()
-            for slot in used:
-                cur.wait_stream(st["streams"][slot])
-        if check:
-            self._device_check()
         return out
 
     # prefetch(wait=False) is supported (the likelihood's groups then overlap the upstream)
@@ -1001,12 +911,7 @@ class GenerateEMRIWaveform:
         gen = self.waveform_generator
         if mode_selection is not None or not include_minus_m:
             return 0
-        calls = []
-        # rows as Python floats (one tolist(): unpacking numpy rows costs ~5x more a walker)
-        for prm in np.asarray(params, dtype=np.float64).reshape(-1, 14).tolist():
-            M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
-            theta, phi, _ = self._angles(qS, phiS, qK, phiK)
-            calls.append((M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps))
+        calls, _ = self.device_calls(params, T, eps)
         return (gen.prefetch(calls) if wait
                 else gen.prefetch(calls, wait=False, concurrency=concurrency))
 
@@ -1054,17 +959,13 @@ class GenerateEMRIWaveform:
         self.prefetch(params, T=T, dt=dt, eps=eps, mode_selection=mode_selection,
                       include_minus_m=include_minus_m, wait=False)
         try:
-            for i, prm in enumerate(params.tolist()):
-                M, mu, a, p0, e0, x0, dist, qS, phiS, qK, phiK, Phi_phi0, Phi_theta0, Phi_r0 = prm
-                theta, phi, rot = self._angles(qS, phiS, qK, phiK)
+            for i, (call, scale) in enumerate(zip(*self.device_calls(params, T, eps))):
                 try:
-                    d = gen.prepare(M, mu, p0, e0, theta, phi, dist, Phi_phi0, Phi_r0, T, eps,
-                                    mode_selection, include_minus_m)
+                    d = gen.prepare(*call, mode_selection, include_minus_m)
                 except (ValueError, RuntimeError) as e:
                     # a walker outside the model's domain: an error, never a number
                     raise _lib.EFDError(f"time_series_batch: upstream of row {i}: {e}") from e
                 K = len(d["m"])
-                scale = complex(rot) * (mu * MRSUN_SI / (dist * Gpc))
                 f_phi, f_r = d.get("f_phi"), d.get("f_r")
                 inp = DeviceInputs.from_host(d["t"], d["teuk"], d["Phi_phi"], d["Phi_r"], f_phi,
                                              f_r, d["m"], d["n"], d["ylms"][:K], d["ylms"][K:],
