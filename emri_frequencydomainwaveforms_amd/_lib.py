@@ -28,6 +28,8 @@ EFD_HANN_LOCAL_PARTIALS = 4096   # efd_hann_loglike_local's scratch doubles per 
 EFD_TD_SPLIT_SCRATCH = 1024   # efd_td_split_loglike's scratch doubles per row
 EFD_PAIR_MAX_ROWS = 64
 EFD_PAIR_SCRATCH = 655360   # the pair statistics' scratch doubles (1024 chunks x 64 rows x 10)
+EFD_DH_MAX_ROWS = 64
+EFD_DH_SCRATCH = 196608   # efd_dh_hh_rows' scratch doubles (1024 chunks x 64 rows x 3)
 EFD_WINDOW_MAX_ROWS = 16   # efd_window_rows' windows per call
 EFD_MODES_AMP_OVERFLOW = 1   # efd_modes_select_batch's status bit: amp capacity too small
 EFD_TRAJ_MAX_LEN = 1024   # efd_traj_batch's longest knot slab
@@ -58,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "efd_loglike_tile_count",
     "efd_loglike_tile_constants",
     "efd_modesum_sum_loglike_ex",
+    "efd_modesum_sum_dh_hh",
     "efd_modesum_status",
     "efd_modesum_contributions",
     "efd_modesum_stats",
@@ -88,6 +91,7 @@ EXPORTED_SYMBOLS = (
     "efd_overlap_rows",
     "efd_pair_stats",
     "efd_td_split_pair_stats",
+    "efd_dh_hh_rows",
     "efd_window_rows",
     "efd_modesum_cpu",
     "efd_modesum_cpu_stats",
@@ -101,6 +105,7 @@ EXPORTED_SYMBOLS = (
     "efd_td_split_loglike_cpu",
     "efd_pair_stats_cpu",
     "efd_td_split_pair_stats_cpu",
+    "efd_dh_hh_rows_cpu",
     "efd_window_rows_cpu",
     "efd_cpu_threads",
     "efd_cpu_last_error",
@@ -307,6 +312,10 @@ def load(path=None):
         lib.efd_modesum_sum_loglike_ex.argtypes = [ctypes.POINTER(ctypes.POINTER(ModesumArgs)),
                                                    ctypes.POINTER(vp), ctypes.POINTER(sz), i32,
                                                    vp, vp, vp, vp, vp]
+    lib.efd_modesum_sum_dh_hh.restype = ctypes.c_int
+    lib.efd_modesum_sum_dh_hh.argtypes = [ctypes.POINTER(ctypes.POINTER(ModesumArgs)),
+                                          ctypes.POINTER(vp), ctypes.POINTER(sz), i32, vp, vp,
+                                          vp, i32, vp, vp]
     lib.efd_modesum_status.restype = ctypes.c_int
     lib.efd_modesum_status.argtypes = [vp, vp]
     if hasattr(lib, "efd_stage_batch"):
@@ -393,6 +402,9 @@ def load(path=None):
     for name in ("efd_td_split_pair_stats", "efd_td_split_pair_stats_cpu"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, i64, i64, i32, dbl, vp, i64, vp, vp, vp, vp, vp]
+    for name in ("efd_dh_hh_rows", "efd_dh_hh_rows_cpu"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, i64, i32, vp, vp, i32, i64, vp, vp, vp]
     for name in ("efd_window_rows", "efd_window_rows_cpu"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, i64, ctypes.POINTER(vp), i32, vp, i64, vp]

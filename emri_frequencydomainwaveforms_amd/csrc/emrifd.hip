@@ -895,15 +895,21 @@ __device__ __forceinline__ TileLds& tile_lds() {
     return lds;
 }
 
-template <bool PAIRED>
+// The fused epilogue of a tile (the sum kernels' compile-time switch EPI): EPI_LL, the likelihood
+// partial sum |d - h w|^2 at llpart[tile]; EPI_DH, the three partials of <d|h> and <h|h> (sum t_re,
+// sum t_im, sum t_hh of dh_term) at llpart[s ntiles + tile], s = 0, 1, 2, where llpart is the
+// waveform's [3][ntiles] slice of the caller's buffer (efd_modesum_sum_dh_hh)
+constexpr int EPI_LL = 0, EPI_DH = 1;
+
+template <bool PAIRED, int EPI>
 __device__ __forceinline__ void tile_epilogue(
     double (&own_r)[BPL], double (&own_i)[BPL], double (&mir_r)[BPL], double (&mir_i)[BPL],
     int32_t w_lo, int lane, int wave, int tid, int64_t nlanes, int64_t nf, int64_t k0,
     int accumulate_out, double* __restrict__ out, double* __restrict__ hp,
     double* __restrict__ hc, const double* __restrict__ lld, const double* __restrict__ llw,
-    double* __restrict__ llpart, int64_t tile);
+    double* __restrict__ llpart, int64_t tile, int64_t ntiles);
 
-template <bool PAIRED, int CAUSTIC, int NB = BPL>
+template <bool PAIRED, int CAUSTIC, int NB = BPL, int EPI = EPI_LL>
 // 4 waves per SIMD (<= 128 VGPRs, 19 spilled, all outside the fast path's FMA chains): with
 // 37.6 KB of LDS per workgroup 4 workgroups fit a CU, and the fourth wave hides more FP64
 // latency than the spills cost (config 2: 1.00 ms against 1.09 ms at 3 waves / 147 VGPRs;
@@ -1398,9 +1404,21 @@ __device__ __forceinline__ void modesum_tile(
             const double2 a = s0[2 * li], m = s0[2 * li + 1];
             a_r[i] = a.x; a_i[i] = a.y; m_r[i] = m.x; m_i[i] = m.y;
         }
-        tile_epilogue<PAIRED>(a_r, a_i, m_r, m_i, w_lo, ll, lw, lt, nlanes, nf, k0,
-                              accumulate_out, out, hp, hc, lld, llw, llpart, tile);
+        tile_epilogue<PAIRED, EPI>(a_r, a_i, m_r, m_i, w_lo, ll, lw, lt, nlanes, nf, k0,
+                                   accumulate_out, out, hp, hc, lld, llw, llpart, tile, ntiles);
     } else {
+        if constexpr (EPI == EPI_DH) {
+            if (PAIRED && !seen && out == nullptr && hp == nullptr) {
+                // no record reached this tile: h = 0 on its bins, and every term of the three
+                // sums is exactly 0 (w is finite), so the tile needs neither d nor w
+                if (tid == 0) {
+                    llpart[tile] = 0.0;
+                    llpart[ntiles + tile] = 0.0;
+                    llpart[2 * ntiles + tile] = 0.0;
+                }
+                return;
+            }
+        }
         if (PAIRED && llconst != nullptr && !seen && out == nullptr && hp == nullptr) {
             // no record reached this tile: h = 0 on its bins, whose likelihood partial is the
             // walker-independent one k_ll_tile_const computed with this epilogue's arithmetic
@@ -1411,21 +1429,22 @@ __device__ __forceinline__ void modesum_tile(
 #pragma unroll
             for (int i = 0; i < BPL; ++i) { own_i[i] = -own_i[i]; mir_i[i] = -mir_i[i]; }
         tid = opq(tid0);
-        tile_epilogue<PAIRED>(own_r, own_i, mir_r, mir_i, w_lo, tid & 63, wave, tid, nlanes, nf,
-                              k0, accumulate_out, out, hp, hc, lld, llw, llpart, tile);
+        tile_epilogue<PAIRED, EPI>(own_r, own_i, mir_r, mir_i, w_lo, tid & 63, wave, tid, nlanes,
+                                   nf, k0, accumulate_out, out, hp, hc, lld, llw, llpart, tile,
+                                   ntiles);
     }
     EFD_EXP_DO(if (threadIdx.x == 0) exp_tile_clock(tile, t_start);)
 }
 
 // The tile's epilogue (whole tile, or the last arriver of a sub-bin split): the spectrum S,
 // the symmetric grid's h+ / hx, and the fused likelihood's partial of the tile
-template <bool PAIRED>
+template <bool PAIRED, int EPI>
 __device__ __forceinline__ void tile_epilogue(
     double (&own_r)[BPL], double (&own_i)[BPL], double (&mir_r)[BPL], double (&mir_i)[BPL],
     int32_t w_lo, int lane, int wave, int tid, int64_t nlanes, int64_t nf, int64_t k0,
     int accumulate_out, double* __restrict__ out, double* __restrict__ hp,
     double* __restrict__ hc, const double* __restrict__ lld, const double* __restrict__ llw,
-    double* __restrict__ llpart, int64_t tile) {
+    double* __restrict__ llpart, int64_t tile, int64_t ntiles) {
     // S is written when out != NULL; on a symmetric grid h+ and hx of bins [k0, nf) are written
     // straight from the registers when hp != NULL (the lane holds S(k) and S(nf-1-k), the two
     // halves of efd_polarizations' flip), so the likelihood path never stores S
@@ -1433,6 +1452,7 @@ __device__ __forceinline__ void tile_epilogue(
     double2* php = reinterpret_cast<double2*>(hp);
     double2* phc = reinterpret_cast<double2*>(hc);
     double llacc = 0.0;   // fused likelihood: this lane's sum of |d - h w|^2
+    double dh[3] = {0.0, 0.0, 0.0};   // EPI_DH: this lane's sums of t_re, t_im, t_hh
 #pragma unroll
     for (int i = 0; i < BPL; ++i) {
         const int64_t k = w_lo + 64 * i + lane;
@@ -1461,7 +1481,17 @@ __device__ __forceinline__ void tile_epilogue(
                 if (j < k0) return;
                 double2 vp = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
                 double2 vc = make_double2(-0.5 * (a.y + b.y), 0.5 * (a.x - b.x));
-                if (lld) {
+                if constexpr (EPI == EPI_DH) {
+                    // h w with each component's product rounded (efd_loglike's rule), then the
+                    // three written terms: no contraction
+#pragma clang fp contract(off)
+                    const int64_t q = j - k0, nb = nf - k0;
+                    const double2 d0 = reinterpret_cast<const double2*>(lld)[q];
+                    const double2 d1 = reinterpret_cast<const double2*>(lld)[nb + q];
+                    const double w0 = llw[q], w1 = llw[nb + q];
+                    dh_term(d0, make_double2(vp.x * w0, vp.y * w0), dh);
+                    dh_term(d1, make_double2(vc.x * w1, vc.y * w1), dh);
+                } else if (lld) {
                     // d - h w rounded like efd_loglike (product rounded, then difference: no
                     // contraction), so a template equal to the injection gives exactly 0
 #pragma clang fp contract(off)
@@ -1486,7 +1516,25 @@ __device__ __forceinline__ void tile_epilogue(
             if (km != k) put(k, sk, sm);
         }
     }
-    if (PAIRED && lld) {
+    if constexpr (EPI == EPI_DH) {
+        // the three partials in the likelihood partial's order (below)
+        if (PAIRED && lld) {
+            __shared__ double dhw4[3][NWAVE];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) dh[s] += __shfl_xor(dh[s], o, 64);
+                if (lane == 0) dhw4[s][wave] = dh[s];
+            }
+            __syncthreads();
+            if (tid < 3) {
+                double t = 0.0;
+#pragma unroll
+                for (int w = 0; w < NWAVE; ++w) t += dhw4[tid][w];
+                llpart[tid * ntiles + tile] = t;
+            }
+        }
+    } else if (PAIRED && lld) {
         // the tile's partial in a fixed order: a butterfly over each wave, then the waves in turn
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) llacc += __shfl_xor(llacc, o, 64);
@@ -1537,13 +1585,13 @@ struct SumDesc {
 // the restrict-qualified parameters the record loop's alias analysis works from. d comes by
 // value: through a reference k_modesum_batch's sparse instances took up to 67 more SGPR spills
 // and one a VGPR more; by value their registers, scratch and LDS are the explicit calls'.
-template <bool PAIRED, int CAUSTIC, int NB = BPL>
+template <bool PAIRED, int CAUSTIC, int NB = BPL, int EPI = EPI_LL>
 __device__ __forceinline__ void modesum_tile(
     const SumDesc d, int64_t nf, int64_t nlanes, int64_t ntiles, int accumulate_out,
     const double* __restrict__ lld, const double* __restrict__ llw,
     const double* __restrict__ llconst, int64_t b, bool direct = false, int ioff = 0,
     double* __restrict__ spart = nullptr, int32_t* __restrict__ scnt = nullptr) {
-    modesum_tile<PAIRED, CAUSTIC, NB>(
+    modesum_tile<PAIRED, CAUSTIC, NB, EPI>(
         d.items, d.ranges, d.seglh, d.seginfo, d.nseg, d.freq, nf, nlanes, ntiles, d.nt, d.K,
         d.gm, d.gn, d.t, d.coefA, d.coefT, d.sctab, d.tkeys, d.tcnt, d.tperm, d.segbase, d.stb0,
         d.stb1, d.hdr, accumulate_out, d.out, d.hp, d.hc, d.k0, lld, llw, d.llpart, llconst, b,
@@ -1577,19 +1625,22 @@ static_assert(sizeof(SumBatch) <= 3584, "batch descriptors must fit the kernel a
 // their constants): each thread's tiles i, i + 256, ... added in that order, then a tree; out =
 // -1/2 * 4 * sum, or NaN when the workspace holds a device-side error flag (the flags stay set:
 // efd_modesum_status_batch reports and clears them), so a caller that finds no NaN in the batch
-// needs no status synchronisation. 256 threads.
+// needs no status synchronisation. 256 threads. The same pass ends efd_modesum_sum_dh_hh's three
+// sums: `sparse` says whether tiles outside the lane union take outside(i) (the constant; 0 for
+// <d|h> and <h|h>) instead of p[i], and the sum is scaled by `scale`.
+template <class Outside>
 __device__ __forceinline__ void ll_final_reduce(const double* __restrict__ p,
-                                                const Header* __restrict__ h,
-                                                const double* __restrict__ llconst,
-                                                int64_t ntiles, double* __restrict__ out) {
+                                                const Header* __restrict__ h, bool sparse,
+                                                Outside outside, int64_t ntiles, double scale,
+                                                double* __restrict__ out) {
     __shared__ double red[256];
     int64_t t0 = 0, t1 = ntiles - 1;
-    if (llconst != nullptr) {
+    if (sparse) {
         const int32_t lo = h->lane_lo, hi = h->lane_hi;
         t0 = lo < hi ? lo / TILE_LANES : ntiles;
         t1 = lo < hi ? (int64_t)(hi - 1) / TILE_LANES : -1;
     }
-    auto val = [&](int64_t i) { return (i < t0 || i > t1) ? llconst[i] : p[i]; };
+    auto val = [&](int64_t i) { return (i < t0 || i > t1) ? outside(i) : p[i]; };
     // four loads in flight at a time
     double acc = 0.0;
     int64_t i = threadIdx.x;
@@ -1609,7 +1660,7 @@ __device__ __forceinline__ void ll_final_reduce(const double* __restrict__ p,
     }
     if (threadIdx.x == 0) {
         const bool bad = h->runs_overflow | h->bad_mn | h->bad_tile;
-        *out = bad ? __longlong_as_double(0x7ff8000000000000LL) : -0.5 * 4.0 * red[0];
+        *out = bad ? __longlong_as_double(0x7ff8000000000000LL) : scale * red[0];
     }
 }
 // SPARSE (the fused likelihood with tile constants, no written outputs): only the tiles inside the
@@ -1619,7 +1670,7 @@ __device__ __forceinline__ void ll_final_reduce(const double* __restrict__ p,
 // agent-scope partial stores and a completion count, made config 4's sum 6 us longer than the two
 // kernels: the reduction then runs in the launch's tail.) A sparse spectrum (config 4: 15 harmonics cover 576 of 6,164 tiles) then
 // launches a few hundred workgroups per walker instead of one per tile.
-template <bool PAIRED, int CAUSTIC, int BPL, bool SPARSE>
+template <bool PAIRED, int CAUSTIC, int BPL, bool SPARSE, int EPI = EPI_LL>
 __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(EFD_WAVES_PER_EU, 8)))
 void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t ntiles,
                      int accumulate_out, const double* __restrict__ lld,
@@ -1654,13 +1705,13 @@ void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t n
                 const int4 e = items[it];
                 const int S = e.y & 0xffff, j = e.y >> 16;
                 if (S > 1)
-                    modesum_tile<PAIRED, CAUSTIC, 1>(
+                    modesum_tile<PAIRED, CAUSTIC, 1, EPI>(
                         d, nf, nlanes, ntiles, accumulate_out, lld, llw, llconst, e.x, true, j,
                         ws_at<double>(W, L.spart) + (size_t)e.z * TILE_LANES * 4,
                         ws_at<int32_t>(W, L.scnt) + e.w);
                 else
-                    modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw,
-                                                  llconst, e.x, true);
+                    modesum_tile<PAIRED, CAUSTIC, BPL, EPI>(d, nf, nlanes, ntiles, accumulate_out,
+                                                            lld, llw, llconst, e.x, true);
                 __syncthreads();   // the next tile's LDS writes after every wave's last reads
             }
             return;
@@ -1669,14 +1720,15 @@ void k_modesum_batch(const SumBatch batch, int64_t nf, int64_t nlanes, int64_t n
         if (lo < hi) {
             const int64_t t1 = min((int64_t)(hi - 1) / TILE_LANES, ntiles - 1);
             for (int64_t tile = lo / TILE_LANES + pos; tile <= t1; tile += nper) {
-                modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw,
-                                              llconst, tile, true);
+                modesum_tile<PAIRED, CAUSTIC, BPL, EPI>(d, nf, nlanes, ntiles, accumulate_out, lld,
+                                                        llw, llconst, tile, true);
                 __syncthreads();   // the next tile's LDS writes after every wave's last reads
             }
         }
         return;
     }
-    modesum_tile<PAIRED, CAUSTIC>(d, nf, nlanes, ntiles, accumulate_out, lld, llw, llconst, pos);
+    modesum_tile<PAIRED, CAUSTIC, BPL, EPI>(d, nf, nlanes, ntiles, accumulate_out, lld, llw,
+                                            llconst, pos);
 }
 
 // The fused likelihood's partial of a tile whose waveform has no record on it (every bin's
@@ -1779,8 +1831,27 @@ __global__ __launch_bounds__(64) void k_status_gather(const StatusBatch sb, int3
 }
 
 __global__ __launch_bounds__(256) void k_ll_final(const LlBatch lb) {
-    ll_final_reduce(lb.part[blockIdx.x], lb.hdr[blockIdx.x], lb.llconst, lb.ntiles,
-                           lb.out + blockIdx.x);
+    const double* llconst = lb.llconst;
+    ll_final_reduce(lb.part[blockIdx.x], lb.hdr[blockIdx.x], llconst != nullptr,
+                    [=](int64_t i) { return llconst[i]; }, lb.ntiles, -0.5 * 4.0,
+                    lb.out + blockIdx.x);
+}
+
+// efd_modesum_sum_dh_hh, second stage: workgroup (i, s) turns sum s of waveform i, its ntiles
+// partials at part[(3 i + s) ntiles ...], into out[3 i + s] = 4 * sum (NaN for all three of a
+// waveform whose workspace holds an error flag). A sparse sum visited the lane union's tiles
+// only, and the others' terms are exactly 0: they are never read.
+struct DhBatch {
+    const Header* hdr[EFD_BATCH_MAX];
+    const double* part;
+    double* out;
+    int64_t ntiles;
+    int32_t sparse;
+};
+__global__ __launch_bounds__(256) void k_dh_final(const DhBatch db) {
+    const int64_t o = 3 * (int64_t)blockIdx.x + blockIdx.y;
+    ll_final_reduce(db.part + o * db.ntiles, db.hdr[blockIdx.x], db.sparse != 0,
+                    [](int64_t) { return 0.0; }, db.ntiles, 4.0, db.out + o);
 }
 
 // K6: the tiles' record lists, built in the preparation phase (k_modesum DMAs them in). The same
@@ -2423,7 +2494,9 @@ static int64_t sparse_wg() {
 }
 int sum_batch_impl(const char* fn, const efd_modesum_args* const* a, void* const* workspace,
                    const size_t* workspace_bytes, int32_t count, const double* d, const double* w,
-                   double* llout, void* stream, const double* llconst = nullptr) {
+                   double* llout, void* stream, const double* llconst = nullptr,
+                   double* dhpart = nullptr, int32_t dhflags = 0) {
+    // dhpart: efd_modesum_sum_dh_hh (the EPI_DH instances; llout = its [count][3], no constants)
     const std::string F(fn);
     if (!a || !workspace || !workspace_bytes)
         return fail(EFD_ERR_ARG, F + ": NULL argument");
@@ -2452,12 +2525,15 @@ int sum_batch_impl(const char* fn, const efd_modesum_args* const* a, void* const
                                                "efd_modesum_workspace_bytes)");
         if (i == 0) L0 = L;
         batch.d[i] = sum_desc(ai, workspace[i], L);
+        if (dhpart) batch.d[i].llpart = dhpart + (size_t)i * 3 * L.ntiles;
     }
     hipStream_t st = (hipStream_t)stream;
     // the sparse form (k_modesum_batch): the fused likelihood with tile constants, nothing
     // written, and in-kernel lists (below 1,024 harmonics: the sparse spectra; denser ones keep
     // the longest-first order over every tile)
-    bool sparse = d != nullptr && llconst != nullptr && a[0]->grid_symmetric;
+    // (<d|h> and <h|h> need no constants: a tile without a record adds exactly 0)
+    bool sparse = d != nullptr && (dhpart ? !(dhflags & 1) : llconst != nullptr) &&
+                  a[0]->grid_symmetric;
     for (int i = 0; i < count && sparse; ++i)
         sparse = !a[i]->out && !a[i]->hp && !a[i]->hc &&
                  efdhip::list_mode(a[i]->K, L0.ntiles) == 0;
@@ -2481,6 +2557,19 @@ int sum_batch_impl(const char* fn, const efd_modesum_args* const* a, void* const
     for_sum_variant(a[0]->grid_symmetric != 0, a[0]->caustic, [&](auto P, auto C) {
         constexpr bool PAIRED = decltype(P)::value;
         constexpr int CAUSTIC = decltype(C)::value;
+        if constexpr (PAIRED) {
+            if (dhpart) {
+                if (sparse)
+                    hipLaunchKernelGGL((k_modesum_batch<true, CAUSTIC, BPL, true, EPI_DH>), grid,
+                                       block, 0, st, batch, a[0]->nf, L0.nlanes, L0.ntiles, acc, d,
+                                       w, nullptr, nper);
+                else
+                    hipLaunchKernelGGL((k_modesum_batch<true, CAUSTIC, BPL, false, EPI_DH>), grid,
+                                       block, 0, st, batch, a[0]->nf, L0.nlanes, L0.ntiles, acc, d,
+                                       w, nullptr, (int64_t)0);
+                return;
+            }
+        }
         if (sparse)
             hipLaunchKernelGGL((k_modesum_batch<PAIRED, CAUSTIC, BPL, true>), grid, block, 0, st,
                                batch, a[0]->nf, L0.nlanes, L0.ntiles, acc, d, w, llconst, nper);
@@ -2490,7 +2579,16 @@ int sum_batch_impl(const char* fn, const efd_modesum_args* const* a, void* const
                                d ? llconst : nullptr, (int64_t)0);
     });
     HIP_TRY(hipGetLastError());
-    if (d) {
+    if (dhpart) {
+        DhBatch db{};
+        for (int i = 0; i < count; ++i) db.hdr[i] = (const Header*)workspace[i];
+        db.part = dhpart;
+        db.out = llout;
+        db.ntiles = L0.ntiles;
+        db.sparse = sparse ? 1 : 0;
+        hipLaunchKernelGGL(k_dh_final, dim3((unsigned)count, 3), dim3(256), 0, st, db);
+        HIP_TRY(hipGetLastError());
+    } else if (d) {
         LlBatch lb{};
         lb.n = count;
         lb.ntiles = L0.ntiles;
@@ -2519,6 +2617,16 @@ int efd_modesum_sum_loglike(const efd_modesum_args* const* a, void* const* works
     if (!d || !w || !out) return fail(EFD_ERR_ARG, "efd_modesum_sum_loglike: NULL d, w or out");
     return sum_batch_impl("efd_modesum_sum_loglike", a, workspace, workspace_bytes, count, d, w,
                           out, stream);
+}
+
+int efd_modesum_sum_dh_hh(const efd_modesum_args* const* a, void* const* workspace,
+                          const size_t* workspace_bytes, int32_t count, const double* d,
+                          const double* w, double* part, int32_t flags, double* out,
+                          void* stream) {
+    if (!d || !w || !part || !out)
+        return fail(EFD_ERR_ARG, "efd_modesum_sum_dh_hh: NULL d, w, part or out");
+    return sum_batch_impl("efd_modesum_sum_dh_hh", a, workspace, workspace_bytes, count, d, w, out,
+                          stream, nullptr, part, flags);
 }
 
 int64_t efd_loglike_tile_count(int64_t nf) {

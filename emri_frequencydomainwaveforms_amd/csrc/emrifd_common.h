@@ -1,9 +1,10 @@
 // emrifd_common.h -- what the library's HIP units share: emrifd.hip (mode sum),
 // emrifd_prepare.hip (its preparation), emrifd_window.hip (window path) and emrifd_reduce.hip
-// (channels and reductions). They share no device code; each is compiled on its own (no
-// relocatable device code) and linked into libemrifd.so. The two units of the mode-sum chain
-// share emrifd_layout.h on top of this. Names declared here have external linkage so that the units can reach them,
-// and hidden visibility so that the library still exports only include/emrifd.h.
+// (channels and reductions). They share no device code but dh_term's few lines; each is compiled
+// on its own (no relocatable device code) and linked into libemrifd.so. The two units of the
+// mode-sum chain share emrifd_layout.h on top of this. Names declared here have external linkage
+// so that the units can reach them, and hidden visibility so that the library still exports only
+// include/emrifd.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,17 @@ EFD_INTERNAL void launch_loglike_final(int rows, const double* part, int np, dou
                                        hipStream_t st);
 }  // namespace efdhip
 using efdhip::fail;
+
+// One bin of one channel of <d|h> and <h|h> (h already weighted) into s = (sum t_re, sum t_im,
+// sum t_hh): the terms of include/emrifd.h's efd_modesum_sum_dh_hh, which the mode sum's epilogue
+// and efd_dh_hh_rows both write through this. t_im is the difference of two rounded products, not
+// an fma, and t_re and t_hh nest alike: with d == h bitwise, t_re == t_hh and t_im == 0 exactly.
+__device__ __forceinline__ void dh_term(const double2 d, const double2 h, double* s) {
+#pragma clang fp contract(off)
+    s[0] += fma(d.x, h.x, d.y * h.y);
+    s[1] += d.x * h.y - d.y * h.x;
+    s[2] += fma(h.x, h.x, h.y * h.y);
+}
 
 #define HIP_TRY(expr)                                                                    \
     do {                                                                                 \

@@ -4,7 +4,8 @@
 // the TD template's half-spectrum split and its fused likelihood (efd_td_split*), and the
 // Fisher matrix's Gram kernel (efd_fisher_gram), and the overlaps of many rows with one fixed
 // waveform (efd_overlap_rows), and the statistics of many row pairs of the mode-by-mode study
-// (efd_pair_stats, efd_td_split_pair_stats, efd_window_rows). Shares only emrifd_common.h with
+// (efd_pair_stats, efd_td_split_pair_stats, efd_window_rows), and <d|h> and <h|h> of written
+// templates (efd_dh_hh_rows). Shares only emrifd_common.h with
 // the mode sum (emrifd.hip) and the window path (emrifd_window.hip).
 
 #include "emrifd_common.h"
@@ -534,6 +535,50 @@ __global__ __launch_bounds__(PS_THREADS) void k_td_split_pair_stats(
     ps_store(s, part);
 }
 
+// <d|h> and <h|h> of written rows (efd_dh_hh_rows): k_pair_stats' shape with the mode sum
+// epilogue's terms (dh_term on h w, each component's product rounded); w is per channel here.
+// Workgroup (c, y) takes bins [c chunk, (c + 1) chunk) of the rows DH_RB y .. DH_RB y + DH_RB - 1:
+// a thread loads its bin's d and w once for all of them (d and w are 1.5 times a row's bytes;
+// one row per workgroup re-read them per row and ran at 0.55 ms for 16 rows of config 2's grid)
+// and keeps three sums per row. A row's terms and their order are those of a call with that row
+// alone: its numbers do not depend on the block it sits in.
+constexpr int DH_RB = 8;
+
+template <int NCHAN>
+__global__ __launch_bounds__(PS_THREADS) void k_dh_hh_rows(
+    const double2* __restrict__ h, int64_t row_stride, int nrow, const double2* __restrict__ d,
+    const double* __restrict__ w, int64_t nbin, int64_t chunk, double* __restrict__ part) {
+#pragma clang fp contract(off)
+    const int row0 = (int)blockIdx.y * DH_RB;
+    const int nr = min(DH_RB, nrow - row0);
+    const double2* hb = h + (int64_t)row0 * row_stride;
+    int64_t k0, k1;
+    chunk_bounds(chunk, nbin, k0, k1);
+    double s[3 * DH_RB];
+#pragma unroll
+    for (int i = 0; i < 3 * DH_RB; ++i) s[i] = 0.0;
+    for (int64_t k = k0 + threadIdx.x; k < k1; k += PS_THREADS) {
+        double2 dv[NCHAN];
+        double ww[NCHAN];
+#pragma unroll
+        for (int c = 0; c < NCHAN; ++c) {
+            dv[c] = d[c * nbin + k];
+            ww[c] = w[c * nbin + k];
+        }
+#pragma unroll
+        for (int r = 0; r < DH_RB; ++r) {
+            if (r >= nr) break;   // (block-uniform)
+            double2 hv[NCHAN];
+#pragma unroll
+            for (int c = 0; c < NCHAN; ++c) hv[c] = ps_stream(hb + (r * row_stride + c * nbin + k));
+#pragma unroll
+            for (int c = 0; c < NCHAN; ++c)
+                dh_term(dv[c], make_double2(hv[c].x * ww[c], hv[c].y * ww[c]), s + 3 * r);
+        }
+    }
+    wg_store(s, part, [=](int i) { return i < 3 * nr ? (int64_t)(3 * row0 + i) : (int64_t)-1; });
+}
+
 // out[j][k] = win[j][k] h[k]: every window of one series from one read of it
 struct wr_ptrs {
     const double* p[EFD_WINDOW_MAX_ROWS];
@@ -765,6 +810,36 @@ int efd_pair_stats(const double* a, int64_t a_stride, const double* b, int64_t b
     });
     HIP_TRY(hipGetLastError());
     launch_final(nrow * nchan * 5, scratch, np, 4.0, out, st);
+    HIP_TRY(hipGetLastError());
+    return EFD_OK;
+}
+
+static_assert(EFD_DH_SCRATCH == PS_MAXB * EFD_DH_MAX_ROWS * 3,
+              "EFD_DH_SCRATCH holds every workgroup's partial of every output");
+
+int efd_dh_hh_rows(const double* h, int64_t row_stride, int32_t nrow, const double* d,
+                   const double* w, int32_t nchan, int64_t nbin, double* out, double* scratch,
+                   void* stream) {
+    if (nrow < 1 || nrow > EFD_DH_MAX_ROWS)
+        return fail(EFD_ERR_ARG, "efd_dh_hh_rows: nrow outside 1..64");
+    if (nchan != 1 && nchan != 2) return fail(EFD_ERR_ARG, "efd_dh_hh_rows: nchan must be 1 or 2");
+    if (!h || !d || !w || !out || !scratch)
+        return fail(EFD_ERR_ARG, "efd_dh_hh_rows: NULL h, d, w, out or scratch");
+    if (nbin <= 0 || nbin > ((int64_t)1 << 40))
+        return fail(EFD_ERR_ARG, "efd_dh_hh_rows: nbin out of range");
+    if (row_stride < nchan * nbin)
+        return fail(EFD_ERR_ARG, "efd_dh_hh_rows: row_stride < nchan nbin");
+    int64_t chunk = 0;
+    const int np = row_chunks(nbin, &chunk);
+    hipStream_t st = (hipStream_t)stream;
+    for_value<1, 2>(nchan, [&](auto NC) {
+        hipLaunchKernelGGL((k_dh_hh_rows<decltype(NC)::value>),
+                           dim3((unsigned)np, (unsigned)((nrow + DH_RB - 1) / DH_RB)),
+                           dim3(PS_THREADS), 0, st, (const double2*)h, row_stride, (int)nrow,
+                           (const double2*)d, w, nbin, chunk, scratch);
+    });
+    HIP_TRY(hipGetLastError());
+    launch_final(nrow * 3, scratch, np, 4.0, out, st);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

@@ -1,9 +1,10 @@
 // emrifd_reduce_cpu.cpp -- host twins of emrifd_reduce.hip's entry points (the channel split,
 // the likelihood and inner product, the TD template's split, the Fisher Gram matrix, the overlap
-// rows, the pair statistics, the window rows): the same arithmetic in C++17 with OpenMP on host
-// pointers, with the signatures of the HIP entry points (`stream` and scratch are accepted and
-// unused). Built with contraction off: a product that feeds a sum rounds first unless it is a
-// written fma. Shares emrifd_cpu_internal.h with the mode sum's twin (emrifd_cpu.cpp).
+// rows, the pair statistics, <d|h> and <h|h> of rows, the window rows): the same arithmetic in
+// C++17 with OpenMP on host pointers, with the signatures of the HIP entry points (`stream` and
+// scratch are accepted and unused). Built with contraction off: a product that feeds a sum
+// rounds first unless it is a written fma. Shares emrifd_cpu_internal.h with the mode sum's twin
+// (emrifd_cpu.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -322,6 +323,40 @@ int efd_td_split_pair_stats_cpu(const double* Z, int64_t stride, int64_t n, int3
         return efdcpu::fail(EFD_ERR_ARG,
                             "efd_td_split_pair_stats_cpu: stride < n or a_stride < 2 nb");
     pair_stats_rows(a, a_stride, Z, stride, true, n, gain, keep, rows, 2, nb, w, out);
+    return EFD_OK;
+}
+
+// efd_dh_hh_rows' arithmetic: h w with each component's product rounded, then the three written
+// terms, a row at a time through chunk_sums (a row's numbers do not depend on the other rows)
+int efd_dh_hh_rows_cpu(const double* h, int64_t row_stride, int32_t nrow, const double* d,
+                       const double* w, int32_t nchan, int64_t nbin, double* out,
+                       double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (nrow < 1 || nrow > EFD_DH_MAX_ROWS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_dh_hh_rows_cpu: nrow outside 1..64");
+    if (nchan != 1 && nchan != 2)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_dh_hh_rows_cpu: nchan must be 1 or 2");
+    if (!h || !d || !w || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_dh_hh_rows_cpu: NULL h, d, w or out");
+    if (nbin <= 0) return efdcpu::fail(EFD_ERR_ARG, "efd_dh_hh_rows_cpu: nbin <= 0");
+    if (row_stride < nchan * nbin)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_dh_hh_rows_cpu: row_stride < nchan nbin");
+    for (int32_t r = 0; r < nrow; ++r) {
+        const double* hr = h + 2 * (int64_t)r * row_stride;
+        double* o = out + 3 * (int64_t)r;
+        chunk_sums(nbin, 3, o, [&](int64_t k0, int64_t k1, double* s) {
+            for (int64_t k = k0; k < k1; ++k)
+                for (int ch = 0; ch < nchan; ++ch) {
+                    const int64_t e = ch * nbin + k;
+                    const double hx = hr[2 * e] * w[e], hy = hr[2 * e + 1] * w[e];
+                    const double dx = d[2 * e], dy = d[2 * e + 1];
+                    s[0] += std::fma(dx, hx, dy * hy);
+                    s[1] += dx * hy - dy * hx;
+                    s[2] += std::fma(hx, hx, hy * hy);
+                }
+        });
+        for (int i = 0; i < 3; ++i) o[i] = 4.0 * o[i];
+    }
     return EFD_OK;
 }
 

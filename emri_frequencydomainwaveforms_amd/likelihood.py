@@ -27,6 +27,11 @@ walker's windowed series h+ - i hx written by efd_td_modesum_windowed into one r
 buffer, one batched complex transform, and efd_td_split_loglike reducing both channels' logL
 straight from it (any window; non_zero_mask folded into w as above).
 Results are numpy float64 arrays ([B]), or device tensors with use_gpu=True, return_cupy=True.
+Likelihood.parts returns the pair the logL is made of instead, <d|h> (complex) and <h|h> per
+walker with logL = -1/2 (d_d - 2 Re <d|h> + <h|h>): on the fused branches from the mode sum's
+epilogue (efd_modesum_sum_dh_hh, no template written), elsewhere from the templates that branch
+writes (efd_dh_hh_rows). separate_d_h=True (lisatools' flag) makes get_ll return that pair, and
+ProfiledLikelihood turns it into the amplitude-maximised or distance-marginalised logL.
 Likelihoods over time-domain DATA (dt only, no df or f_arr) are not part of this path: get_ll
 raises NotImplementedError.
 """
@@ -75,6 +80,7 @@ class Likelihood:
         self.fused_likelihood = True
         self._fused = None
         self._tile_const = None
+        self._d_d = None
         self._specific_likelihood_setup()
 
     def _specific_likelihood_setup(self):
@@ -188,6 +194,7 @@ class Likelihood:
         self._d, self._w = d, w
         self._w_templ = w
         self._tile_const = None   # (their tile constants are made again on the next call)
+        self._d_d = None          # (<d|d> too)
         self._hloc = None         # the windowed logL's per-bin data (made on the next call)
         tm = self.template_model
         mask = getattr(tm, "non_zero_mask", None)
@@ -195,8 +202,85 @@ class Likelihood:
             self._w_templ = (w * mask.to(torch.float64)[None, :]).contiguous()
 
     # ---------------------------------------------------------------------------------------
+    @property
+    def d_d(self):
+        """<d|d> = 4 sum |d|^2 of the weighted data (efd_inner_product), made once per
+        injection."""
+        if self._d_d is None:
+            self._d_d = float(self._red.inner(self._d, self._d).real.item())
+        return self._d_d
+
+    def parts(self, params, *args, **kwargs):
+        """(<d|h>, <h|h>) of every walker: complex128 [B] and float64 [B] (numpy, or device
+        tensors with use_gpu=True, return_cupy=True), with logL = -1/2 (d_d - 2 Re <d|h> +
+        <h|h>) (inner_product(d, h, complex=True)'s convention). The branches are get_ll's: the
+        fused ones take both numbers from the mode sum's epilogue (BatchPreparer.sum_dh_hh),
+        the others reduce the templates they write anyway (Reducer.dh_hh_rows; the windowed and
+        TD templates through fill_batch, a group of WINDOW_GROUP walkers per reduction)."""
+        torch = self.torch
+        if self.frequency_domain is False:
+            raise NotImplementedError("a dt-only (time-domain data) likelihood is not part of "
+                                      "the FD path")
+        num_likes = params.shape[0]
+        out = torch.empty((num_likes, 3), dtype=torch.float64, device=self.device)
+        nch, nb = self._d.shape
+        tm = self.template_model
+        host = None
+        if self.vectorized:
+            h_all = tm(*params, *args, **kwargs)
+            for i in range(num_likes):
+                self._red.dh_hh_rows(self._as_channels(h_all[i]), self._d, self._w,
+                                     out=out[i:i + 1])
+        elif (getattr(tm, "can_pipeline", False)
+              and (host := self._get_ll_fused(tm, params, args, kwargs, out, dh=True))
+              is not None):
+            pass
+        elif getattr(tm, "can_pipeline", False):
+            P = self._pipeline_for(tm)
+            P.order_after_current()
+            _prefetch(tm, params, args, kwargs)
+            for i, params_i in enumerate(params):
+                j = P.next_slot()
+                slot = tm.submit(P, self._pbufs[j], *params_i, *args, order=False, **kwargs)
+                with torch.cuda.stream(P.stream(slot)):
+                    self._preds[slot].dh_hh_rows(self._pbufs[slot], self._d, self._w_templ,
+                                                 out=out[i:i + 1])
+            P.wait()
+        elif getattr(tm, "can_fill_batch", False) and not args:
+            G = min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
+                        or int(getattr(tm, "WINDOW_GROUP", 8))), _lib.EFD_DH_MAX_ROWS)
+            rows = getattr(self, "_dh_rows", None)
+            if rows is None or tuple(rows.shape) != (G, nch, nb):
+                rows = self._dh_rows = torch.empty((G, nch, nb), dtype=torch.complex128,
+                                                   device=self.device)
+            _prefetch(tm, params, args, kwargs, concurrency=G if G < num_likes else None)
+            for g0 in range(0, num_likes, G):
+                m = len(params[g0:g0 + G])
+                tm.fill_batch(rows[:m], params[g0:g0 + m], **kwargs)
+                self._red.dh_hh_rows(rows[:m], self._d, self._w_templ, out=out[g0:g0 + m])
+        elif getattr(tm, "can_fill", False):
+            if self._buf is None or tuple(self._buf.shape) != (nch, nb):
+                self._buf = torch.empty((nch, nb), dtype=torch.complex128, device=self.device)
+            _prefetch(tm, params, args, kwargs)
+            for i, params_i in enumerate(params):
+                tm.fill(self._buf, *params_i, *args, **kwargs)
+                self._red.dh_hh_rows(self._buf, self._d, self._w_templ, out=out[i:i + 1])
+        else:
+            for i, params_i in enumerate(params):
+                h = self._as_channels(tm(*params_i, *args, **kwargs))
+                self._red.dh_hh_rows(h, self._d, self._w, out=out[i:i + 1])
+        if self.noise_has_been_added:
+            raise NotImplementedError
+        if self.use_gpu and self.return_cupy:
+            return torch.complex(out[:, 0], out[:, 1]), out[:, 2].clone()
+        if host is None:
+            host = out.cpu().numpy()
+        return host[:, 0] + 1j * host[:, 1], host[:, 2].copy()
+
     def get_ll(self, params, *args, **kwargs):
         torch = self.torch
+        if self.separate_d_h:
+            return self.parts(params, *args, **kwargs)
         if self.frequency_domain is False:
             raise NotImplementedError("a dt-only (time-domain data) likelihood is not part of "
                                       "the FD path")
@@ -310,7 +394,7 @@ class Likelihood:
     # launch ahead of the first group (pe.setup(trajectory="device"); efd_traj_batch)
     device_trajectory = False
 
-    def _get_ll_fused(self, tm, params, args, kwargs, out):
+    def _get_ll_fused(self, tm, params, args, kwargs, out, dh=False):
         """The pipelined path with the likelihood fused into the mode sum: per group of
         FUSED_GROUP walkers, the template chain collects each walker's host inputs
         (BatchPreparer), one upload and one efd_modesum_prepare_batch prepare the group on its
@@ -336,7 +420,11 @@ class Likelihood:
         host route): the caller then takes the per-walker path. A walker whose preparation or
         sum raised a device-side error comes back NaN from the kernel
         (efd_modesum_sum_loglike), and only then are the groups' status flags read, which
-        raises."""
+        raises.
+
+        dh (Likelihood.parts): out is [n][3] and every group's sum is BatchPreparer.sum_dh_hh
+        behind the Python steps (flush / flush_device), which needs no tile constants; the
+        host result is [n][3]."""
         torch = self.torch
         from .summation import BatchPreparer
         from .waveform import GenerateEMRIWaveform
@@ -354,8 +442,9 @@ class Likelihood:
         else:
             _prefetch(tm, params, args, kwargs)
         n = len(params)
+        per = 3 if dh else 1     # doubles per walker in out
         if n == 0:
-            return np.empty(0, dtype=np.float64)
+            return np.empty((0, 3) if dh else 0, dtype=np.float64)
         ngroups = -(-n // (_lib.EFD_BATCH_MAX if device else self.FUSED_GROUP))
         G = -(-n // ngroups)                       # balanced groups of at most that many
         caustic = getattr(getattr(getattr(tm.waveform_generator, "waveform_generator", None),
@@ -391,9 +480,9 @@ class Likelihood:
         _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
                                         arr, len(arr)), "efd_stream_order", lib)
         pin = F.get("pin")
-        if pin is None or pin.numel() < n:
-            pin = F["pin"] = torch.empty(max(n, 64), dtype=torch.float64, pin_memory=True)
-        native = self.FUSED_NATIVE_GROUP and hasattr(lib, "efd_fused_group")
+        if pin is None or pin.numel() < per * n:
+            pin = F["pin"] = torch.empty(max(per * n, 64), dtype=torch.float64, pin_memory=True)
+        native = self.FUSED_NATIVE_GROUP and hasattr(lib, "efd_fused_group") and not dh
         used = []
         try:
             batch = getattr(tm, "submit_batch", None)
@@ -424,6 +513,10 @@ class Likelihood:
                         continue
                     gi, jobs = B.flush()
                 used.append(gi)
+                if dh:
+                    B.sum_dh_hh(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
+                                sst.cuda_stream)
+                    continue
                 tc = self._tile_constants(freq, k0, sst, B)
                 B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
                               sst.cuda_stream, tile_const=tc)
@@ -432,7 +525,7 @@ class Likelihood:
             for gj in sorted(set(used) - {last}):
                 _lib.check(lib.efd_stream_order(gst[gj], (ctypes.c_void_p * 1)(gst[last]), 1),
                            "efd_stream_order", lib)
-            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * n, gst[last]),
+            _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * per * n, gst[last]),
                        "efd_download", lib)
         finally:
             for f in futs:
@@ -448,7 +541,9 @@ class Likelihood:
                     B.stream(gi).synchronize()
             elif used:
                 B.stream(used[-1]).synchronize()
-        host = pin[:n].numpy().copy()
+        host = pin[:per * n].numpy().copy()
+        if dh:
+            host = host.reshape(n, 3)
         if np.isnan(host).any():
             B.wait()   # device-side errors of the groups' workspaces (sticky across reuse)
         return host
@@ -545,6 +640,8 @@ class Likelihood:
             if self.fill_data_noise:
                 args_in += (self.injection_channels, self.noise_factor)
             out_ll.append(_to_numpy(self.get_ll(*args_in, **kwargs)))
+        if self.separate_d_h:   # (<d|h>, <h|h>) per subset: each concatenated on its own
+            return tuple(np.concatenate([o[k] for o in out_ll], axis=0) for k in range(2))
         return np.concatenate(out_ll, axis=0)
 
 
@@ -570,3 +667,150 @@ def _to_numpy(x):
     if hasattr(x, "detach"):
         return x.detach().cpu().numpy()
     return np.asarray(x)
+
+
+# ---- what the (<d|h>, <h|h>) pair is for: host arithmetic on float64 arrays [B] ---------------
+def profile_none(d_d, re_dh, h_h):
+    """logL = -1/2 (d_d - 2 Re <d|h> + <h|h>)."""
+    return -0.5 * (d_d - 2.0 * np.asarray(re_dh, dtype=np.float64)
+                   + np.asarray(h_h, dtype=np.float64))
+
+
+def profile_amplitude(d_d, re_dh, h_h):
+    """The logL maximised over an overall amplitude A >= 0 of the template, in closed form:
+    (-1/2 d_d + 1/2 max(Re <d|h>, 0)^2 / <h|h>, A_hat = max(Re <d|h>, 0) / <h|h>); a walker
+    with <h|h> = 0 (no template) has A_hat = 0 and no gain."""
+    re = np.maximum(np.asarray(re_dh, dtype=np.float64), 0.0)
+    hh = np.asarray(h_h, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        A = np.where(hh > 0.0, re / hh, 0.0)
+    return -0.5 * d_d + 0.5 * re * A, A
+
+
+# k of the break points u* +- k sigma of the distance quadrature's panels
+_PEAK_K = (0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 5.0, 6.0, 8.0, 10.0, 12.0, 16.0, 24.0, 40.0)
+_PANEL_MAX = 0.25    # the widest panel in log u
+DISTANCE_NODES = 16  # Gauss-Legendre nodes per panel
+
+
+def _distance_panels(re, hh, u_lo, u_hi):
+    """The panels' break points in t = log u for one walker: the range's ends, the Gaussian
+    factor's u* +- k sigma (u* = Re <d|h> / <h|h>, sigma = <h|h>^(-1/2)), a geometric ladder in
+    from each end at that end's decay length 1 / |Re <d|h> - u <h|h>| (a peak far outside the
+    range leaves an exponential against the nearer end), and a uniform split of what is still
+    wider than _PANEL_MAX."""
+    pts = [u_lo, u_hi]
+    if hh > 0.0:
+        us, sg = re / hh, hh ** -0.5
+        for k in _PEAK_K:
+            pts += [us - k * sg, us + k * sg]
+        pts.append(us)
+    for edge, sign in ((u_lo, 1.0), (u_hi, -1.0)):
+        slope = abs(re - edge * hh)
+        if slope > 0.0:
+            step = 1.0 / slope
+            while step < u_hi - u_lo:
+                pts.append(edge + sign * step)
+                step *= 2.0
+    t = np.log(np.unique(np.clip(np.asarray(pts, dtype=np.float64), u_lo, u_hi)))
+    out = [t[:1]]
+    for a, b in zip(t[:-1], t[1:]):
+        m = max(1, int(np.ceil((b - a) / _PANEL_MAX)))
+        out.append(a + (b - a) * np.arange(1, m + 1) / m)
+    return np.concatenate(out)
+
+
+def marginalize_distance(d_d, re_dh, h_h, dist_ref, dist_range, prior_power=2,
+                         nodes=DISTANCE_NODES):
+    """log of the likelihood marginalised over the distance D of a template made at dist_ref,
+      log int pi(D) exp(-1/2 d_d + u Re <d|h> - 1/2 u^2 <h|h>) dD,  u = dist_ref / D,
+    with pi proportional to D^prior_power, normalised on dist_range = (lo, hi). Per walker a
+    composite Gauss-Legendre rule in t = log u (dD = -D dt: the power-law prior and Jacobian are
+    smooth there) over _distance_panels' panels, `nodes` nodes each, summed in log-sum-exp form:
+    finite for <h|h> = 0 (the integrand is then the prior alone, log = -1/2 d_d) and for peaks
+    of any height."""
+    re = np.atleast_1d(np.asarray(re_dh, dtype=np.float64))
+    hh = np.atleast_1d(np.asarray(h_h, dtype=np.float64))
+    lo, hi = float(dist_range[0]), float(dist_range[1])
+    if not (0.0 < lo < hi) or not dist_ref > 0.0:
+        raise ValueError("marginalize_distance: 0 < lo < hi and dist_ref > 0")
+    p = float(prior_power)
+    # log of the prior's norm int_lo^hi D^p dD, with D in units of hi (no overflow)
+    lognorm = (np.log(np.log(hi / lo)) if p == -1.0
+               else np.log((1.0 - (lo / hi) ** (p + 1.0)) / (p + 1.0))) + (p + 1.0) * np.log(hi)
+    u_lo, u_hi = dist_ref / hi, dist_ref / lo
+    x, wq = np.polynomial.legendre.leggauss(int(nodes))
+    out = np.empty(len(re), dtype=np.float64)
+    for i in range(len(re)):
+        t = _distance_panels(re[i], hh[i], u_lo, u_hi)
+        a, b = t[:-1, None], t[1:, None]
+        tt = 0.5 * (a + b) + 0.5 * (b - a) * x[None, :]
+        ww = 0.5 * (b - a) * wq[None, :]
+        u = np.exp(tt)
+        # pi(D) dD = D^(p + 1) dt / norm, D = dist_ref / u
+        L = np.log(ww) + (p + 1.0) * (np.log(dist_ref) - tt) + u * re[i] - 0.5 * u * u * hh[i]
+        m = L.max()
+        out[i] = m + np.log(np.exp(L - m).sum()) - lognorm
+    return -0.5 * d_d + out
+
+
+class ProfiledLikelihood:
+    """A Likelihood's logL with the template's overall amplitude (the source's distance) taken
+    out, from Likelihood.parts' pair: a callable (params, **kwargs) -> float64 [B] that a sampler
+    takes as its log-likelihood. The parameters go through the likelihood's own __call__ (its
+    transforms and subset batching).
+
+    mode: "none", -1/2 (d_d - 2 Re <d|h> + <h|h>): the plain logL from the pair;
+          "amplitude", profile_amplitude's closed form; `last` then holds A_hat and, with
+            dist_ref, D_hat = dist_ref / A_hat of the last call;
+          "distance", marginalize_distance over dist_range with the prior D^prior_power, the
+            templates being made at distance dist_ref.
+    snr(params, **kwargs) returns (sqrt <h|h>, Re <d|h> / sqrt <h|h>): the optimal and the
+    matched-filter SNR of every walker."""
+
+    MODES = ("none", "amplitude", "distance")
+
+    def __init__(self, like, mode, dist_ref=None, dist_range=None, prior_power=2):
+        if mode not in self.MODES:
+            raise ValueError(f"mode: one of {self.MODES}")
+        if mode == "distance" and (dist_ref is None or dist_range is None):
+            raise ValueError("mode 'distance' needs dist_ref and dist_range")
+        self.like, self.mode = like, mode
+        self.dist_ref, self.dist_range, self.prior_power = dist_ref, dist_range, prior_power
+        self.last = {}
+
+    def parts(self, params, **kwargs):
+        """(<d|h> complex128 [B], <h|h> float64 [B]) through the likelihood's __call__."""
+        like = self.like
+        keep = like.separate_d_h
+        like.separate_d_h = True
+        try:
+            d_h, h_h = like(params, **kwargs)
+        finally:
+            like.separate_d_h = keep
+        return d_h, h_h
+
+    def combine(self, d_d, d_h, h_h):
+        """The mode's logL from given numbers (host arithmetic only)."""
+        re = np.real(d_h)
+        if self.mode == "none":
+            return profile_none(d_d, re, h_h)
+        if self.mode == "amplitude":
+            ll, A = profile_amplitude(d_d, re, h_h)
+            self.last = {"A_hat": A}
+            if self.dist_ref is not None:
+                with np.errstate(divide="ignore"):
+                    self.last["D_hat"] = np.where(A > 0.0, self.dist_ref / A, np.inf)
+            return ll
+        return marginalize_distance(d_d, re, h_h, self.dist_ref, self.dist_range,
+                                    self.prior_power)
+
+    def __call__(self, params, **kwargs):
+        d_h, h_h = self.parts(params, **kwargs)
+        return self.combine(self.like.d_d, d_h, h_h)
+
+    def snr(self, params, **kwargs):
+        d_h, h_h = self.parts(params, **kwargs)
+        rho = np.sqrt(h_h)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return rho, np.where(rho > 0.0, np.real(d_h) / rho, 0.0)

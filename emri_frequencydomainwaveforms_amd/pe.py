@@ -39,6 +39,7 @@ class PESetup:
     f_like: np.ndarray       # the likelihood's frequencies (f >= 0 of the template grid)
     half_step: int           # walkers per Likelihood call (ntemps * nwalkers / 2)
     info: dict = field(default_factory=dict)
+    marg: object = None      # setup(marginalize=...): likelihood.ProfiledLikelihood around `like`
 
     def half_steps(self):
         """The start's walker batches, one per red-blue half-step."""
@@ -49,7 +50,8 @@ class PESetup:
 def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None, nwalkers=16,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
           window=None, start_cov=None, template="fd", injectFD=None, upstream="host",
-          mode_selector_kwargs=None, trajectory="host"):
+          mode_selector_kwargs=None, trajectory="host", marginalize=None,
+          dist_range=(0.1, 10.0)):
     """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
     generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
     not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
@@ -78,7 +80,14 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     trajectories are integrated on the device as well, all of a likelihood call's in one launch
     (Likelihood.device_trajectory; efd_traj_batch). The injection is the same.
     mode_selector_kwargs: passed to both generators, e.g. dict(sensitivity_fn=get_sensitivity)
-    for the noise-weighted mode selection (amplitude.ModeSelector)."""
+    for the noise-weighted mode selection (amplitude.ModeSelector).
+    marginalize: None, "amplitude" or "distance": PESetup.marg is then a
+    likelihood.ProfiledLikelihood around `like` (the logL maximised over the template's overall
+    amplitude, or marginalised over the distance on dist_range = (lo, hi) Gpc with a D^2 prior),
+    a log-likelihood function of the same sampled coordinates in which the fixed distance of the
+    templates is only the reference. `like` and the rest of the setup do not change."""
+    if marginalize not in (None, "amplitude", "distance"):
+        raise ValueError("marginalize: None, 'amplitude' or 'distance'")
     if template not in ("fd", "td"):
         raise ValueError("template: 'fd' or 'td'")
     from .waveform import GenerateEMRIWaveform, _check_trajectory, _check_upstream
@@ -182,9 +191,13 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
         import gc
         gc.collect()
         gc.freeze()
+    marg = None
+    if marginalize is not None:
+        from .likelihood import ProfiledLikelihood
+        marg = ProfiledLikelihood(like, marginalize, dist_ref=dist, dist_range=dist_range)
     return PESetup(few=few, gen=gen, like=like, transform=tc, truth14=injection,
                    truth6=truth6, start=start, kwargs=kw, f_like=f_like,
-                   half_step=max(1, nwalkers * ntemps // 2), info=info)
+                   half_step=max(1, nwalkers * ntemps // 2), info=info, marg=marg)
 
 
 class _SampledToWaveform:

@@ -273,6 +273,35 @@ class Reducer:
                        "efd_td_split_pair_stats", self.lib)
         return out
 
+    def dh_hh_rows(self, rows, d, w, out=None):
+        """(Re <d|h_r>, Im <d|h_r>, <h_r|h_r>) of every written template row against one
+        weighted data d and weight w (efd_dh_hh_rows; the fused mode sum's terms, see
+        include/emrifd.h) as a float64 [nrow][3] device tensor.
+
+        rows: complex128 [nrow][nchan][nbin] (or one template [nchan][nbin]), nchan 1 or 2,
+        contiguous rows a fixed stride apart; d: complex128 [nchan][nbin]; w: float64
+        [nchan][nbin]. More than EFD_DH_MAX_ROWS rows go in several calls; a row's numbers are
+        bitwise what any other split gives."""
+        torch = self.torch
+        if rows.dim() == 2:
+            rows = rows[None]
+        ph, sh, nrow, nchan, nbin = self._pair_rows(rows, "rows")
+        pd = self._check(d, "d", torch.complex128, (nchan, nbin))
+        pw = self._check(w, "w", torch.float64, (nchan, nbin))
+        if out is None:
+            out = torch.empty((nrow, 3), dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() < 3 * nrow or not out.is_contiguous():
+            raise ValueError(f"dh_hh_rows: out float64 [{nrow}][3], contiguous")
+        scr = self._scratch("_scr_dh", _lib.EFD_DH_SCRATCH)
+        M = _lib.EFD_DH_MAX_ROWS
+        for r0 in range(0, nrow, M):
+            n = min(M, nrow - r0)
+            _lib.check(self.lib.efd_dh_hh_rows(ph + 16 * sh * r0, sh, n, pd, pw, nchan, nbin,
+                                               out.data_ptr() + 24 * r0, scr.data_ptr(),
+                                               self._stream()),
+                       "efd_dh_hh_rows", self.lib)
+        return out
+
     def window_rows(self, h, windows, out):
         """out[j] = windows[j] * h for every window of one series (efd_window_rows): h
         complex128 [n]; windows: float64 [n] tensors, or None for the unwindowed copy; out:

@@ -442,6 +442,46 @@ def sum_batch_loglike(jobs, d, w, out, stream=None, tile_const=None):
     return wss
 
 
+def _check_dh_out(torch, out, n):
+    if out.dtype != torch.float64 or out.numel() < 3 * n or not out.is_contiguous():
+        raise ValueError(f"sum_batch_dh_hh: out float64 [{n}][3], contiguous")
+
+
+def sum_batch_dh_hh(jobs, d, w, out, stream=None, dense=False, part=None):
+    """<d|h> and <h|h> of several prepared waveforms from the mode sum's epilogue
+    (efd_modesum_sum_dh_hh): out[i] = (Re <d|h_i>, Im <d|h_i>, <h_i|h_i>), 4 sum conj(d) h w and
+    4 sum |h w|^2 over both channels, h_i never written to HBM.
+
+    jobs, d, w: as sum_batch_loglike; out: float64 [len(jobs)][3] on the device. dense: visit
+    every tile (the sparse launch's A/B switch; bitwise the same numbers). part: float64
+    [>= 3 len(jobs) efd_loglike_tile_count(nf)] for the tiles' partials (its contents do not
+    matter), or None to allocate it. At most EFD_BATCH_MAX waveforms."""
+    torch = _torch()
+    jobs = list(jobs)
+    if jobs:   # (none: the marshaller's count check raises)
+        kw0 = jobs[0][1]
+        _check_ll_io(torch, d, w, torch.empty(1, dtype=torch.float64),
+                     int(kw0["freq"].numel()) - int(kw0.get("k0", 0)), 1)
+        _check_dh_out(torch, out, len(jobs))
+
+    def one(i, eng, kw):
+        kw = dict(kw)
+        a = kw.pop("_args", None)   # the prepare call's own struct, as it is
+        return (a, eng._ws) if a is not None else eng._args(**kw)
+
+    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_dh_hh", jobs, one, stream)
+    need = 3 * n * int(lib.efd_loglike_tile_count(int(jobs[0][1]["freq"].numel())))
+    if part is None:
+        part = torch.empty(need, dtype=torch.float64, device=d.device)
+    elif part.dtype != torch.float64 or part.numel() < need or not part.is_contiguous():
+        raise ValueError(f"sum_batch_dh_hh: part float64 [>= {need}], contiguous")
+    _lib.check(lib.efd_modesum_sum_dh_hh(pa, pw, pb, n, torch.view_as_real(d).data_ptr(),
+                                         w.data_ptr(), part.data_ptr(), 1 if dense else 0,
+                                         out.data_ptr(), st),
+               "efd_modesum_sum_dh_hh", lib)
+    return wss
+
+
 class WaveformPipeline:
     """Several FD waveforms in flight on one device.
 
@@ -617,6 +657,7 @@ class _Group:
         self.arg_views = [self.args[i] for i in range(size)]   # stable per-walker views
         self.tmpl = None      # (key, template struct) of the last flush (BatchPreparer._take)
         self.ws_floor = None  # (device, smallest workspace, walkers) flush_loglike sized last
+        self.dh_part = None   # sum_dh_hh's tile partials (grown on the group's stream)
         # (first, count, args**, workspaces*, bytes*) per launch of at most EFD_BATCH_MAX of
         # the group's first n walkers, for every n: pointers into the arrays above
         self.chunks = [None]
@@ -960,6 +1001,30 @@ class BatchPreparer:
                 _lib.check(self.lib.efd_modesum_sum_loglike_ex(
                     pa_c, pw_c, pb_c, cnt, dp, wp, tile_const.data_ptr(), op + 8 * c0, stream),
                     "efd_modesum_sum_loglike_ex", self.lib)
+
+    def sum_dh_hh(self, gi, d, w, out, stream, dense=False):
+        """efd_modesum_sum_dh_hh over group gi's last flush, in launches of EFD_BATCH_MAX
+        walkers like sum_loglike: out float64 [n][3] = (Re <d|h>, Im <d|h>, <h|h>) per walker;
+        d, w as sum_batch_loglike. `stream` is the group's (its partials buffer, grown here
+        when the grid or the group outgrows it, belongs to that stream)."""
+        torch = _torch()
+        G = self.groups[gi]
+        n = G.n
+        nf = int(G.args[0].nf)
+        _check_ll_io(torch, d, w, torch.empty(1, dtype=torch.float64), nf - int(G.args[0].k0), 1)
+        _check_dh_out(torch, out, n)
+        per = 3 * int(self.lib.efd_loglike_tile_count(nf))
+        if G.dh_part is None or G.dh_part.numel() < per * n:
+            with torch.cuda.stream(G.stream):
+                G.dh_part = torch.empty(per * max(n, len(G.engines)), dtype=torch.float64,
+                                        device=self.device)
+        dp, wp, op = torch.view_as_real(d).data_ptr(), w.data_ptr(), out.data_ptr()
+        pp = G.dh_part.data_ptr()
+        for c0, cnt, pa_c, pw_c, pb_c in G.chunks[n]:
+            _lib.check(self.lib.efd_modesum_sum_dh_hh(pa_c, pw_c, pb_c, cnt, dp, wp,
+                                                      pp + 8 * per * c0, 1 if dense else 0,
+                                                      op + 24 * c0, stream),
+                       "efd_modesum_sum_dh_hh", self.lib)
 
     def release(self, gi, event):
         """The group's workspaces and inputs are free again once `event` (recorded after the sum

@@ -198,6 +198,32 @@ int efd_modesum_sum_loglike_ex(const efd_modesum_args* const* a, void* const* wo
                                const double* w, const double* tile_const, double* out,
                                void* stream);
 
+/*
+ * <d|h> and <h|h> of each waveform from the mode sum's epilogue, the templates again never
+ * written (Likelihood.parts; lisatools' separate_d_h pair, inner_product(d, h, complex=True)'s
+ * convention, diagnostic.py:103-110). With hw = h_c[j] * w[c][j] (each component's product
+ * rounded, efd_loglike's rule) and dv = d[c][j], per bin and channel, as written (no contraction):
+ *   t_re = fma(dv.x, hw.x, dv.y * hw.y)
+ *   t_im = dv.x * hw.y - dv.y * hw.x      (two rounded products and their difference)
+ *   t_hh = fma(hw.x, hw.x, hw.y * hw.y)
+ *   out[3 i + 0] = Re <d|h> = 4 sum t_re,  out[3 i + 1] = Im <d|h> = 4 sum t_im,
+ *   out[3 i + 2] = <h|h> = 4 sum t_hh,  so that logL = -1/2 (<d|d> - 2 Re <d|h> + <h|h>).
+ * The three sums take their terms in the same order: a d equal to h w bit for bit gives
+ * Re <d|h> == <h|h> bitwise and Im <d|h> == 0.0. a, workspace, d, w: efd_modesum_sum_loglike's,
+ * with its argument checks; w must be finite (a zero weight drops a bin). part: caller-owned
+ * device doubles [count][3][efd_loglike_tile_count(nf)] for the tiles' partials; every entry the
+ * call reads it has written itself. A tile no harmonic reaches adds exactly 0, so the sparse
+ * launch (only the tiles of each waveform's lane range; taken under efd_modesum_sum_loglike_ex's
+ * rule, without needing constants) equals the dense one bitwise; flags bit 0 forces the dense
+ * launch. Fixed reduction orders: bitwise reproducible, and a waveform's numbers do not depend
+ * on the batch around it. A waveform whose workspace holds a device-side error flag gets three
+ * NaN and keeps its flags (efd_modesum_status_batch). out: [count][3] device doubles.
+ */
+int efd_modesum_sum_dh_hh(const efd_modesum_args* const* a, void* const* workspace,
+                          const size_t* workspace_bytes, int32_t count, const double* d,
+                          const double* w, double* part, int32_t flags, double* out,
+                          void* stream);
+
 /* Synchronises `stream` and reports errors detected on the device by the calls on this
  * workspace since the previous efd_modesum_status (the flags are sticky across preparations, so
  * a workspace reused by several waveforms before its status is read loses none): a harmonic
@@ -571,6 +597,24 @@ int efd_td_split_pair_stats(const double* Z, int64_t stride, int64_t n, int32_t 
                             const uint8_t* keep, double* out, double* scratch, void* stream);
 
 /*
+ * efd_modesum_sum_dh_hh's three numbers for templates that were written: row r, complex
+ * [nchan][nbin] at h + 2 r row_stride doubles (row_stride >= nchan nbin), against one d complex
+ * [nchan][nbin] and one w real [nchan][nbin]; out[3 r ..] = (Re <d|h>, Im <d|h>, <h|h>), the same
+ * three terms per bin and channel. 1 <= nrow <= EFD_DH_MAX_ROWS, nchan 1 or 2; scratch:
+ * EFD_DH_SCRATCH device doubles. Every element of h is read once; d and w once per row (from the
+ * XCD's cache after the first). efd_pair_stats' promises: no atomics, a partition that depends on
+ * nbin only, fixed orders (bitwise reproducible); a row's numbers are the same alone or beside
+ * other rows; with d == h w bit for bit Re <d|h> == <h|h> and Im <d|h> == 0.0. EFD_ERR_ARG before
+ * any launch: NULL h, d, w, out or scratch, nrow or nchan out of range, nbin <= 0, row_stride too
+ * small.
+ */
+#define EFD_DH_MAX_ROWS 64
+#define EFD_DH_SCRATCH 196608
+int efd_dh_hh_rows(const double* h, int64_t row_stride, int32_t nrow, const double* d,
+                   const double* w, int32_t nchan, int64_t nbin, double* out, double* scratch,
+                   void* stream);
+
+/*
  * Every windowing of one series from one read of it: out[j][k] = win[j][k] h[k] (real times
  * complex, each part one product), h complex [n], win: HOST array of nwin device pointers to
  * real windows [n], 1 <= nwin <= EFD_WINDOW_MAX_ROWS; a NULL entry copies the series bit for bit
@@ -623,6 +667,9 @@ int efd_pair_stats_cpu(const double* a, int64_t a_stride, const double* b, int64
 int efd_td_split_pair_stats_cpu(const double* Z, int64_t stride, int64_t n, int32_t rows,
                                 double gain, const double* a, int64_t a_stride, const double* w,
                                 const uint8_t* keep, double* out, double* scratch, void* stream);
+int efd_dh_hh_rows_cpu(const double* h, int64_t row_stride, int32_t nrow, const double* d,
+                       const double* w, int32_t nchan, int64_t nbin, double* out,
+                       double* scratch, void* stream);
 int efd_window_rows_cpu(const double* h, int64_t n, const double* const* win, int32_t nwin,
                         double* out, int64_t out_stride, void* stream);
 /* OpenMP threads of the twins (n <= 0: all available); returns the previous setting. */
