@@ -2,9 +2,9 @@
 source is compiled to an object under build/, all of them at once, and one link step follows:
 
   csrc/emrifd_cpu.cpp, emrifd_reduce_cpu.cpp -> g++ -O3 -march=x86-64-v4 -fopenmp
-                         -ffp-contract=off each (the host twins, efd_*_cpu: the mode sum's and the
-                         reductions'; AVX-512 is on both this container's Sapphire Rapids and the
-                         GPU box's EPYC 9575F)
+                         -ffp-contract=off each (the host twins, efd_*_cpu: the mode sum's, the
+                         reductions' and the noise draws'; AVX-512 is on both this container's
+                         Sapphire Rapids and the GPU box's EPYC 9575F)
   csrc/emrifd_host.cpp -> g++ -O3 -fopenmp: the host upstream stand-ins (trajectory, p0 solve) in C++,
   the walker batches' staging and the PSD table of the noise-weighted mode selection
   (csrc/emrifd_psd.h: its NaN and sign guards need a unit built without -ffast-math)
@@ -13,13 +13,15 @@ source is compiled to an object under build/, all of them at once, and one link 
   csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode
                          sum, its preparation, the window path, the channel split and reductions)
                          and emrifd_traj.hip (UPSTREAM_HIP_UNITS: the device trajectories and p0
-                         solve, upstream of that chain)
+                         solve, upstream of that chain) and emrifd_noise.hip (NOISE_HIP_UNITS:
+                         the noise draws and their overlaps; csrc/emrifd_noise.h is shared with
+                         emrifd_reduce_cpu.cpp)
                          -> hipcc --offload-arch=gfx950 -c each; all share csrc/emrifd_common.h,
                          the first two also csrc/emrifd_layout.h (no relocatable device code);
                          emrifd_prepare.hip includes csrc/emrifd_modes_device.inc (amplitudes and
                          mode selection on the device); emrifd_traj.hip includes
                          csrc/traj_costab.inc (the host's cosine table)
-  link                -> hipcc -shared over the nine objects, with libgomp and libmvec
+  link                -> hipcc -shared over the ten objects, with libgomp and libmvec
 """
 
 import glob
@@ -34,7 +36,9 @@ HIP_UNITS = [SRC, os.path.join(CSRC, "emrifd_prepare.hip"), os.path.join(CSRC, "
              os.path.join(CSRC, "emrifd_reduce.hip")]
 # the HIP units upstream of that chain (the same flags; they share emrifd_common.h only)
 UPSTREAM_HIP_UNITS = [os.path.join(CSRC, "emrifd_traj.hip")]
-ALL_HIP_UNITS = HIP_UNITS + UPSTREAM_HIP_UNITS
+# the noise realisations' unit (the same flags; six HIP units in all)
+NOISE_HIP_UNITS = [os.path.join(CSRC, "emrifd_noise.hip")]
+ALL_HIP_UNITS = HIP_UNITS + UPSTREAM_HIP_UNITS + NOISE_HIP_UNITS
 CPU_SRC = os.path.join(CSRC, "emrifd_cpu.cpp")
 REDUCE_CPU_SRC = os.path.join(CSRC, "emrifd_reduce_cpu.cpp")
 HOST_SRC = os.path.join(CSRC, "emrifd_host.cpp")
@@ -107,7 +111,7 @@ def build(force=False, verbose=False, extra=()):
     os.makedirs(OBJDIR, exist_ok=True)
     gxx = ["g++", "-O3", f"-march={CPU_ARCH}", "-fPIC", "-std=c++17", "-fopenmp"]
     bid = [f'-DEFD_BUILD_ID="{sid}"'] if not extra else []
-    # the longest compile (the mode sum) first; nine compilers at once, one per source
+    # the longest compile (the mode sum) first; ten compilers at once, one per source
     cmds = [hip_compile_cmd(s, obj_path(s), (*bid, *extra)) for s in ALL_HIP_UNITS]
     cmds += [[*gxx, "-ffp-contract=off", "-c", s, "-o", obj_path(s)]
              for s in (CPU_SRC, REDUCE_CPU_SRC, HOST_SRC)]

@@ -33,6 +33,9 @@ EFD_DH_SCRATCH = 196608   # efd_dh_hh_rows' scratch doubles (1024 chunks x 64 ro
 EFD_WINDOW_MAX_ROWS = 16   # efd_window_rows' windows per call
 EFD_MODES_AMP_OVERFLOW = 1   # efd_modes_select_batch's status bit: amp capacity too small
 EFD_TRAJ_MAX_LEN = 1024   # efd_traj_batch's longest knot slab
+EFD_NOISE_MAX_ROWS = 16   # efd_noise_overlap_rows' rows per call
+EFD_NOISE_DRAWS_PER_LAUNCH = 256
+EFD_NOISE_SCRATCH = 1048576   # its scratch doubles (256 workgroups x 256 draws x 16 rows)
 # efd_traj_batch's and efd_traj_p_at_t_batch's per-source status words
 EFD_TRAJ_OK = 0
 EFD_TRAJ_BAD_SOURCE = 1
@@ -121,6 +124,11 @@ EXPORTED_SYMBOLS = (
     "efd_modes_select_batch_weighted",
     "efd_traj_batch",
     "efd_traj_p_at_t_batch",
+    "efd_noise_fd",
+    "efd_noise_overlap_rows",
+    "efd_noise_fd_cpu",
+    "efd_noise_overlap_rows_cpu",
+    "efd_noise_philox_cpu",
 )
 
 
@@ -473,6 +481,16 @@ def load(path=None):
         lib.efd_traj_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp]
         lib.efd_traj_p_at_t_batch.restype = ctypes.c_int
         lib.efd_traj_p_at_t_batch.argtypes = [vp, i32, dbl, dbl, vp, vp, vp]
+    if hasattr(lib, "efd_noise_fd"):   # noise realisations (absent only in older builds)
+        u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+        for name in ("efd_noise_fd", "efd_noise_fd_cpu"):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = [vp, vp, i32, i64, u64, u64, u32, i32, vp]
+        for name in ("efd_noise_overlap_rows", "efd_noise_overlap_rows_cpu"):
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = [vp, i32, vp, i32, i64, u64, u32, i64, vp, vp, vp]
+        lib.efd_noise_philox_cpu.restype = ctypes.c_int
+        lib.efd_noise_philox_cpu.argtypes = [vp, vp, vp]
     _ = dbl
     if path is None:
         _lib = lib

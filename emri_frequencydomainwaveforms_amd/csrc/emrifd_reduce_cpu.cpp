@@ -1,6 +1,7 @@
 // emrifd_reduce_cpu.cpp -- host twins of emrifd_reduce.hip's entry points (the channel split,
 // the likelihood and inner product, the TD template's split, the Fisher Gram matrix, the overlap
-// rows, the pair statistics, <d|h> and <h|h> of rows, the window rows): the same arithmetic in
+// rows, the pair statistics, <d|h> and <h|h> of rows, the window rows) and of emrifd_noise.hip's
+// (the noise draws and their overlaps with rows, on emrifd_noise.h): the same arithmetic in
 // C++17 with OpenMP on host pointers, with the signatures of the HIP entry points (`stream` and
 // scratch are accepted and unused). Built with contraction off: a product that feeds a sum
 // rounds first unless it is a written fma. Shares emrifd_cpu_internal.h with the mode sum's twin
@@ -14,6 +15,7 @@
 
 #include "../../include/emrifd.h"
 #include "emrifd_cpu_internal.h"
+#include "emrifd_noise.h"
 
 namespace {
 
@@ -377,6 +379,95 @@ int efd_window_rows_cpu(const double* h, int64_t n, const double* const* win, in
             o[2 * k + 1] = wj ? x * h[2 * k + 1] : h[2 * k + 1];
         }
     }
+    return EFD_OK;
+}
+
+// efd_noise_fd's arithmetic: one draw per live bin (emrifd_noise.h), s = 0.5 gain, (s xi_r,
+// s xi_i), added to out under accumulate
+int efd_noise_fd_cpu(double* out, const double* gain, int32_t nchan, int64_t nbin, uint64_t bin0,
+                     uint64_t seed, uint32_t realisation, int32_t accumulate, void* stream) {
+    (void)stream;
+    if (nbin == 0) return EFD_OK;
+    if (!out) return efdcpu::fail(EFD_ERR_ARG, "efd_noise_fd_cpu: NULL out");
+    if (nchan < 1 || nbin < 0)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_noise_fd_cpu: nchan < 1 or nbin < 0");
+    for (int32_t c = 0; c < nchan; ++c) {
+        double* o = out + 2 * (int64_t)c * nbin;
+        const double* g = gain ? gain + (int64_t)c * nbin : nullptr;
+#pragma omp parallel for schedule(static) num_threads(efdcpu::nthreads())
+        for (int64_t i = 0; i < nbin; ++i) {
+            const double gv = g ? g[i] : 1.0;
+            if (!efdnoise::live_gain(gv)) {
+                if (!accumulate) o[2 * i] = o[2 * i + 1] = 0.0;
+                continue;
+            }
+            double xr, xi;
+            efdnoise::draw_xi(seed, realisation, (uint32_t)c, bin0 + (uint64_t)i, xr, xi);
+            const double s = 0.5 * gv;
+            const double vr = s * xr, vi = s * xi;
+            if (accumulate) {
+                o[2 * i] += vr;
+                o[2 * i + 1] += vi;
+            } else {
+                o[2 * i] = vr;
+                o[2 * i + 1] = vi;
+            }
+        }
+    }
+    return EFD_OK;
+}
+
+// efd_noise_overlap_rows' arithmetic: the gain multiplied into the rows' bin once, then per draw
+// fma(xi_r, g h_r, fma(xi_i, g h_i, acc)), channels inside bins, through chunk_sums: an entry
+// does not depend on the other rows or draws. 64 draws at a time bound the partial sums' memory.
+int efd_noise_overlap_rows_cpu(const double* rows, int32_t nrow, const double* gain,
+                               int32_t nchan, int64_t nbin, uint64_t seed, uint32_t real0,
+                               int64_t ndraw, double* out, double* scratch, void* stream) {
+    (void)scratch; (void)stream;
+    if (nrow < 1 || nrow > EFD_NOISE_MAX_ROWS)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_noise_overlap_rows_cpu: nrow outside 1..16");
+    if (nchan < 1 || nbin < 1)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_noise_overlap_rows_cpu: nchan < 1 or nbin < 1");
+    if (ndraw < 0 || (uint64_t)real0 + (uint64_t)ndraw > ((uint64_t)1 << 32))
+        return efdcpu::fail(EFD_ERR_ARG,
+                            "efd_noise_overlap_rows_cpu: real0 + ndraw outside 0..2^32");
+    if (ndraw == 0) return EFD_OK;
+    if (!rows || !out)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_noise_overlap_rows_cpu: NULL rows or out");
+    const int64_t row_stride = (int64_t)nchan * nbin;
+    for (int64_t d0 = 0; d0 < ndraw; d0 += 64) {
+        const int nd = (int)std::min<int64_t>(64, ndraw - d0);
+        chunk_sums(nbin, nd * nrow, out + d0 * nrow, [&](int64_t k0, int64_t k1, double* acc) {
+            double hr[EFD_NOISE_MAX_ROWS], hi[EFD_NOISE_MAX_ROWS];
+            for (int64_t k = k0; k < k1; ++k)
+                for (int32_t c = 0; c < nchan; ++c) {
+                    const int64_t e = (int64_t)c * nbin + k;
+                    const double g = gain ? gain[e] : 1.0;
+                    if (!efdnoise::live_gain(g)) continue;
+                    for (int p = 0; p < nrow; ++p) {
+                        hr[p] = g * rows[2 * (row_stride * p + e)];
+                        hi[p] = g * rows[2 * (row_stride * p + e) + 1];
+                    }
+                    for (int j = 0; j < nd; ++j) {
+                        double xr, xi;
+                        efdnoise::draw_xi(seed, real0 + (uint32_t)(d0 + j), (uint32_t)c,
+                                          (uint64_t)k, xr, xi);
+                        double* a = acc + (int64_t)j * nrow;
+                        for (int p = 0; p < nrow; ++p)
+                            a[p] = std::fma(xr, hr[p], std::fma(xi, hi[p], a[p]));
+                    }
+                }
+        });
+    }
+    return EFD_OK;
+}
+
+int efd_noise_philox_cpu(const uint32_t* counter, const uint32_t* key, uint32_t* words) {
+    if (!counter || !key || !words)
+        return efdcpu::fail(EFD_ERR_ARG, "efd_noise_philox_cpu: NULL argument");
+    uint32_t c[4] = {counter[0], counter[1], counter[2], counter[3]};
+    efdnoise::philox4x32_10(c, key[0], key[1]);
+    for (int i = 0; i < 4; ++i) words[i] = c[i];
     return EFD_OK;
 }
 

@@ -42,6 +42,21 @@ def _reducer(device):
     return _REDUCERS[key]
 
 
+def noise_overlaps(rows, gain, seed, num_draws, real0=0):
+    """<n_r | rows_p> for num_draws noise draws r = real0 ... and every row p, as a float64
+    [num_draws][nrow] device tensor (Reducer.noise_overlap_rows, efd_noise_overlap_rows): sum_c
+    sum_k gain[c][k] Re(conj xi_r(c, k) rows[p][c][k]) with the noise regenerated in registers,
+    never written. rows: complex128 [nrow][nchan][nbin] on the device (at most
+    EFD_NOISE_MAX_ROWS rows, e.g. fisher's derivatives); gain: float64 [nchan][nbin], sqrt(4 df /
+    S) = sqrt(4 fisher_weights) for the likelihood's noise, or None (= 1). The covariance of the
+    result over the draws is then the rows' Fisher matrix 4 sum (df / S) Re(conj a b)."""
+    torch = require_gpu()
+    rows = rows.to(torch.complex128).contiguous()
+    if gain is not None:
+        gain = torch.as_tensor(gain, dtype=torch.float64, device=rows.device).contiguous()
+    return _reducer(rows.device).noise_overlap_rows(rows, gain, seed, num_draws, real0=real0)
+
+
 def _as_channels(sig, torch, device):
     if not isinstance(sig, list):
         sig = [sig]

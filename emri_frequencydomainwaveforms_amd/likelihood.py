@@ -6,7 +6,9 @@ noise_fn = FDutils.get_sensitivity, f_arr = frequency[frequency >= 0]):
 
   inject_signal (:80-234)  data d = inj * sqrt(diff(f)/PSD) and the noise factor
                            w = sqrt(diff(f)/PSD), diff(f)[0] = diff(f)[1]; repeated
-                           injections add up; add_noise raises NotImplementedError (as :199)
+                           injections add up; add_noise=True adds one noise realisation on
+                           the device (the reference raises at :184 and leaves the recipe
+                           below it; see inject_signal)
   get_ll (:236-293)        per walker: template h, ll = -1/2 * 4 * sum |d - h w|^2 over
                            channels and bins, skipping bin 0 when w[0][0] is NaN (:268)
   __call__ (:295-334)      parameter transform, transpose_params, `subset` batching
@@ -66,6 +68,7 @@ class Likelihood:
         self.frequency_domain = df is not None or f_arr is not None
         self.return_cupy = return_cupy
         self.noise_has_been_added = False
+        self.noise_seed = None   # the seed of inject_signal(add_noise=True)'s realisation
         self.torch = torch = require_gpu()
         self.device = torch.device("cuda", torch.cuda.current_device())
         from .reductions import Reducer
@@ -95,7 +98,22 @@ class Likelihood:
 
     # ---------------------------------------------------------------------------------------
     def inject_signal(self, data_stream=None, params=None, waveform_kwargs={}, noise_fn=None,
-                      noise_kwargs={}, add_noise=False):
+                      noise_kwargs={}, add_noise=False, noise_seed=None):
+        """lisatools' inject_signal. add_noise=True adds one stationary noise realisation to
+        the data, once: a later injection into a likelihood that already has noise adds no
+        second one (as the reference's guard, :183). The reference's recipe (:185-199) is
+        n = sqrt(S) (0.5 / sqrt(df)) xi per bin, which in the weighted space d = x sqrt(df / S)
+        is 0.5 xi on every bin whatever the PSD: efd_noise_fd adds it to the weighted data on
+        the device (realisation 0 of the counter-based generator of include/emrifd.h, keyed on
+        noise_seed, channel and bin). It works on df, f_arr and dt grids (the reference sets
+        can_add_noise = False for f_arr, where its add_noise was a silent no-op; on such a grid
+        df is diff_freqs). Bins the likelihood drops (w NaN or 0: f = 0 where the PSD is not
+        finite, and bins outside the template's non_zero_mask) get no noise. noise_seed=None
+        draws a seed from the OS and stores it in self.noise_seed; with more than one
+        torch.distributed rank that raises ValueError, since the replicas' data would differ.
+        noise_likelihood_factor is computed as the reference computes it (:202-207) and kept as
+        an attribute; it is NOT added to logL (the reference marks it "TODO: need to check
+        this", and it is a constant)."""
         torch = self.torch
         # the injection's parameters when the data is exactly the template model's output for
         # them (a single injection, no noise): the windowed logL's per-bin data is then made by
@@ -151,7 +169,7 @@ class Likelihood:
                 can_add_noise = True
             else:
                 freqs = _to_numpy(self.f_arr)
-                can_add_noise = False
+                can_add_noise = True   # (False in the reference; df is diff_freqs here)
         else:
             freqs = np.fft.rfftfreq(self.injection_length, self.dt)
             can_add_noise = True
@@ -164,8 +182,20 @@ class Likelihood:
         diff_freqs[1:] = np.diff(freqs)
         diff_freqs[0] = diff_freqs[1]
         self.base_injections = injection_channels
-        if add_noise and can_add_noise and self.noise_has_been_added is False:
-            raise NotImplementedError   # as the reference (likelihood.py:199)
+        new_noise = bool(add_noise and can_add_noise and self.noise_has_been_added is False)
+        if new_noise:
+            if noise_seed is None:
+                dist = getattr(torch, "distributed", None)
+                if (dist is not None and dist.is_available() and dist.is_initialized()
+                        and dist.get_world_size() > 1):
+                    raise ValueError("inject_signal(add_noise=True) needs noise_seed when "
+                                     "torch.distributed has more than one rank: the replicas' "
+                                     "noise would differ")
+                from .noise import new_seed
+                noise_seed = new_seed()
+            noise_seed = int(noise_seed)
+            if not 0 <= noise_seed < 2 ** 64:
+                raise ValueError("noise_seed: an integer in 0..2^64 - 1")
 
         with np.errstate(invalid="ignore", divide="ignore"):
             nf = np.asarray([(diff_freqs / p) ** 0.5 for p in psd])
@@ -180,7 +210,55 @@ class Likelihood:
                 weighted, device=self.device)
         self.data_length = int(self.injection_channels.shape[1])
         self.psd = psd
-        self._prepare_reduction()
+        if new_noise:
+            # 0.5 xi on every bin that carries weight, added to the weighted data in place
+            self.noise_seed = noise_seed
+            self.injection_channels = self.injection_channels.contiguous()
+            self._red.noise_fd(self.injection_channels, noise_seed, 0, 0, self._noise_live(),
+                               accumulate=True)
+            with np.errstate(invalid="ignore"):
+                self.noise_likelihood_factor = np.sum(
+                    [1.0 / 2.0 * (2 * np.pi) * np.sum(diff_freqs * p) for p in psd])
+            self.noise_has_been_added = True
+        if self.noise_has_been_added:
+            self._inj_call = None   # the data is no longer the template of any parameters
+        self._prepare_reduction()   # (after the noise: drops the tile constants, d_d, _hloc)
+
+    def _noise_live(self):
+        """float64 [nchan][nbin]: 1 on the bins that carry noise, 0 on the bins the likelihood
+        drops (noise factor NaN or 0, column 0 when w[0][0] is NaN, and bins outside the
+        template's non_zero_mask)."""
+        torch = self.torch
+        w = self.noise_factor
+        live = torch.isfinite(w) & (w != 0.0)
+        if bool(torch.isnan(w[0, 0]).item()):
+            live[:, 0] = False
+        tm = self.template_model
+        mask = getattr(tm, "non_zero_mask", None)
+        if mask is not None and getattr(tm, "can_fill", False):
+            live &= mask.to(device=self.device, dtype=torch.bool)[None, :]
+        return live.to(torch.float64).contiguous()
+
+    @property
+    def noise_to_add(self):
+        """The strain noise of the injection, sqrt(S) (0.5 / sqrt(df)) xi per channel and bin
+        (the reference's attribute, :186-195), as a complex128 [nchan][nbin] device tensor
+        regenerated from noise_seed on demand; 0 on the bins that carry no noise."""
+        if not self.noise_has_been_added:
+            raise AttributeError("noise_to_add: no noise has been added")
+        torch = self.torch
+        live = self._noise_live()
+        gain = torch.where(live > 0.0, 1.0 / self.noise_factor, torch.zeros_like(live))
+        out = torch.empty(tuple(live.shape), dtype=torch.complex128, device=self.device)
+        return self._red.noise_fd(out, self.noise_seed, 0, 0, gain.contiguous())
+
+    @property
+    def noise_added_base_injections(self):
+        """base_injections (the last injection's unweighted channels) plus noise_to_add, as a
+        device tensor (the reference's attribute, :210), made on demand."""
+        base = self.torch.as_tensor(np.asarray(self.base_injections, dtype=np.complex128),
+                                    device=self.device)
+        return base + self.noise_to_add
 
     def _prepare_reduction(self):
         """Device copies used by efd_loglike: skip bin 0 by zeroing it when w[0][0] is NaN."""
@@ -269,8 +347,6 @@ class Likelihood:
             for i, params_i in enumerate(params):
                 h = self._as_channels(tm(*params_i, *args, **kwargs))
                 self._red.dh_hh_rows(h, self._d, self._w, out=out[i:i + 1])
-        if self.noise_has_been_added:
-            raise NotImplementedError
         if self.use_gpu and self.return_cupy:
             return torch.complex(out[:, 0], out[:, 1]), out[:, 2].clone()
         if host is None:
@@ -295,8 +371,6 @@ class Likelihood:
                 self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
         elif (getattr(tm, "can_pipeline", False)
               and (host := self._get_ll_fused(tm, params, args, kwargs, out)) is not None):
-            if self.noise_has_been_added:
-                raise NotImplementedError
             if self.use_gpu and self.return_cupy:
                 return out
             return host
@@ -350,8 +424,6 @@ class Likelihood:
             for i, params_i in enumerate(params):
                 h = self._as_channels(tm(*params_i, *args, **kwargs))
                 self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
-        if self.noise_has_been_added:
-            raise NotImplementedError
         if self.use_gpu and self.return_cupy:
             return out
         return out.cpu().numpy()

@@ -51,7 +51,7 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
           ntemps=1, seed=SEED, caustic="uniform", subset=24, window_flag=False, freeze_gc=True,
           window=None, start_cov=None, template="fd", injectFD=None, upstream="host",
           mode_selector_kwargs=None, trajectory="host", marginalize=None,
-          dist_range=(0.1, 10.0)):
+          dist_range=(0.1, 10.0), add_noise=False, noise_seed=None):
     """template: "fd" (get_fd_waveform_fromFD around the FD generator) or "td" (the DFT of the TD
     generator's waveform, get_fd_waveform_fromTD: emri_pe.py -template td, :250-305); "td" does
     not go with downsample (:325-326). For "td", window may also be a 1-D array of the grid's
@@ -85,7 +85,10 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     likelihood.ProfiledLikelihood around `like` (the logL maximised over the template's overall
     amplitude, or marginalised over the distance on dist_range = (lo, hi) Gpc with a D^2 prior),
     a log-likelihood function of the same sampled coordinates in which the fixed distance of the
-    templates is only the reference. `like` and the rest of the setup do not change."""
+    templates is only the reference. `like` and the rest of the setup do not change.
+    add_noise, noise_seed: Likelihood.inject_signal's: one stationary noise realisation added to
+    the weighted data on the device, reproducible from info["noise_seed"] (None without noise;
+    noise_seed=None draws a seed from the OS)."""
     if marginalize not in (None, "amplitude", "distance"):
         raise ValueError("marginalize: None, 'amplitude' or 'distance'")
     if template not in ("fd", "td"):
@@ -180,7 +183,8 @@ def setup(Tobs=2.0, dt=10.0, eps=1e-2, M=1e6, mu=10.0, e0=0.35, downsample=None,
     info["trajectory"] = trajectory
     data = (gen_fd if inject_fd else gen_td)(*injection, **kw)
     like.inject_signal(data_stream=data, noise_fn=[get_sensitivity, get_sensitivity],
-                       noise_kwargs=[{}, {}])
+                       noise_kwargs=[{}, {}], add_noise=add_noise, noise_seed=noise_seed)
+    info["noise_seed"] = like.noise_seed if like.noise_has_been_added else None
     if start_cov is None:
         cov = np.load(_COV, allow_pickle=False) / (2.4 * 6)
     else:
@@ -329,6 +333,33 @@ def systematic_bias(s, eps, approx_kwargs=None, approx_model=None, accuracy=True
     if "stencil_agreement" in finfo:
         info["stencil_agreement"] = finfo["stencil_agreement"]
     return syst_vec, bias, info
+
+
+def noise_scatter(s, eps, num_draws=1024, seed=SEED, accuracy=True, real0=0):
+    """The scatter the Fisher covariance predicts, from explicit noise draws: for num_draws
+    realisations n_r of the likelihood's noise (the generator of Likelihood.inject_signal's
+    add_noise, keyed on seed; realisations real0 ...) the linearised maximum-likelihood shifts
+    dtheta_r = cov <n_r | dh> in the six sampled coordinates. fisher_covariance's derivatives and
+    weights w = df / S go through diagnostic.noise_overlaps with gain = sqrt(4 w) (the Fisher
+    matrix is 4 sum w Re(conj dh_i dh_j)): one pass per draw block that regenerates the noise in
+    registers, no noise buffer.
+    Returns (dtheta [num_draws][6], sample_cov [6][6], agreement, info) with agreement =
+    max_ij |sample_cov - cov|_ij / sqrt(cov_ii cov_jj); info holds "fisher", "cov", "overlaps"
+    ([num_draws][6], host), "derivs" and "weights" (device) and, with accuracy,
+    "stencil_agreement". The sample covariance of <n_r | dh> itself estimates the Fisher
+    matrix, each entry with the Wishart standard error sqrt((F_ii F_jj + F_ij^2) / num_draws)."""
+    from . import diagnostic as dg
+    F, cov, finfo = fisher_covariance(s, eps, accuracy=accuracy, return_derivs=True)
+    gain = (4.0 * finfo["weights"]).sqrt().contiguous()
+    over = dg.noise_overlaps(finfo["derivs"], gain, seed, num_draws, real0=real0).cpu().numpy()
+    dtheta = over @ cov.T
+    sample_cov = np.cov(dtheta, rowvar=False) if num_draws > 1 else np.full((6, 6), np.nan)
+    sd = np.sqrt(np.diag(cov))
+    info = {"fisher": F, "cov": cov, "overlaps": over, "derivs": finfo["derivs"],
+            "weights": finfo["weights"]}
+    if "stencil_agreement" in finfo:
+        info["stencil_agreement"] = finfo["stencil_agreement"]
+    return dtheta, sample_cov, float(np.max(np.abs(sample_cov - cov) / np.outer(sd, sd))), info
 
 
 class MemoizedUpstream:

@@ -1,5 +1,6 @@
 """Device reductions of the likelihood side: thin wrappers of efd_loglike / efd_inner_product /
-efd_fisher_gram / efd_overlap_rows / efd_pair_stats / efd_td_split_pair_stats.
+efd_fisher_gram / efd_overlap_rows / efd_pair_stats / efd_td_split_pair_stats, and of the noise
+realisations' efd_noise_fd / efd_noise_overlap_rows.
 
 All run in libemrifd.so (HIP, gfx950) as fixed-partition two-pass reductions, so results are
 bitwise reproducible. They read the channels in place: h, d complex128 [nchan][nbin], w float64
@@ -302,6 +303,52 @@ class Reducer:
                        "efd_dh_hh_rows", self.lib)
         return out
 
+    def noise_fd(self, out, seed, realization=0, bin0=0, gain=None, accumulate=False):
+        """out[c][i] = gain[c][i] * 0.5 * xi(c, bin0 + i) (efd_noise_fd; with accumulate added
+        to out): the counter-based draws of include/emrifd.h's "Noise realisations", a function
+        of (seed, realization, channel, bin) alone. out: complex128 [nchan][nbin] on this
+        device; gain: float64 [nchan][nbin] or None (= 1), a gain of 0 or NaN leaves the bin
+        without noise. Returns out."""
+        torch = self.torch
+        if out.dim() != 2:
+            raise ValueError(f"out: expected complex128 [nchan][nbin], got {tuple(out.shape)}")
+        nchan, nbin = int(out.shape[0]), int(out.shape[1])
+        po = self._check(out, "out", torch.complex128, (nchan, nbin))
+        pg = None if gain is None else self._check(gain, "gain", torch.float64, (nchan, nbin))
+        seed, realization, bin0 = _noise_key(seed, realization, bin0)
+        _lib.check(self.lib.efd_noise_fd(po, pg, nchan, nbin, bin0, seed, realization,
+                                         int(bool(accumulate)), self._stream()),
+                   "efd_noise_fd", self.lib)
+        return out
+
+    def noise_overlap_rows(self, rows, gain, seed, num_draws, real0=0, out=None):
+        """out[r][p] = sum_c sum_k gain[c][k] Re(conj xi_{real0 + r}(c, k) rows[p][c][k]) for
+        num_draws draws (efd_noise_overlap_rows: the noise is regenerated in registers, never
+        written) as a float64 [num_draws][nrow] device tensor. rows: complex128
+        [nrow][nchan][nbin] contiguous, nrow <= EFD_NOISE_MAX_ROWS; gain: float64 [nchan][nbin]
+        or None (= 1). With gain = sqrt(4 df / S) an entry is <n_r | rows_p>. An entry does not
+        depend on the other rows or draws, or on how the draws are split over calls."""
+        torch = self.torch
+        if rows.dim() != 3 or not 1 <= rows.shape[0] <= _lib.EFD_NOISE_MAX_ROWS:
+            raise ValueError(f"rows: expected complex128 [1..{_lib.EFD_NOISE_MAX_ROWS}][nchan]"
+                             f"[nbin], got {tuple(rows.shape)}")
+        nrow, nchan, nbin = (int(v) for v in rows.shape)
+        pr = self._check(rows, "rows", torch.complex128, (nrow, nchan, nbin))
+        pg = None if gain is None else self._check(gain, "gain", torch.float64, (nchan, nbin))
+        num_draws = int(num_draws)
+        seed, real0, _ = _noise_key(seed, real0, 0)
+        if num_draws < 0 or real0 + num_draws > 2 ** 32:
+            raise ValueError("noise_overlap_rows: real0 + num_draws outside 0..2^32")
+        if out is None:
+            out = torch.empty((num_draws, nrow), dtype=torch.float64, device=self.device)
+        po = self._check(out, "out", torch.float64, (num_draws, nrow))
+        scr = self._scratch("_scr_nz", _lib.EFD_NOISE_SCRATCH)
+        _lib.check(self.lib.efd_noise_overlap_rows(pr, nrow, pg, nchan, nbin, seed, real0,
+                                                   num_draws, po, scr.data_ptr(),
+                                                   self._stream()),
+                   "efd_noise_overlap_rows", self.lib)
+        return out
+
     def window_rows(self, h, windows, out):
         """out[j] = windows[j] * h for every window of one series (efd_window_rows): h
         complex128 [n]; windows: float64 [n] tensors, or None for the unwindowed copy; out:
@@ -321,3 +368,16 @@ class Reducer:
         _lib.check(self.lib.efd_window_rows(ph, n, ptrs, nwin, pout, stride, self._stream()),
                    "efd_window_rows", self.lib)
         return out
+
+
+def _noise_key(seed, realization, bin0):
+    """(seed, realization, bin0) as the integers the C ABI takes: a 64-bit seed, a 32-bit
+    realisation, a 64-bit first bin."""
+    seed, realization, bin0 = int(seed), int(realization), int(bin0)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed: an integer in 0..2^64 - 1")
+    if not 0 <= realization < 2 ** 32:
+        raise ValueError("realization: an integer in 0..2^32 - 1")
+    if not 0 <= bin0 < 2 ** 64:
+        raise ValueError("bin0: an integer in 0..2^64 - 1")
+    return seed, realization, bin0

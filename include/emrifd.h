@@ -900,6 +900,56 @@ int efd_traj_p_at_t_batch(const efd_traj_source* src /* p0 ignored, T = t_out in
                           int32_t count, double xtol, double rtol_root,
                           double* p0 /* device [count] */, int32_t* status, void* stream);
 
+/*
+ * Noise realisations (not part of the reference's interface, which stubbed them:
+ * lisatools/sampling/likelihood.py:183-199, utils/utility.py:5-13; csrc/emrifd_noise.hip and the
+ * shared arithmetic csrc/emrifd_noise.h). One unit complex normal xi(c, k) per (seed,
+ * realisation, channel c, bin k), a function of those four alone:
+ *   Philox4x32-10 (Salmon et al. 2011) with counter (k & 0xffffffff, k >> 32, c, realisation)
+ *   and key (seed & 0xffffffff, seed >> 32) gives the words w0..w3;
+ *   a = (w0 << 21) | (w1 >> 11), b = (w2 << 21) | (w3 >> 11); u1 = (a + 1) 2^-53, u2 = b 2^-53;
+ *   xi = sqrt(-2 ln u1) (cos 2 pi u2 + i sin 2 pi u2), so E |xi|^2 = 2.
+ * lisatools' noise on a bin of spacing df and PSD S is sqrt(S) (0.5 / sqrt(df)) xi; in the
+ * likelihood's weighted space (x sqrt(df / S)) that is 0.5 xi on every bin.
+ *
+ * efd_noise_fd: out[c][i] = gain[c][i] * 0.5 * xi(c, bin0 + i) for c < nchan, i < nbin (with
+ *   accumulate != 0 added to out instead). out complex [nchan][nbin]; gain [nchan][nbin] or NULL
+ *   (= 1). A gain of 0 or NaN gives exactly 0 (leaves out untouched under accumulate); the bin
+ *   still counts, so slices of a grid (bin0) are bitwise the whole grid's. nbin = 0 does nothing
+ *   and returns 0. One launch, asynchronous, no scratch.
+ *
+ * efd_noise_overlap_rows: out[r - real0][p] = sum_c sum_k gain[c][k] Re(conj xi_r(c, k)
+ *   rows[p][c][k]) for the draws r in [real0, real0 + ndraw) and the rows p < nrow; the noise is
+ *   regenerated in registers and never written. rows complex [nrow][nchan][nbin] contiguous; gain
+ *   [nchan][nbin] or NULL (= 1), a gain of 0 or NaN contributes nothing; out [ndraw][nrow];
+ *   scratch EFD_NOISE_SCRATCH doubles. With gain = sqrt(4 df / S) this is <n_r | rows_p> of the
+ *   noise n_r = sqrt(S) (0.5 / sqrt(df)) xi_r, whose covariance over r is the rows' Fisher (Gram)
+ *   matrix. Limits: 1 <= nrow <= EFD_NOISE_MAX_ROWS, 1 <= nbin <= 2^40, real0 + ndraw <= 2^32
+ *   (EFD_ERR_ARG beyond); any ndraw: the call runs EFD_NOISE_DRAWS_PER_LAUNCH draws per launch.
+ *   Fixed-partition two-pass reduction without atomics: an entry depends on (seed, r, row p,
+ *   gain, nchan, nbin) only, not on the other rows, the other draws or how ndraw is split over
+ *   calls. ndraw = 0 does nothing.
+ *
+ * The _cpu twins take host pointers (scratch and stream unused) and share the integer stage and
+ * the order of the floating-point steps; efd_noise_philox_cpu returns the four words of one
+ * Philox4x32-10 call (counter[4], key[2]) for known-answer tests.
+ */
+#define EFD_NOISE_MAX_ROWS 16
+#define EFD_NOISE_DRAWS_PER_LAUNCH 256
+#define EFD_NOISE_SCRATCH 1048576   /* 256 workgroups x 256 draws x 16 rows */
+
+int efd_noise_fd(double* out, const double* gain, int32_t nchan, int64_t nbin, uint64_t bin0,
+                 uint64_t seed, uint32_t realisation, int32_t accumulate, void* stream);
+int efd_noise_overlap_rows(const double* rows, int32_t nrow, const double* gain, int32_t nchan,
+                           int64_t nbin, uint64_t seed, uint32_t real0, int64_t ndraw, double* out,
+                           double* scratch, void* stream);
+int efd_noise_fd_cpu(double* out, const double* gain, int32_t nchan, int64_t nbin, uint64_t bin0,
+                     uint64_t seed, uint32_t realisation, int32_t accumulate, void* stream);
+int efd_noise_overlap_rows_cpu(const double* rows, int32_t nrow, const double* gain,
+                               int32_t nchan, int64_t nbin, uint64_t seed, uint32_t real0,
+                               int64_t ndraw, double* out, double* scratch, void* stream);
+int efd_noise_philox_cpu(const uint32_t* counter, const uint32_t* key, uint32_t* words);
+
 #ifdef __cplusplus
 }
 #endif
