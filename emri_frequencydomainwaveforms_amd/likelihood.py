@@ -13,39 +13,66 @@ noise_fn = FDutils.get_sensitivity, f_arr = frequency[frequency >= 0]):
                            channels and bins, skipping bin 0 when w[0][0] is NaN (:268)
   __call__ (:295-334)      parameter transform, transpose_params, `subset` batching
 
-What changes is where the work happens. Data and noise factor live on the device. On
-symmetric grids (FEW's own and the drivers' downsampled f_arr) the walkers' mode sums run a few
-at a time in one launch with the likelihood fused into the sum's epilogue
-(efd_modesum_sum_loglike): the templates are never written, each walker's logL lands in its slot
-of a device result vector, and the batch costs one host synchronisation. Otherwise (or with
-fused_likelihood = False) each walker's template is reduced by efd_loglike (HIP) straight from
-the template buffer, and the 2 x N_pos residual d - h w is never materialised. When the template is this package's
-get_fd_waveform_fromFD around a GenerateEMRIWaveform (the drivers' case), h+ and hx are written
-by efd_polarizations directly into one reusable [2][N_pos] buffer (the stream orders reuse), and
-non_zero_mask is folded into the template weight (w * mask) instead of zeroing h.
-The reference's other template mode, get_fd_waveform_fromTD around the TD GenerateEMRIWaveform
-(emri_pe.py -template td), takes the same batched branch: groups of WINDOW_GROUP walkers, each
-walker's windowed series h+ - i hx written by efd_td_modesum_windowed into one row of a shared
-buffer, one batched complex transform, and efd_td_split_loglike reducing both channels' logL
-straight from it (any window; non_zero_mask folded into w as above).
-Results are numpy float64 arrays ([B]), or device tensors with use_gpu=True, return_cupy=True.
-Likelihood.parts returns the pair the logL is made of instead, <d|h> (complex) and <h|h> per
-walker with logL = -1/2 (d_d - 2 Re <d|h> + <h|h>): on the fused branches from the mode sum's
-epilogue (efd_modesum_sum_dh_hh, no template written), elsewhere from the templates that branch
-writes (efd_dh_hh_rows). separate_d_h=True (lisatools' flag) makes get_ll return that pair, and
-ProfiledLikelihood turns it into the amplitude-maximised or distance-marginalised logL.
-Likelihoods over time-domain DATA (dt only, no df or f_arr) are not part of this path: get_ll
-raises NotImplementedError.
+What changes is where the work happens. Data and noise factor live on the device, and the
+2 x N_pos residual d - h w is never materialised. Results are numpy float64 arrays ([B]), or
+device tensors with use_gpu=True, return_cupy=True. Likelihood.parts returns the pair the logL
+is made of instead, <d|h> (complex) and <h|h> per walker with logL = -1/2 (d_d - 2 Re <d|h> +
+<h|h>); separate_d_h=True (lisatools' flag) makes get_ll return that pair, and
+ProfiledLikelihood (profiled.py, re-exported here) turns it into the amplitude-maximised or
+distance-marginalised logL. Likelihoods over time-domain DATA (dt only, no df or f_arr) are not
+part of this path: get_ll raises NotImplementedError.
+
+Routing. get_ll and parts hand Likelihood._run an output kind (LOGL or PAIR, below the class),
+and _run takes the branch choose_branch names from the template model's flags:
+  pipelined     get_fd_waveform_fromFD around a GenerateEMRIWaveform (the drivers' case). On
+                symmetric grids (FEW's own and the drivers' downsampled f_arr) the walkers' mode
+                sums run a group at a time in one launch with the reduction in the sum's
+                epilogue (efd_modesum_sum_loglike, efd_modesum_sum_dh_hh): no template is
+                written, and the batch costs one host synchronisation (_run_fused: _fused_route
+                picks _HostFeed or _DeviceFeed, _fused_preparer holds the BatchPreparer,
+                _fused_drive runs the groups, joins their streams and copies out). Otherwise, or
+                with fused_likelihood = False, h+ and hx are written by efd_polarizations into
+                one reusable [2][N_pos] buffer per pipeline slot and reduced from it
+                (efd_loglike, efd_dh_hh_rows).
+  window_batch  windowed templates, and get_fd_waveform_fromTD around the TD GenerateEMRIWaveform
+                (emri_pe.py -template td): groups of WINDOW_GROUP walkers, their series in the
+                rows of one buffer (TD: h+ - i hx by efd_td_modesum_windowed), one batched
+                transform, and the logL reduced straight from it (efd_hann_loglike,
+                efd_td_split_loglike), or the rows written (fill_batch) for efd_dh_hh_rows.
+  fill, call, vectorized   one template at a time into a buffer, or as the model returns it.
+Where the model fills a buffer, non_zero_mask is folded into the template weight (w * mask)
+instead of zeroing h.
 """
 
 import ctypes
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _lib
-from .summation import require_gpu
+from .noise import check_seed, new_seed
+from .profiled import (DISTANCE_NODES, ProfiledLikelihood, marginalize_distance,  # noqa: F401
+                       profile_amplitude, profile_none)
+from .reductions import Reducer
+from .summation import BatchPreparer, WaveformPipeline, loglike_tile_constants, require_gpu
+
+
+def choose_branch(tm, vectorized, has_args):
+    """The branch Likelihood._run takes, from the template model's flags alone (the output kind
+    plays no part, no GPU state is touched). vectorized: the likelihood's flag; has_args: whether
+    positional waveform arguments were passed (the windowed batch takes keyword ones only, the
+    per-walker fill forwards them). "pipelined" is the fused groups or the per-slot pipeline."""
+    if vectorized:
+        return "vectorized"
+    if getattr(tm, "can_pipeline", False):
+        return "pipelined"
+    if getattr(tm, "can_fill_batch", False) and not has_args:
+        return "window_batch"
+    if getattr(tm, "can_fill", False):
+        return "fill"
+    return "call"
 
 
 class Likelihood:
@@ -71,9 +98,9 @@ class Likelihood:
         self.noise_seed = None   # the seed of inject_signal(add_noise=True)'s realisation
         self.torch = torch = require_gpu()
         self.device = torch.device("cuda", torch.cuda.current_device())
-        from .reductions import Reducer
         self._red = Reducer(self.device)
         self._buf = None
+        self.branch_taken = None   # the branch of the last get_ll / parts (see _run)
         # walkers whose templates are in flight at once in get_ll (WaveformPipeline slots);
         # one HIP stream each (the box exposes 4 hardware queues per process)
         self.num_streams = 4
@@ -146,33 +173,16 @@ class Likelihood:
             raise ValueError("Number of channels from template_model does not match number of "
                              "channels declare by user.")
 
-        if isinstance(noise_fn, list):
-            if len(noise_fn) != 1 and len(noise_fn) != self.num_channels:
-                raise ValueError("Number of noise functions does not match number of channels "
-                                 "declared by user.")
-            elif len(noise_fn) == 1:
-                noise_fn = [noise_fn[0] for _ in range(self.num_channels)]
-        else:
-            noise_fn = [noise_fn for _ in range(self.num_channels)]
-        if isinstance(noise_kwargs, list):
-            if len(noise_kwargs) != 1 and len(noise_kwargs) != self.num_channels:
-                raise ValueError("Number of noise kwargs does not match number of channels "
-                                 "declared by user.")
-            elif len(noise_kwargs) == 1:
-                noise_kwargs = [noise_kwargs[0] for _ in range(self.num_channels)]
-        else:
-            noise_kwargs = [noise_kwargs for _ in range(self.num_channels)]
+        noise_fn = _per_channel(noise_fn, self.num_channels, "noise functions")
+        noise_kwargs = _per_channel(noise_kwargs, self.num_channels, "noise kwargs")
 
-        if self.frequency_domain:
-            if self.df is not None:
-                freqs = np.arange(self.injection_length) * self.df
-                can_add_noise = True
-            else:
-                freqs = _to_numpy(self.f_arr)
-                can_add_noise = True   # (False in the reference; df is diff_freqs here)
+        if self.df is not None:
+            freqs = np.arange(self.injection_length) * self.df
+        elif self.frequency_domain:
+            # (the reference sets can_add_noise = False here; df is diff_freqs on this grid)
+            freqs = _to_numpy(self.f_arr)
         else:
             freqs = np.fft.rfftfreq(self.injection_length, self.dt)
-            can_add_noise = True
         psd = [np.asarray(_to_numpy(fn(freqs, **kw)), dtype=np.float64)
                for fn, kw in zip(noise_fn, noise_kwargs)]
         if self.frequency_domain is False:
@@ -182,7 +192,7 @@ class Likelihood:
         diff_freqs[1:] = np.diff(freqs)
         diff_freqs[0] = diff_freqs[1]
         self.base_injections = injection_channels
-        new_noise = bool(add_noise and can_add_noise and self.noise_has_been_added is False)
+        new_noise = bool(add_noise and self.noise_has_been_added is False)
         if new_noise:
             if noise_seed is None:
                 dist = getattr(torch, "distributed", None)
@@ -191,11 +201,8 @@ class Likelihood:
                     raise ValueError("inject_signal(add_noise=True) needs noise_seed when "
                                      "torch.distributed has more than one rank: the replicas' "
                                      "noise would differ")
-                from .noise import new_seed
                 noise_seed = new_seed()
-            noise_seed = int(noise_seed)
-            if not 0 <= noise_seed < 2 ** 64:
-                raise ValueError("noise_seed: an integer in 0..2^64 - 1")
+            noise_seed = check_seed(noise_seed)
 
         with np.errstate(invalid="ignore", divide="ignore"):
             nf = np.asarray([(diff_freqs / p) ** 0.5 for p in psd])
@@ -233,11 +240,17 @@ class Likelihood:
         live = torch.isfinite(w) & (w != 0.0)
         if bool(torch.isnan(w[0, 0]).item()):
             live[:, 0] = False
-        tm = self.template_model
-        mask = getattr(tm, "non_zero_mask", None)
-        if mask is not None and getattr(tm, "can_fill", False):
+        mask = self._template_mask()
+        if mask is not None:
             live &= mask.to(device=self.device, dtype=torch.bool)[None, :]
         return live.to(torch.float64).contiguous()
+
+    def _template_mask(self):
+        """The template model's non_zero_mask where it is folded into the template weight and
+        its bins dropped from the likelihood (models that fill a buffer), or None."""
+        tm = self.template_model
+        mask = getattr(tm, "non_zero_mask", None)
+        return mask if getattr(tm, "can_fill", False) else None
 
     @property
     def noise_to_add(self):
@@ -274,9 +287,8 @@ class Likelihood:
         self._tile_const = None   # (their tile constants are made again on the next call)
         self._d_d = None          # (<d|d> too)
         self._hloc = None         # the windowed logL's per-bin data (made on the next call)
-        tm = self.template_model
-        mask = getattr(tm, "non_zero_mask", None)
-        if mask is not None and getattr(tm, "can_fill", False):
+        mask = self._template_mask()
+        if mask is not None:
             self._w_templ = (w * mask.to(torch.float64)[None, :]).contiguous()
 
     # ---------------------------------------------------------------------------------------
@@ -295,138 +307,106 @@ class Likelihood:
         fused ones take both numbers from the mode sum's epilogue (BatchPreparer.sum_dh_hh),
         the others reduce the templates they write anyway (Reducer.dh_hh_rows; the windowed and
         TD templates through fill_batch, a group of WINDOW_GROUP walkers per reduction)."""
-        torch = self.torch
-        if self.frequency_domain is False:
-            raise NotImplementedError("a dt-only (time-domain data) likelihood is not part of "
-                                      "the FD path")
-        num_likes = params.shape[0]
-        out = torch.empty((num_likes, 3), dtype=torch.float64, device=self.device)
-        nch, nb = self._d.shape
-        tm = self.template_model
-        host = None
-        if self.vectorized:
-            h_all = tm(*params, *args, **kwargs)
-            for i in range(num_likes):
-                self._red.dh_hh_rows(self._as_channels(h_all[i]), self._d, self._w,
-                                     out=out[i:i + 1])
-        elif (getattr(tm, "can_pipeline", False)
-              and (host := self._get_ll_fused(tm, params, args, kwargs, out, dh=True))
-              is not None):
-            pass
-        elif getattr(tm, "can_pipeline", False):
-            P = self._pipeline_for(tm)
-            P.order_after_current()
-            _prefetch(tm, params, args, kwargs)
-            for i, params_i in enumerate(params):
-                j = P.next_slot()
-                slot = tm.submit(P, self._pbufs[j], *params_i, *args, order=False, **kwargs)
-                with torch.cuda.stream(P.stream(slot)):
-                    self._preds[slot].dh_hh_rows(self._pbufs[slot], self._d, self._w_templ,
-                                                 out=out[i:i + 1])
-            P.wait()
-        elif getattr(tm, "can_fill_batch", False) and not args:
-            G = min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
-                        or int(getattr(tm, "WINDOW_GROUP", 8))), _lib.EFD_DH_MAX_ROWS)
-            rows = getattr(self, "_dh_rows", None)
-            if rows is None or tuple(rows.shape) != (G, nch, nb):
-                rows = self._dh_rows = torch.empty((G, nch, nb), dtype=torch.complex128,
-                                                   device=self.device)
-            _prefetch(tm, params, args, kwargs, concurrency=G if G < num_likes else None)
-            for g0 in range(0, num_likes, G):
-                m = len(params[g0:g0 + G])
-                tm.fill_batch(rows[:m], params[g0:g0 + m], **kwargs)
-                self._red.dh_hh_rows(rows[:m], self._d, self._w_templ, out=out[g0:g0 + m])
-        elif getattr(tm, "can_fill", False):
-            if self._buf is None or tuple(self._buf.shape) != (nch, nb):
-                self._buf = torch.empty((nch, nb), dtype=torch.complex128, device=self.device)
-            _prefetch(tm, params, args, kwargs)
-            for i, params_i in enumerate(params):
-                tm.fill(self._buf, *params_i, *args, **kwargs)
-                self._red.dh_hh_rows(self._buf, self._d, self._w_templ, out=out[i:i + 1])
-        else:
-            for i, params_i in enumerate(params):
-                h = self._as_channels(tm(*params_i, *args, **kwargs))
-                self._red.dh_hh_rows(h, self._d, self._w, out=out[i:i + 1])
-        if self.use_gpu and self.return_cupy:
-            return torch.complex(out[:, 0], out[:, 1]), out[:, 2].clone()
-        if host is None:
-            host = out.cpu().numpy()
-        return host[:, 0] + 1j * host[:, 1], host[:, 2].copy()
+        return self._run(PAIR, params, args, kwargs)
 
     def get_ll(self, params, *args, **kwargs):
-        torch = self.torch
-        if self.separate_d_h:
-            return self.parts(params, *args, **kwargs)
+        return self._run(PAIR if self.separate_d_h else LOGL, params, args, kwargs)
+
+    def _run(self, kind, params, args, kwargs):
+        """The branch ladder, walked once for either output kind: the _branch_* method that
+        choose_branch names fills `out`, one slot per walker, and returns the host copy if it
+        already has one (the fused groups' pinned download). branch_taken names the branch that
+        ran ("pipelined" resolved to "fused" or "per_slot")."""
         if self.frequency_domain is False:
             raise NotImplementedError("a dt-only (time-domain data) likelihood is not part of "
                                       "the FD path")
-        num_likes = params.shape[0]
-        out = torch.empty(num_likes, dtype=torch.float64, device=self.device)
-        nch, nb = self._d.shape
         tm = self.template_model
-        if self.vectorized:
-            h_all = tm(*params, *args, **kwargs)
-            for i in range(num_likes):
-                h = self._as_channels(h_all[i])
-                self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
-        elif (getattr(tm, "can_pipeline", False)
-              and (host := self._get_ll_fused(tm, params, args, kwargs, out)) is not None):
-            if self.use_gpu and self.return_cupy:
-                return out
-            return host
-        elif getattr(tm, "can_pipeline", False):
-            # several walkers in flight: each pipeline slot has its own template buffer,
-            # stream and reduction scratch; walker i's template and logL run on one slot's
-            # stream, the batch costs one host synchronisation
-            P = self._pipeline_for(tm)
-            P.order_after_current()
-            _prefetch(tm, params, args, kwargs)
-            for i, params_i in enumerate(params):
-                j = P.next_slot()
-                slot = tm.submit(P, self._pbufs[j], *params_i, *args, order=False, **kwargs)
-                with torch.cuda.stream(P.stream(slot)):
-                    self._preds[slot].loglike(self._pbufs[slot], self._d, self._w_templ,
-                                              out=out[i:i + 1])
-            P.wait()
-        elif getattr(tm, "can_fill_batch", False) and not args:
-            # windowed templates (the drivers' Hann window, or another of scipy's cosine-sum
-            # windows: fdutils.COSINE_WINDOWS): groups of WINDOW_GROUP walkers,
-            # their spectra in one buffer and the window's transforms batched over them
-            # and the windowed templates' logL reduced in place (efd_hann_loglike or
-            # efd_cosw_loglike, at most EFD_HANN_ROWS_MAX rows a call). TD templates
-            # (get_fd_waveform_fromTD) group the same way: one transform per walker and
-            # efd_td_split_loglike. The batch takes keyword waveform arguments only;
-            # extra positional ones go to the per-walker fill below, which forwards them
-            G = min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
-                        or int(getattr(tm, "WINDOW_GROUP", 8))), _lib.EFD_HANN_ROWS_MAX)
-            scr = getattr(self, "_wscratch", None)
-            per_row = max(_lib.EFD_LOGLIKE_SCRATCH, _lib.EFD_HANN_LOCAL_PARTIALS,
-                          _lib.EFD_TD_SPLIT_SCRATCH)
-            if scr is None or scr.numel() < G * per_row:
-                scr = self._wscratch = torch.empty(G * per_row, dtype=torch.float64,
-                                                   device=self.device)
-            local = self._hann_local(tm, kwargs)
-            # the upstream G walkers at a time, in order: the first group's device work then
-            # overlaps the later walkers' upstream
-            _prefetch(tm, params, args, kwargs, concurrency=G if G < num_likes else None)
-            for g0 in range(0, num_likes, G):
-                rows = params[g0:g0 + G]
-                tm.loglike_batch(out[g0:g0 + len(rows)], rows, self._d, self._w_templ, scr,
-                                 *args, local=local, **kwargs)
-        elif getattr(tm, "can_fill", False):
-            if self._buf is None or tuple(self._buf.shape) != (nch, nb):
-                self._buf = torch.empty((nch, nb), dtype=torch.complex128, device=self.device)
-            _prefetch(tm, params, args, kwargs)
-            for i, params_i in enumerate(params):
-                tm.fill(self._buf, *params_i, *args, **kwargs)
-                self._red.loglike(self._buf, self._d, self._w_templ, out=out[i:i + 1])
-        else:
-            for i, params_i in enumerate(params):
-                h = self._as_channels(tm(*params_i, *args, **kwargs))
-                self._red.loglike(h, self._d, self._w, out=out[i:i + 1])
+        out = self.torch.empty((params.shape[0], *kind.tail), dtype=self.torch.float64,
+                               device=self.device)
+        self.branch_taken = name = choose_branch(tm, self.vectorized, bool(args))
+        host = getattr(self, "_branch_" + name)(kind, tm, params, args, kwargs, out)
         if self.use_gpu and self.return_cupy:
-            return out
-        return out.cpu().numpy()
+            return kind.device(self, out)
+        return kind.host(out.cpu().numpy() if host is None else host)
+
+    def _branch_vectorized(self, kind, tm, params, args, kwargs, out):
+        h_all = tm(*params, *args, **kwargs)
+        for i in range(params.shape[0]):
+            kind.reduce(self._red, self._as_channels(h_all[i]), self._d, self._w,
+                        out=out[i:i + 1])
+
+    def _branch_pipelined(self, kind, tm, params, args, kwargs, out):
+        """The fused groups where they apply, else num_streams walkers in flight: a walker's
+        template and reduction run on its slot's stream, with the slot's buffer and scratch;
+        the batch costs one host synchronisation."""
+        host = self._run_fused(kind, tm, params, args, kwargs, out)
+        self.branch_taken = "per_slot" if host is None else "fused"
+        if host is not None:
+            return host
+        P = self._pipeline_for(tm)
+        P.order_after_current()
+        _prefetch(tm, params, args, kwargs)
+        for i, params_i in enumerate(params):
+            j = P.next_slot()
+            slot = tm.submit(P, self._pbufs[j], *params_i, *args, order=False, **kwargs)
+            with self.torch.cuda.stream(P.stream(slot)):
+                kind.reduce(self._preds[slot], self._pbufs[slot], self._d, self._w_templ,
+                            out=out[i:i + 1])
+        P.wait()
+
+    def _branch_window_batch(self, kind, tm, params, args, kwargs, out):
+        """Windowed (Hann, or another of fdutils.COSINE_WINDOWS) and TD templates: groups of G
+        walkers, the transforms batched over a group; kind.window is what becomes of one."""
+        n = params.shape[0]
+        G = _window_group(tm, kind.window_cap)
+        group = kind.window(self, tm, G, kwargs)
+        # the upstream G walkers at a time, in order: the first group's device work then
+        # overlaps the later walkers' upstream
+        _prefetch(tm, params, args, kwargs, concurrency=G if G < n else None)
+        for g0 in range(0, n, G):
+            rows = params[g0:g0 + G]
+            group(out[g0:g0 + len(rows)], rows)
+
+    def _window_loglike(self, tm, G, kwargs):
+        """LOGL's windowed action: the template model reduces the group's logL in place
+        (efd_hann_loglike, efd_cosw_loglike or efd_td_split_loglike; EFD_HANN_ROWS_MAX rows)."""
+        scr = getattr(self, "_wscratch", None)
+        per_row = max(_lib.EFD_LOGLIKE_SCRATCH, _lib.EFD_HANN_LOCAL_PARTIALS,
+                      _lib.EFD_TD_SPLIT_SCRATCH)
+        if scr is None or scr.numel() < G * per_row:
+            scr = self._wscratch = self.torch.empty(G * per_row, dtype=self.torch.float64,
+                                                    device=self.device)
+        local = self._hann_local(tm, kwargs)
+        return lambda out_g, rows: tm.loglike_batch(out_g, rows, self._d, self._w_templ, scr,
+                                                    local=local, **kwargs)
+
+    def _window_rows(self, tm, G, kwargs):
+        """PAIR's windowed action: the group's templates written as rows, then one
+        efd_dh_hh_rows over them (EFD_DH_MAX_ROWS rows)."""
+        shape = (G, *self._d.shape)
+        buf = getattr(self, "_dh_rows", None)
+        if buf is None or tuple(buf.shape) != shape:
+            buf = self._dh_rows = self.torch.empty(shape, dtype=self.torch.complex128,
+                                                   device=self.device)
+
+        def group(out_g, rows):
+            tm.fill_batch(buf[:len(rows)], rows, **kwargs)
+            self._red.dh_hh_rows(buf[:len(rows)], self._d, self._w_templ, out=out_g)
+        return group
+
+    def _branch_fill(self, kind, tm, params, args, kwargs, out):
+        shape = tuple(self._d.shape)
+        if self._buf is None or tuple(self._buf.shape) != shape:
+            self._buf = self.torch.empty(shape, dtype=self.torch.complex128, device=self.device)
+        _prefetch(tm, params, args, kwargs)
+        for i, params_i in enumerate(params):
+            tm.fill(self._buf, *params_i, *args, **kwargs)
+            kind.reduce(self._red, self._buf, self._d, self._w_templ, out=out[i:i + 1])
+
+    def _branch_call(self, kind, tm, params, args, kwargs, out):
+        for i, params_i in enumerate(params):
+            h = self._as_channels(tm(*params_i, *args, **kwargs))
+            kind.reduce(self._red, h, self._d, self._w, out=out[i:i + 1])
 
     # the windowed logL in its per-bin form, reduced inside the transforms' last pass
     # (efd_hann_loglike_local; False: efd_hann_loglike's mirror-pair form after the transforms)
@@ -435,21 +415,17 @@ class Likelihood:
     def _hann_local(self, tm, kwargs):
         """The template model's per-bin windowed-logL data for this likelihood's d, w (made once
         per injection), or None."""
-        hloc = getattr(self, "_hloc", None)
-        if hloc is None:
+        if getattr(self, "_hloc", None) is None:
             make = getattr(tm, "hann_local", None) if self.HANN_LOCAL else None
             inj = getattr(self, "_inj_call", None)
-            if make is None:
-                hloc = False
-            elif inj is not None:
-                hloc = make(self._d, self._w_templ, inj=inj[0], **inj[1]) or False
-            else:
-                hloc = make(self._d, self._w_templ, **kwargs) or False
-            self._hloc = hloc
-        return hloc or None
+            if make is not None and inj is not None:
+                kwargs = dict(inj[1], inj=inj[0])
+            self._hloc = make is not None and make(self._d, self._w_templ, **kwargs) or False
+        return self._hloc or None
 
     # walkers per fused group (EFD_FUSED_GROUP overrides it: an experiment switch): one
-    # efd_modesum_prepare_batch and one efd_modesum_sum_loglike each; FUSED_DEPTH groups rotate so group i+1's preparation runs beside group i's sum.
+    # efd_modesum_prepare_batch and one efd_modesum_sum_loglike each; FUSED_DEPTH groups rotate
+    # so group i+1's preparation runs beside group i's sum.
     # Balanced groups of at most 16 (EFD_BATCH_MAX): config 5's 64-walker half-steps (host-bound,
     # 43-tile grids) ran 54-60 k logL/s in 4 groups against 40-51 k in 8 (5 interleaved rounds);
     # config 4's 8 walkers are one group either way (groups of 4 or 3: -5 to -10%)
@@ -466,132 +442,99 @@ class Likelihood:
     # launch ahead of the first group (pe.setup(trajectory="device"); efd_traj_batch)
     device_trajectory = False
 
-    def _get_ll_fused(self, tm, params, args, kwargs, out, dh=False):
-        """The pipelined path with the likelihood fused into the mode sum: per group of
-        FUSED_GROUP walkers, the template chain collects each walker's host inputs
-        (BatchPreparer), one upload and one efd_modesum_prepare_batch prepare the group on its
-        stream, and one efd_modesum_sum_loglike right behind them on the same stream writes the
-        group's log-likelihoods into its slice of out (the templates never reach HBM; a
-        cross-stream wait between preparation and sum cost ~12 us of idle device per group on
-        config 4's chain, tools/chain_timeline.py). A group's next flush is behind its sum in
-        stream order; the streams join once, before the copy out.
+    def _run_fused(self, kind, tm, params, args, kwargs, out):
+        """The reduction fused into the mode sum: per balanced group of walkers, the feed puts
+        the group's inputs on a group stream, one efd_modesum_prepare_batch prepares it there,
+        and kind.fused_sum right behind it on the same stream writes the group's slice of out
+        (no template reaches HBM; a cross-stream wait between preparation and sum cost ~12 us of
+        idle device per group on config 4's chain, tools/chain_timeline.py). On the host route
+        LOGL's group is one native call instead (flush_loglike, efd_fused_group). Both routes'
+        groups live in one preparer: a Likelihood switched between them keeps its workspaces.
+        Returns the result on the host, [n, *kind.tail] (one synchronisation per batch), or
+        None, before queueing anything, when no route applies: the caller then takes the
+        per-walker path."""
+        Feed = self._fused_route(tm, args, kwargs)
+        if Feed is None:
+            return None
+        n = len(params)
+        if n == 0:
+            return np.empty((0, *kind.tail), dtype=np.float64)
+        ngroups = -(-n // (_lib.EFD_BATCH_MAX if Feed is _DeviceFeed else self.FUSED_GROUP))
+        G = -(-n // ngroups)                       # balanced groups of at most that many
+        F = self._fused_preparer(tm, G)
+        B = F["prep"]
+        feed = Feed(self, F, tm, params, args, kwargs)
+        self._order_group_streams(F, ngroups)
+        if (kind.native_group and Feed is _HostFeed and self.FUSED_NATIVE_GROUP
+                and hasattr(B.lib, "efd_fused_group")):
+            def step(g0, g):
+                # the tile constants are made on the group's stream (once per grid), before
+                # the sum that reads them
+                sst, freq, k0 = feed.collect(g)
+                tc = self._tile_constants(freq, k0, sst, B)
+                return B.flush_loglike(self._d, self._w_templ, out, tile_const=tc, out_off=g0)
+        else:
+            def step(g0, g):
+                gi, m, sst, freq, k0 = feed.flush(g)
+                kind.fused_sum(self, B, gi, out[g0:g0 + m], sst, freq, k0)
+                return gi
+        return self._fused_drive(F, feed, step, n, G, out, kind.width).reshape((n, *kind.tail))
 
-        With device_upstream only the feed of a group differs: the walkers' trajectories start
-        on the prefetch pool at once (device_trajectory: all of them in one launch on the
-        current stream instead); per balanced group of at most EFD_BATCH_MAX walkers the
-        generator's device_inputs_batch (packed trajectory upload, efd_modes_select_batch, the
-        read of the group's K) runs on the group's stream and BatchPreparer.flush_device
-        prepares the group from what it left on the device, so a group's device chain runs
-        beside the next group's trajectories and selection. The groups live in the host
-        route's preparer: a Likelihood switched between the routes keeps its workspaces.
-
-        Returns the log-likelihoods on the host (one synchronisation per batch), or None,
-        before queueing anything, when the template's grid is not symmetric, or neither route
-        applies (fused_likelihood off; the device route needs a GenerateEMRIWaveform, keyword
-        waveform arguments and no explicit mode list, and otherwise leaves the walkers to the
-        host route): the caller then takes the per-walker path. A walker whose preparation or
-        sum raised a device-side error comes back NaN from the kernel
-        (efd_modesum_sum_loglike), and only then are the groups' status flags read, which
-        raises.
-
-        dh (Likelihood.parts): out is [n][3] and every group's sum is BatchPreparer.sum_dh_hh
-        behind the Python steps (flush / flush_device), which needs no tile constants; the
-        host result is [n][3]."""
-        torch = self.torch
-        from .summation import BatchPreparer
+    def _fused_route(self, tm, args, kwargs):
+        """What feeds the fused groups: _DeviceFeed with device_upstream (it needs a
+        GenerateEMRIWaveform, keyword waveform arguments and no explicit mode list, and
+        otherwise leaves the walkers to the host route), _HostFeed with fused_likelihood, or
+        None when neither applies or the template's grid is not symmetric. Queues nothing."""
         from .waveform import GenerateEMRIWaveform
-        few = getattr(tm, "waveform_generator", None)
-        device = (self.device_upstream and not args and isinstance(few, GenerateEMRIWaveform)
+        device = (self.device_upstream and not args
+                  and isinstance(getattr(tm, "waveform_generator", None), GenerateEMRIWaveform)
                   and kwargs.get("mode_selection") is None)
         if not (device or self.fused_likelihood) or not self._fused_grid_ok(tm, kwargs):
             return None
-        if device:
-            cw = few.waveform_generator.create_waveform
-            freq, _ = cw._grid(kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("f_arr"))
-            k0 = cw.positive_start()
-            if getattr(tm, "_suffix_k0", k0) != k0:
-                raise ValueError("positive_frequency_mask does not match the generator's grid")
-        else:
-            _prefetch(tm, params, args, kwargs)
-        n = len(params)
-        per = 3 if dh else 1     # doubles per walker in out
-        if n == 0:
-            return np.empty((0, 3) if dh else 0, dtype=np.float64)
-        ngroups = -(-n // (_lib.EFD_BATCH_MAX if device else self.FUSED_GROUP))
-        G = -(-n // ngroups)                       # balanced groups of at most that many
-        caustic = getattr(getattr(getattr(tm.waveform_generator, "waveform_generator", None),
-                                  "create_waveform", None), "caustic", "uniform")
+        return _DeviceFeed if device else _HostFeed
+
+    def _fused_preparer(self, tm, G):
+        """self._fused: the groups' BatchPreparer ("prep", made again when the caustic
+        treatment changes or a group outgrows it) and what is cached beside it: the group
+        streams' handles ("gst"; efd_stream_order takes them: one event record and one stream
+        wait each, in C), arrays of them per ordering, the pinned result ("pin") and the device
+        trajectories' state ("traj")."""
+        caustic = _caustic(tm)
         F = self._fused
         if F is None or F["prep"].caustic != caustic or F["prep"].group < G:
             B = BatchPreparer(max(G, self.FUSED_GROUP), self.FUSED_DEPTH, caustic=caustic,
                               device=self.device)
-            # the group streams' handles, for the orderings below (efd_stream_order: one event
-            # record and one stream wait each, in C)
             F = self._fused = dict(prep=B, gst=[B.stream(gi).cuda_stream
                                                 for gi in range(len(B.groups))])
+        return F
+
+    def _order_group_streams(self, F, ngroups):
+        """The group streams this batch's flushes take (the preparer's rotation from its next
+        group) wait for the work queued so far on the current stream: one stream wait each."""
         B, gst = F["prep"], F["gst"]
-        lib = B.lib
-        # the device route's trajectories: on the prefetch pool, or all of them in one launch on
-        # the current stream, which the groups' streams are ordered after below
-        futs, trajs = [], None
-        if device:
-            B.restart()
-            calls, scales = few.device_calls(params, kwargs.get("T", 1.0),
-                                             kwargs.get("eps", 1e-5))
-            if self.device_trajectory:
-                trajs = few.device_trajectories(calls, self.device, F.setdefault("traj", {}))
-            else:
-                futs = few.waveform_generator.trajectories_async(calls)
-        # the group streams this batch's flushes take (B's rotation from its next group), after
-        # the work queued so far on the current stream: one stream wait each
         key = ("ord", gst.index(B.next_flush()[0].cuda_stream), min(ngroups, len(gst)))
         arr = F.get(key)
         if arr is None:
             arr = F[key] = (ctypes.c_void_p * key[2])(
                 *[gst[(key[1] + k) % len(gst)] for k in range(key[2])])
-        _lib.check(lib.efd_stream_order(torch.cuda.current_stream(self.device).cuda_stream,
-                                        arr, len(arr)), "efd_stream_order", lib)
+        _lib.check(B.lib.efd_stream_order(
+            self.torch.cuda.current_stream(self.device).cuda_stream, arr, len(arr)),
+            "efd_stream_order", B.lib)
+
+    def _fused_drive(self, F, feed, step, n, G, out, per):
+        """step(g0, slice) for every group of G walkers (it returns the preparer's group), the
+        join of the used group streams into the last one, which copies `out` (per doubles a
+        walker) to the pinned buffer, and the wait for it. Returns the host copy; a failed
+        walker comes back NaN from the kernel, and only then are the groups' flags read."""
+        B, gst, lib = F["prep"], F["gst"], F["prep"].lib
         pin = F.get("pin")
         if pin is None or pin.numel() < per * n:
-            pin = F["pin"] = torch.empty(max(per * n, 64), dtype=torch.float64, pin_memory=True)
-        native = self.FUSED_NATIVE_GROUP and hasattr(lib, "efd_fused_group") and not dh
+            pin = F["pin"] = self.torch.empty(max(per * n, 64), dtype=self.torch.float64,
+                                              pin_memory=True)
         used = []
         try:
-            batch = getattr(tm, "submit_batch", None)
             for g0 in range(0, n, G):
-                g = slice(g0, g0 + G)
-                if device:
-                    sst = B.next_flush()[0]
-                    inps = few.waveform_generator.device_inputs_batch(
-                        calls[g], include_minus_m=bool(kwargs.get("include_minus_m", True)),
-                        device=self.device, stream=sst, state=B.next_select(),
-                        futures=futs[g] if trajs is None else None,
-                        trajs=trajs[g] if trajs is not None else None)
-                    gi, jobs = B.flush_device(inps, freq, scales[g], k0)
-                else:
-                    if batch is not None:
-                        batch(B, params[g], *args, **kwargs)
-                    else:
-                        for i in range(g0, min(n, g0 + G)):
-                            tm.submit(B, None, *params[i], *args, order=False,
-                                      prepare_only=True, **kwargs)
-                    sst, freq, k0 = B.next_flush()
-                    if native:
-                        # the tile constants are made on the group's stream (once per grid),
-                        # before the sum that reads them
-                        tc = self._tile_constants(freq, k0, sst, B)
-                        used.append(B.flush_loglike(self._d, self._w_templ, out, tile_const=tc,
-                                                    out_off=g0))
-                        continue
-                    gi, jobs = B.flush()
-                used.append(gi)
-                if dh:
-                    B.sum_dh_hh(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
-                                sst.cuda_stream)
-                    continue
-                tc = self._tile_constants(freq, k0, sst, B)
-                B.sum_loglike(gi, self._d, self._w_templ, out[g0:g0 + len(jobs)],
-                              sst.cuda_stream, tile_const=tc)
+                used.append(step(g0, slice(g0, g0 + G)))
             # the other groups' streams join the last one, which copies out
             last = used[-1]
             for gj in sorted(set(used) - {last}):
@@ -600,7 +543,7 @@ class Likelihood:
             _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * per * n, gst[last]),
                        "efd_download", lib)
         finally:
-            for f in futs:
+            for f in feed.futs:
                 f.cancel()
             B.drop_pending()
             # `out` belongs to the current stream: nothing may still write it when it is
@@ -614,11 +557,18 @@ class Likelihood:
             elif used:
                 B.stream(used[-1]).synchronize()
         host = pin[:per * n].numpy().copy()
-        if dh:
-            host = host.reshape(n, 3)
         if np.isnan(host).any():
             B.wait()   # device-side errors of the groups' workspaces (sticky across reuse)
         return host
+
+    def _sum_loglike(self, B, gi, out_g, sst, freq, k0):
+        """LOGL's sum behind a flushed group, on its stream (efd_modesum_sum_loglike)."""
+        tc = self._tile_constants(freq, k0, sst, B)
+        B.sum_loglike(gi, self._d, self._w_templ, out_g, sst.cuda_stream, tile_const=tc)
+
+    def _sum_dh_hh(self, B, gi, out_g, sst, freq, k0):
+        """PAIR's (efd_modesum_sum_dh_hh: no tile constants)."""
+        B.sum_dh_hh(gi, self._d, self._w_templ, out_g, sst.cuda_stream)
 
     # tiles no harmonic reaches take a precomputed partial instead of re-reading d and w
     # (efd_loglike_tile_constants; bitwise the same logL)
@@ -631,7 +581,6 @@ class Likelihood:
         so any group's later sum may read them."""
         if not self.fused_tile_constants:
             return None
-        from .summation import loglike_tile_constants
         nf, k0 = int(freq.numel()), int(k0)
         key = (nf, k0, id(self._d), id(self._w_templ))
         tc = self._tile_const
@@ -647,8 +596,7 @@ class Likelihood:
     def _fused_grid_ok(self, tm, kwargs):
         """Whether the template's grid for these kwargs is mirror-symmetric (the fused sum's
         requirement); set up once per grid, without queueing any device work."""
-        cw = getattr(getattr(getattr(tm, "waveform_generator", None), "waveform_generator", None),
-                     "create_waveform", None)
+        cw = _create_waveform(tm)
         if cw is None or not hasattr(cw, "_grid"):
             return False
         _, sym = cw._grid(kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("f_arr"))
@@ -657,11 +605,8 @@ class Likelihood:
     def _pipeline_for(self, tm):
         """The WaveformPipeline (self.num_streams slots) and per-slot buffers of get_ll."""
         torch = self.torch
-        from .reductions import Reducer
-        from .summation import WaveformPipeline
         nch, nb = self._d.shape
-        caustic = getattr(getattr(getattr(tm.waveform_generator, "waveform_generator", None),
-                                  "create_waveform", None), "caustic", "uniform")
+        caustic = _caustic(tm)
         P = getattr(self, "_pipe", None)
         if P is None or P.caustic != caustic:
             P = self._pipe = WaveformPipeline(self.num_streams, caustic=caustic,
@@ -692,11 +637,9 @@ class Likelihood:
         if self.parameter_transforms is not None:
             key = list(self.parameter_transforms.keys())[0]
             params = self.parameter_transforms[key].both_transforms(params)
-        if self.transpose_params:
+        subset_axis = 1 if self.transpose_params else 0
+        if subset_axis:
             params = params.T
-            subset_axis = 1
-        else:
-            subset_axis = 0
         num_likes = params.shape[subset_axis]
         inds_likes = np.arange(num_likes)
         if self.subset is not None:
@@ -715,6 +658,118 @@ class Likelihood:
         if self.separate_d_h:   # (<d|h>, <h|h>) per subset: each concatenated on its own
             return tuple(np.concatenate([o[k] for o in out_ll], axis=0) for k in range(2))
         return np.concatenate(out_ll, axis=0)
+
+
+class _HostFeed:
+    """Fused groups (at most FUSED_GROUP walkers) fed from the host upstream, which starts on
+    the prefetch pool at once: the template chain collects a group's packed host inputs in the
+    preparer (submit_batch), whose flush stages, uploads and prepares them."""
+    futs = ()
+
+    def __init__(self, like, F, tm, params, args, kwargs):
+        self.B, self.tm, self.params, self.args, self.kwargs = F["prep"], tm, params, args, kwargs
+        self.batch = getattr(tm, "submit_batch", None)
+        _prefetch(tm, params, args, kwargs)
+
+    def collect(self, g):
+        """Walkers g into the preparer; the stream, grid and k0 of the flush that takes them."""
+        if self.batch is not None:
+            self.batch(self.B, self.params[g], *self.args, **self.kwargs)
+        else:
+            for p in self.params[g]:
+                self.tm.submit(self.B, None, *p, *self.args, order=False, prepare_only=True,
+                               **self.kwargs)
+        return self.B.next_flush()
+
+    def flush(self, g):
+        """(group index, walkers, the group's stream, grid, k0) of walkers g, prepared."""
+        sst, freq, k0 = self.collect(g)
+        gi, jobs = self.B.flush()
+        return gi, len(jobs), sst, freq, k0
+
+
+class _DeviceFeed:
+    """Fused groups (at most EFD_BATCH_MAX walkers) fed from the device upstream: the walkers'
+    trajectories start on the prefetch pool at once (device_trajectory: all of them in one
+    launch on the current stream, which the group streams are then ordered after); per group
+    the generator's device_inputs_batch (packed trajectory upload, efd_modes_select_batch, the
+    read of the group's K) runs on the group's stream and BatchPreparer.flush_device prepares
+    the group from what it left on the device, so a group's device chain runs beside the next
+    group's trajectories and selection."""
+
+    def __init__(self, like, F, tm, params, args, kwargs):
+        self.B, self.few, self.kwargs = F["prep"], tm.waveform_generator, kwargs
+        self.device = like.device
+        cw = _create_waveform(tm)
+        self.freq, _ = cw._grid(kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("f_arr"))
+        self.k0 = cw.positive_start()
+        if getattr(tm, "_suffix_k0", self.k0) != self.k0:
+            raise ValueError("positive_frequency_mask does not match the generator's grid")
+        self.B.restart()
+        self.calls, self.scales = self.few.device_calls(params, kwargs.get("T", 1.0),
+                                                        kwargs.get("eps", 1e-5))
+        self.futs, self.trajs = [], None
+        if like.device_trajectory:
+            self.trajs = self.few.device_trajectories(self.calls, like.device,
+                                                      F.setdefault("traj", {}))
+        else:
+            self.futs = self.few.waveform_generator.trajectories_async(self.calls)
+
+    def flush(self, g):
+        """As _HostFeed.flush."""
+        sst = self.B.next_flush()[0]
+        inps = self.few.waveform_generator.device_inputs_batch(
+            self.calls[g], include_minus_m=bool(self.kwargs.get("include_minus_m", True)),
+            device=self.device, stream=sst, state=self.B.next_select(),
+            futures=self.futs[g] if self.trajs is None else None,
+            trajs=self.trajs[g] if self.trajs is not None else None)
+        gi, jobs = self.B.flush_device(inps, self.freq, self.scales[g], self.k0)
+        return gi, len(jobs), sst, self.freq, self.k0
+
+
+# The output kinds of Likelihood._run. tail, width: a walker's slot in `out` ([n, *tail], width
+# doubles); reduce(reducer, h, d, w, out=): one written template to its slot; window: the
+# windowed branch's per-group action, at most window_cap rows a group; fused_sum: the sum behind
+# a fused group's flush; native_group: whether the host route's one-call group may take it;
+# device, host: the result as the caller gets it.
+LOGL = SimpleNamespace(
+    tail=(), width=1, reduce=Reducer.loglike,
+    window=Likelihood._window_loglike, window_cap=_lib.EFD_HANN_ROWS_MAX,
+    fused_sum=Likelihood._sum_loglike, native_group=True,
+    device=lambda like, out: out, host=lambda host: host)
+PAIR = SimpleNamespace(
+    tail=(3,), width=3, reduce=Reducer.dh_hh_rows,
+    window=Likelihood._window_rows, window_cap=_lib.EFD_DH_MAX_ROWS,
+    fused_sum=Likelihood._sum_dh_hh, native_group=False,
+    device=lambda like, out: (like.torch.complex(out[:, 0], out[:, 1]), out[:, 2].clone()),
+    host=lambda host: (host[:, 0] + 1j * host[:, 1], host[:, 2].copy()))
+
+
+def _create_waveform(tm):
+    """tm.waveform_generator.waveform_generator.create_waveform (the mode sum's object), or None."""
+    return getattr(getattr(getattr(tm, "waveform_generator", None), "waveform_generator", None),
+                   "create_waveform", None)
+
+
+def _caustic(tm):
+    return getattr(_create_waveform(tm), "caustic", "uniform")
+
+
+def _window_group(tm, cap):
+    """Walkers per group of the windowed branch: EFD_WINDOW_GROUP, else the template model's
+    WINDOW_GROUP (8), at most `cap` rows (the group's reduction's limit)."""
+    return min(max(1, int(os.environ.get("EFD_WINDOW_GROUP", 0))
+                   or int(getattr(tm, "WINDOW_GROUP", 8))), cap)
+
+
+def _per_channel(x, nch, what):
+    """inject_signal's noise_fn / noise_kwargs, one per channel: a list of nch, or a list of
+    one or a single value repeated."""
+    if not isinstance(x, list):
+        return [x] * nch
+    if len(x) not in (1, nch):
+        raise ValueError(f"Number of {what} does not match number of channels declared by user.")
+    return x * nch if len(x) == 1 else x
 
 
 def _prefetch(tm, params, args, kwargs, concurrency=None):
@@ -739,150 +794,3 @@ def _to_numpy(x):
     if hasattr(x, "detach"):
         return x.detach().cpu().numpy()
     return np.asarray(x)
-
-
-# ---- what the (<d|h>, <h|h>) pair is for: host arithmetic on float64 arrays [B] ---------------
-def profile_none(d_d, re_dh, h_h):
-    """logL = -1/2 (d_d - 2 Re <d|h> + <h|h>)."""
-    return -0.5 * (d_d - 2.0 * np.asarray(re_dh, dtype=np.float64)
-                   + np.asarray(h_h, dtype=np.float64))
-
-
-def profile_amplitude(d_d, re_dh, h_h):
-    """The logL maximised over an overall amplitude A >= 0 of the template, in closed form:
-    (-1/2 d_d + 1/2 max(Re <d|h>, 0)^2 / <h|h>, A_hat = max(Re <d|h>, 0) / <h|h>); a walker
-    with <h|h> = 0 (no template) has A_hat = 0 and no gain."""
-    re = np.maximum(np.asarray(re_dh, dtype=np.float64), 0.0)
-    hh = np.asarray(h_h, dtype=np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        A = np.where(hh > 0.0, re / hh, 0.0)
-    return -0.5 * d_d + 0.5 * re * A, A
-
-
-# k of the break points u* +- k sigma of the distance quadrature's panels
-_PEAK_K = (0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 5.0, 6.0, 8.0, 10.0, 12.0, 16.0, 24.0, 40.0)
-_PANEL_MAX = 0.25    # the widest panel in log u
-DISTANCE_NODES = 16  # Gauss-Legendre nodes per panel
-
-
-def _distance_panels(re, hh, u_lo, u_hi):
-    """The panels' break points in t = log u for one walker: the range's ends, the Gaussian
-    factor's u* +- k sigma (u* = Re <d|h> / <h|h>, sigma = <h|h>^(-1/2)), a geometric ladder in
-    from each end at that end's decay length 1 / |Re <d|h> - u <h|h>| (a peak far outside the
-    range leaves an exponential against the nearer end), and a uniform split of what is still
-    wider than _PANEL_MAX."""
-    pts = [u_lo, u_hi]
-    if hh > 0.0:
-        us, sg = re / hh, hh ** -0.5
-        for k in _PEAK_K:
-            pts += [us - k * sg, us + k * sg]
-        pts.append(us)
-    for edge, sign in ((u_lo, 1.0), (u_hi, -1.0)):
-        slope = abs(re - edge * hh)
-        if slope > 0.0:
-            step = 1.0 / slope
-            while step < u_hi - u_lo:
-                pts.append(edge + sign * step)
-                step *= 2.0
-    t = np.log(np.unique(np.clip(np.asarray(pts, dtype=np.float64), u_lo, u_hi)))
-    out = [t[:1]]
-    for a, b in zip(t[:-1], t[1:]):
-        m = max(1, int(np.ceil((b - a) / _PANEL_MAX)))
-        out.append(a + (b - a) * np.arange(1, m + 1) / m)
-    return np.concatenate(out)
-
-
-def marginalize_distance(d_d, re_dh, h_h, dist_ref, dist_range, prior_power=2,
-                         nodes=DISTANCE_NODES):
-    """log of the likelihood marginalised over the distance D of a template made at dist_ref,
-      log int pi(D) exp(-1/2 d_d + u Re <d|h> - 1/2 u^2 <h|h>) dD,  u = dist_ref / D,
-    with pi proportional to D^prior_power, normalised on dist_range = (lo, hi). Per walker a
-    composite Gauss-Legendre rule in t = log u (dD = -D dt: the power-law prior and Jacobian are
-    smooth there) over _distance_panels' panels, `nodes` nodes each, summed in log-sum-exp form:
-    finite for <h|h> = 0 (the integrand is then the prior alone, log = -1/2 d_d) and for peaks
-    of any height."""
-    re = np.atleast_1d(np.asarray(re_dh, dtype=np.float64))
-    hh = np.atleast_1d(np.asarray(h_h, dtype=np.float64))
-    lo, hi = float(dist_range[0]), float(dist_range[1])
-    if not (0.0 < lo < hi) or not dist_ref > 0.0:
-        raise ValueError("marginalize_distance: 0 < lo < hi and dist_ref > 0")
-    p = float(prior_power)
-    # log of the prior's norm int_lo^hi D^p dD, with D in units of hi (no overflow)
-    lognorm = (np.log(np.log(hi / lo)) if p == -1.0
-               else np.log((1.0 - (lo / hi) ** (p + 1.0)) / (p + 1.0))) + (p + 1.0) * np.log(hi)
-    u_lo, u_hi = dist_ref / hi, dist_ref / lo
-    x, wq = np.polynomial.legendre.leggauss(int(nodes))
-    out = np.empty(len(re), dtype=np.float64)
-    for i in range(len(re)):
-        t = _distance_panels(re[i], hh[i], u_lo, u_hi)
-        a, b = t[:-1, None], t[1:, None]
-        tt = 0.5 * (a + b) + 0.5 * (b - a) * x[None, :]
-        ww = 0.5 * (b - a) * wq[None, :]
-        u = np.exp(tt)
-        # pi(D) dD = D^(p + 1) dt / norm, D = dist_ref / u
-        L = np.log(ww) + (p + 1.0) * (np.log(dist_ref) - tt) + u * re[i] - 0.5 * u * u * hh[i]
-        m = L.max()
-        out[i] = m + np.log(np.exp(L - m).sum()) - lognorm
-    return -0.5 * d_d + out
-
-
-class ProfiledLikelihood:
-    """A Likelihood's logL with the template's overall amplitude (the source's distance) taken
-    out, from Likelihood.parts' pair: a callable (params, **kwargs) -> float64 [B] that a sampler
-    takes as its log-likelihood. The parameters go through the likelihood's own __call__ (its
-    transforms and subset batching).
-
-    mode: "none", -1/2 (d_d - 2 Re <d|h> + <h|h>): the plain logL from the pair;
-          "amplitude", profile_amplitude's closed form; `last` then holds A_hat and, with
-            dist_ref, D_hat = dist_ref / A_hat of the last call;
-          "distance", marginalize_distance over dist_range with the prior D^prior_power, the
-            templates being made at distance dist_ref.
-    snr(params, **kwargs) returns (sqrt <h|h>, Re <d|h> / sqrt <h|h>): the optimal and the
-    matched-filter SNR of every walker."""
-
-    MODES = ("none", "amplitude", "distance")
-
-    def __init__(self, like, mode, dist_ref=None, dist_range=None, prior_power=2):
-        if mode not in self.MODES:
-            raise ValueError(f"mode: one of {self.MODES}")
-        if mode == "distance" and (dist_ref is None or dist_range is None):
-            raise ValueError("mode 'distance' needs dist_ref and dist_range")
-        self.like, self.mode = like, mode
-        self.dist_ref, self.dist_range, self.prior_power = dist_ref, dist_range, prior_power
-        self.last = {}
-
-    def parts(self, params, **kwargs):
-        """(<d|h> complex128 [B], <h|h> float64 [B]) through the likelihood's __call__."""
-        like = self.like
-        keep = like.separate_d_h
-        like.separate_d_h = True
-        try:
-            d_h, h_h = like(params, **kwargs)
-        finally:
-            like.separate_d_h = keep
-        return d_h, h_h
-
-    def combine(self, d_d, d_h, h_h):
-        """The mode's logL from given numbers (host arithmetic only)."""
-        re = np.real(d_h)
-        if self.mode == "none":
-            return profile_none(d_d, re, h_h)
-        if self.mode == "amplitude":
-            ll, A = profile_amplitude(d_d, re, h_h)
-            self.last = {"A_hat": A}
-            if self.dist_ref is not None:
-                with np.errstate(divide="ignore"):
-                    self.last["D_hat"] = np.where(A > 0.0, self.dist_ref / A, np.inf)
-            return ll
-        return marginalize_distance(d_d, re, h_h, self.dist_ref, self.dist_range,
-                                    self.prior_power)
-
-    def __call__(self, params, **kwargs):
-        d_h, h_h = self.parts(params, **kwargs)
-        return self.combine(self.like.d_d, d_h, h_h)
-
-    def snr(self, params, **kwargs):
-        d_h, h_h = self.parts(params, **kwargs)
-        rho = np.sqrt(h_h)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return rho, np.where(rho > 0.0, np.real(d_h) / rho, 0.0)

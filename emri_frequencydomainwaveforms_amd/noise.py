@@ -13,6 +13,7 @@ geometry, and a slice of a grid (bin0) is bitwise the whole grid's.
                      space has gain = 1: its noise is 0.5 xi on every bin, whatever the PSD)
   generate_noise_fd  lisatools' helper for one channel of strain noise
   new_seed           a 63-bit seed from the OS
+  check_seed         the range a caller's seed must lie in
 """
 
 import os
@@ -35,6 +36,14 @@ def _reducer(device):
 def new_seed():
     """A seed from the OS's entropy (63 bits, so that it survives a signed 64-bit store)."""
     return int.from_bytes(os.urandom(8), "little") >> 1
+
+
+def check_seed(seed, what="noise_seed"):
+    """`seed` as an int the generator's 64-bit key holds, or ValueError."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: an integer in 0..2^64 - 1")
+    return seed
 
 
 def standard_noise(nchan, nbin, seed, realization=0, bin0=0, gain=None, out=None,

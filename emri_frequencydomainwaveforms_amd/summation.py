@@ -939,7 +939,7 @@ class BatchPreparer:
         """flush() and sum_loglike() of the collected walkers in one native call
         (efd_fused_group: staging, upload, the staged event, the preparation and the fused sum
         on the next group's stream); returns the group index. The fused likelihood's per-group
-        host path (Likelihood._get_ll_fused): the same launches on the same stream as flush()
+        host path (Likelihood._run_fused): the same launches on the same stream as flush()
         then sum_loglike(gi, ..., G's stream), bitwise the same logL, in one ctypes
         transition instead of five. d, w: checked once per pair of buffers. The logL go to
         out[out_off : out_off + n]."""

@@ -291,14 +291,19 @@ def test_failing_walker_gets_three_nan(sources):
 
 
 # ---- Likelihood.parts, one test per branch ---------------------------------------------------
-def _check_parts(like, gen, walkers, kw, templates=None):
+def _check_parts(like, gen, walkers, kw, branch, templates=None):
     """parts against the identity with get_ll of the same object, and against
     diagnostic.inner_product(..., complex=True) on gen(*params); returns (d_h, h_h).
+    branch: the branch both calls must report (Likelihood.branch_taken), so that neither output
+    kind is quietly sent down another route.
     templates: the walkers' templates [n][2][nb] where gen(*params) is not what the branch
     evaluates (the device trajectory)."""
     from emri_frequencydomainwaveforms_amd import diagnostic as dg
     ll = like.get_ll(walkers, **kw)
+    took = like.branch_taken
     d_h, h_h = like.parts(walkers, **kw)
+    print("branch of get_ll, of parts:", took, like.branch_taken)
+    assert took == like.branch_taken == branch
     assert d_h.dtype == np.complex128 and h_h.dtype == np.float64
     assert d_h.shape == h_h.shape == (len(walkers),)
     d_d = like.d_d
@@ -345,7 +350,7 @@ def _walkers(s):
 
 def test_parts_fused_host_upstream(small):
     s = small
-    d_h, h_h = _check_parts(s.like, s.gen, _walkers(s), s.kwargs)
+    d_h, h_h = _check_parts(s.like, s.gen, _walkers(s), s.kwargs, "fused")
     # the data is the model's own output: the truth's numbers coincide
     assert d_h[0].real == h_h[0] and d_h[0].imag == 0.0
     # separate_d_h=True returns the pair through get_ll, and __call__ with subset through it
@@ -394,7 +399,7 @@ def test_parts_device_routes(small, route):
                                 device="cuda")
         s.few.generate_batch(W, templates, **s.kwargs, **route)
         torch.cuda.synchronize()
-    d_h, h_h = _check_parts(s.like, s.gen, W, s.kwargs, templates)
+    d_h, h_h = _check_parts(s.like, s.gen, W, s.kwargs, "fused", templates)
     assert np.all(h_h > 0)
 
 
@@ -412,7 +417,7 @@ def test_parts_pipelined_asymmetric_grid(small):
     like = Likelihood(gen, 2, f_arr=f_arr[f_arr >= 0], use_gpu=True)
     like.inject_signal(data_stream=gen(*s.truth14, **kw), noise_fn=[get_sensitivity] * 2,
                        noise_kwargs=[{}, {}])
-    _check_parts(like, gen, _walkers(s), kw)
+    _check_parts(like, gen, _walkers(s), kw, "per_slot")
     # the plain fill branch, a plain callable and a vectorized one on the same grid
     class FillOnly:
         can_fill = True
@@ -423,31 +428,34 @@ def test_parts_pipelined_asymmetric_grid(small):
         def __call__(self, *a, **k):
             return gen(*a, **k)
 
-    for tm, vec in ((FillOnly(), False), (lambda *a, **k: gen(*a, **k), False),
-                    (lambda *rows, **k: [gen(*r, **k) for r in rows], True)):
+    for tm, vec, branch in ((FillOnly(), False, "fill"),
+                            (lambda *a, **k: gen(*a, **k), False, "call"),
+                            (lambda *rows, **k: [gen(*r, **k) for r in rows], True, "vectorized")):
         lk2 = Likelihood(tm, 2, f_arr=f_arr[f_arr >= 0], use_gpu=True, vectorized=vec)
         lk2.inject_signal(data_stream=gen(*s.truth14, **kw), noise_fn=[get_sensitivity] * 2,
                           noise_kwargs=[{}, {}])
-        _check_parts(lk2, gen, _walkers(s)[:3], kw)
+        _check_parts(lk2, gen, _walkers(s)[:3], kw, branch)
 
 
 def test_parts_td_template():
     from emri_frequencydomainwaveforms_amd import pe
     s = pe.setup(template="td", Tobs=0.02, dt=20.0, M=3e5, nwalkers=4)
-    _check_parts(s.like, s.gen, _walkers(s), s.kwargs)
+    _check_parts(s.like, s.gen, _walkers(s), s.kwargs, "window_batch")
 
 
 def test_parts_short_windowed_grid():
     from emri_frequencydomainwaveforms_amd import pe
     s = pe.setup(Tobs=0.02, dt=10.0, M=1e5, window_flag=True, nwalkers=4)
-    _check_parts(s.like, s.gen, _walkers(s), s.kwargs)
+    # (a grid too short for HannConvolution keeps the exact transform pair: no batch, the fill)
+    assert not s.gen.can_fill_batch
+    _check_parts(s.like, s.gen, _walkers(s), s.kwargs, "fill")
 
 
 def test_parts_batched_window_path():
     from emri_frequencydomainwaveforms_amd import pe
     s = pe.setup(Tobs=0.75, dt=10.0, eps=1e-2, nwalkers=4, ntemps=1, window_flag=True)
     assert s.gen.can_fill_batch
-    _check_parts(s.like, s.gen, _walkers(s)[:3], s.kwargs)
+    _check_parts(s.like, s.gen, _walkers(s)[:3], s.kwargs, "window_batch")
 
 
 @pytest.mark.parametrize("mode", ["amplitude", "distance"])

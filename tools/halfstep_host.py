@@ -5,8 +5,8 @@
 ("python": the groups' host steps in Python, Likelihood.FUSED_NATIVE_GROUP = False)
 
 Runs bench.py's likelihood setup (pe.setup) and times the product code itself: the methods
-Likelihood._get_ll_fused calls (the template's submit_batch, BatchPreparer.flush_loglike or
-flush + sum_loglike, _tile_constants) and BatchPreparer's steps inside a flush (_take: the
+Likelihood._run_fused's group steps call (the template's submit_batch, BatchPreparer.flush_loglike
+or flush + sum_loglike, _tile_constants) and BatchPreparer's steps inside a flush (_take: the
 checks and waits, _sources, _stage, the workspace sizing) are wrapped with perf_counter
 accumulators. Prints microseconds per half-step; a flush's figure includes its steps'.
 """
