@@ -98,20 +98,20 @@ static_assert(offsetof(Item, ph) % 16 == 0 && offsetof(Item, fd) % 16 == 0 &&
               offsetof(Item, fdd) % 16 == 0, "the fast path's coefficient pairs are 16-B aligned");
 static_assert(offsetof(Item, b) % 16 == 0 && sizeof(Item::b) == 8 * 16, "b: 8 whole pieces");
 
-// The error flags (runs_overflow, bad_mn, bad_tile) are sticky: k_group clears only the counters
-// of a header it has initialised before (magic == HDR_MAGIC), so an error raised by any call on
-// this workspace survives later preparations until efd_modesum_status reports and clears it (a
-// pipeline slot reused by several walkers before its status is read loses none of them). A
-// header without the magic (fresh device memory) is zeroed whole.
+// The error flags (runs_overflow, bad_mn, bad_tile) are sticky: k_group_b clears only the
+// counters of a header it has initialised before (magic == HDR_MAGIC), so an error raised by any
+// call on this workspace survives later preparations until efd_modesum_status reports and clears
+// it (a pipeline slot reused by several walkers before its status is read loses none of them).
+// A header without the magic (fresh device memory) is zeroed whole.
 constexpr int64_t HDR_MAGIC = 0x45464448445233LL;   // "EFDHDR3"
 struct Header {
     int64_t contributions;      // C of the last call: (l, m, n) branch x bin pairs (k_items)
     int64_t evaluations;        // SPA evaluations: (m, n) group branch x bin pairs
-    int32_t runs_overflow;      // set by k_prep when a harmonic has > MAXRUNS monotonic runs
-    int32_t groups;             // G: distinct (m, n) of the call (k_group)
-    int32_t bad_mn;             // set by k_group when |m| > 255 or |n| > 1023
+    int32_t runs_overflow;      // set by k_prep_b when a harmonic has > MAXRUNS monotonic runs
+    int32_t groups;             // G: distinct (m, n) of the call (k_group_b)
+    int32_t bad_mn;             // set by k_group_b when |m| > 255 or |n| > 1023
     int32_t bad_tile;           // set by k_modesum when a dispatch-order entry is out of range
-    int64_t magic;              // HDR_MAGIC once k_group has initialised the header
+    int64_t magic;              // HDR_MAGIC once k_group_b has initialised the header
     int32_t lane_lo, lane_hi;   // union [lo, hi) of the segments' lane ranges (k_segment_compact)
     int32_t nitems;             // sparse sum's work items (k_segments_one's split plan), -1: none
     int32_t nsplit;             // split tiles of the plan
@@ -133,18 +133,25 @@ __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~size_
 
 // (also evaluated on the device by the batched preparation kernels: a few dozen scalar integer
 // operations per workgroup, so the kernel arguments carry one workspace pointer per waveform)
-__host__ __device__ inline Layout make_layout(int32_t nt, int32_t K, int64_t nf, int paired) {
+// td: the TD sum's workspace instead, the FD layout's grouping and spline buffers only, in the
+// same order (no records, no segment tables, no sin/cos table, no tile lists: those take no
+// room there, and no stage of the TD preparation touches their offsets)
+__host__ __device__ inline Layout make_layout(int32_t nt, int32_t K, int64_t nf, int paired,
+                                              bool td = false) {
     Layout L{};
     const int64_t ni = nt - 1;
     L.nlanes = paired ? (nf + 1) / 2 : nf;
     L.ntiles = (L.nlanes + TILE_LANES - 1) / TILE_LANES;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    L.header = take(sizeof(Header));
-    L.coefA = take(sizeof(double) * ni * 4 * 4 * K);   // [ni][4][4K]: Bp re/im, Bm re/im
-    L.coefT = take(sizeof(double) * ni * 4 * 8);
-    L.kslope = take(sizeof(double) * nt * 2);
-    L.tscratch = take(sizeof(double) * nt * 16);
+    // all: a buffer of both workspaces; take: one of the FD workspace alone, no bytes under td
+    // (the choice is made on the size, not on the offset: the offsets stay one chain of adds)
+    auto all = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
+    auto take = [&](size_t bytes) { return all(td ? 0 : bytes); };
+    L.header = all(sizeof(Header));
+    L.coefA = all(sizeof(double) * ni * 4 * 4 * K);   // [ni][4][4K]: Bp re/im, Bm re/im
+    L.coefT = all(sizeof(double) * ni * 4 * 8);
+    L.kslope = all(sizeof(double) * nt * 2);
+    L.tscratch = all(sizeof(double) * nt * 16);
     L.invcp = take(sizeof(double) * nt * K);
     L.invdp = take(sizeof(double) * nt * K);
     L.runs = take(sizeof(int32_t) * 4 * MAXRUNS * K);
@@ -163,12 +170,12 @@ __host__ __device__ inline Layout make_layout(int32_t nt, int32_t K, int64_t nf,
     L.stbcap = 64 * L.ntiles + 4 * (int64_t)(2 * MAXRUNS * K);
     L.stb0 = take(sizeof(int32_t) * (size_t)L.stbcap);
     L.stb1 = take(sizeof(int32_t) * (size_t)L.stbcap);
-    L.gm = take(sizeof(int32_t) * K);
-    L.gn = take(sizeof(int32_t) * K);
-    L.gstart = take(sizeof(int32_t) * (K + 1));
-    L.gmem = take(sizeof(int32_t) * K);
-    L.gkeys = take(sizeof(unsigned long long) * (size_t)MAX_K);   // k_group's general-case sort
-    L.gamp = take(sizeof(double) * nt * 4 * K);
+    L.gm = all(sizeof(int32_t) * K);
+    L.gn = all(sizeof(int32_t) * K);
+    L.gstart = all(sizeof(int32_t) * (K + 1));
+    L.gmem = all(sizeof(int32_t) * K);
+    L.gkeys = all(sizeof(unsigned long long) * (size_t)MAX_K);   // k_group_b's general-case sort
+    L.gamp = all(sizeof(double) * nt * 4 * K);
     L.sctab = take(sizeof(double) * 2 * 512);
     L.tkeys = take(sizeof(uint32_t) * (size_t)L.ntiles * KEYCAP);   // prebuilt tile lists
     L.tcnt = take(sizeof(int32_t) * (size_t)L.ntiles);
@@ -209,6 +216,7 @@ struct PrepBatch {
     int32_t pcr_groups;   // k_prep_pcr_b groups the harmonics itself (k_group_b not launched)
     int32_t seg_lds;      // k_segments_one's dynamic LDS bytes for the ranges table (0: none)
     int32_t split_min;    // k_segments_one: tiles costing at most this (wave-records) stay whole
+    int32_t td;           // the TD sum's preparation: d[0].ws is a TD workspace (make_td_layout)
 };
 static_assert(sizeof(PrepBatch) <= 3072, "kernel arguments stay well inside 4 KB");
 
@@ -252,28 +260,8 @@ __device__ __forceinline__ int block_excl_scan(int v, int* wsum, int lane, int w
 constexpr int32_t SEG_NO_STB = INT32_MIN;
 
 // TD workspace: the FD layout's grouping and spline buffers only (no records, no tile lists)
-struct TdLayout {
-    size_t header, coefA, coefT, kslope, tscratch, gm, gn, gstart, gmem, gkeys, gamp, total;
-};
-inline TdLayout make_td_layout(int32_t nt, int32_t K) {
-    TdLayout L{};
-    const int64_t ni = nt - 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    L.header = take(sizeof(Header));
-    L.coefA = take(sizeof(double) * ni * 4 * 4 * K);
-    L.coefT = take(sizeof(double) * ni * 4 * 8);
-    L.kslope = take(sizeof(double) * nt * 2);
-    L.tscratch = take(sizeof(double) * nt * 16);
-    L.gm = take(sizeof(int32_t) * K);
-    L.gn = take(sizeof(int32_t) * K);
-    L.gstart = take(sizeof(int32_t) * (K + 1));
-    L.gmem = take(sizeof(int32_t) * K);
-    L.gkeys = take(sizeof(unsigned long long) * (size_t)MAX_K);
-    L.gamp = take(sizeof(double) * nt * 4 * K);
-    L.total = off;
-    return L;
-}
+using TdLayout = Layout;
+inline TdLayout make_td_layout(int32_t nt, int32_t K) { return make_layout(nt, K, 0, 0, true); }
 
 }  // namespace
 
@@ -298,7 +286,8 @@ EFD_INTERNAL int launch_tile_lists(const void* prep_batch, int64_t ntiles, bool 
 EFD_INTERNAL int prepare_batch(const char* fn, const efd_modesum_args* const* a,
                                void* const* workspace, const size_t* workspace_bytes,
                                int32_t count, void* stream);
-// The TD sum's preparation (emrifd_prepare.hip): header cleared, k_group, k_group_amp and
-// k_prep's spline roles into the checked workspace (make_td_layout)
+// The TD sum's preparation (emrifd_prepare.hip): header cleared, then a PrepBatch of one with
+// td set through k_group_b, k_group_amp_b and k_prep_b's trajectory and amplitude roles, into
+// the checked workspace (make_td_layout)
 EFD_INTERNAL int td_prepare(const efd_td_args* a, void* workspace, hipStream_t st);
 }  // namespace efdhip

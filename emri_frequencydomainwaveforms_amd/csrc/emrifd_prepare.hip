@@ -4,7 +4,10 @@
 // (k_items) and the segment table (k_segment_*, k_seg_tiles, k_segments_one), with their host
 // side: efd_modesum_prepare, efd_modesum_prepare_batch, efd_spline_build and the TD sum's
 // preparation. It writes the workspace (emrifd_layout.h) that emrifd.hip's K6-K9 read, and uses
-// nothing else of that unit's device code; the chain ends by launching K6 there.
+// nothing else of that unit's device code; the chain ends by launching K6 there. Every stage is
+// one kernel that takes the batch descriptor by value and reads its waveform's inputs and
+// workspace buffers through a PrepView; the TD sum's preparation is a batch of one through the
+// first three of them.
 
 #include "emrifd_layout.h"
 
@@ -264,6 +267,60 @@ __device__ void pcr_not_a_knot(int n, FX X, FY Y, FOUT OUT, double* L) {
 }
 
 // ----------------------------------------------------------------------------------------
+// One waveform's preparation state as its workgroup sees it, built once from (B, blockIdx.z):
+// the waveform's inputs and switches (PrepDesc: t .. f_r, amp, ylm_*, m, n, freq, the scale,
+// nt, K, lists, pcr, env), the batch's grid scalars, and the workspace's buffers by name and
+// type. A stage takes the view and names the buffers it touches. The three kernels the TD sum's
+// preparation shares (k_group_b, k_group_amp_b, k_prep_b) pass td = B.td: in a TD workspace
+// only the header, the spline and the group buffers exist (make_layout's td) and every other
+// pointer of the view is null. The kernels of the FD chain alone leave td at its constant.
+// ----------------------------------------------------------------------------------------
+struct PrepView : PrepDesc {
+    int64_t nf, nl, nl1, stbcap;
+    int32_t paired, td;
+    Header* header;
+    double *coefA, *coefT, *kslope, *tscratch, *invcp, *invdp, *gamp;
+    int32_t *runs, *nseg, *slotcnt, *slottiles, *segbase, *stb0, *stb1;
+    int32_t *gm, *gn, *gstart, *gmem;
+    unsigned long long* gkeys;
+    Item* items;
+    int4 *ranges, *seginfo, *slotinfo;
+    int2 *seglh, *slotlh;
+    double2* sctab;
+    int4* sitem;     // the split plan: items, and one arrival counter per split tile
+    int32_t* scnt;
+    __device__ __forceinline__ explicit PrepView(const PrepBatch& B, bool td_ws = false)
+        : PrepDesc(B.d[blockIdx.z]), nf(B.nf), nl(B.nl), nl1(B.nl1), paired(B.paired),
+          td(td_ws) {
+        const Layout L = make_layout(nt, K, nf, paired, td_ws);
+        stbcap = L.stbcap;
+        at(header, L.header); at(coefA, L.coefA); at(coefT, L.coefT); at(kslope, L.kslope);
+        at(tscratch, L.tscratch); at(gm, L.gm); at(gn, L.gn); at(gstart, L.gstart);
+        at(gmem, L.gmem); at(gkeys, L.gkeys); at(gamp, L.gamp);
+        fd(invcp, L.invcp); fd(invdp, L.invdp); fd(runs, L.runs); fd(items, L.items);
+        fd(ranges, L.ranges); fd(seglh, L.seglh); fd(seginfo, L.seginfo); fd(nseg, L.nseg);
+        fd(slotlh, L.slotlh); fd(slotinfo, L.slotinfo); fd(slotcnt, L.slotcnt);
+        fd(slottiles, L.slottiles); fd(segbase, L.segbase); fd(stb0, L.stb0); fd(stb1, L.stb1);
+        fd(sctab, L.sctab); fd(sitem, L.sitem); fd(scnt, L.scnt);
+    }
+    // lane limit of sub-branch sb's segments (paired grids: the non-positive half, see K4)
+    // (from copies: a choice between members themselves becomes a variable offset into the view,
+    // which then lives in scratch memory)
+    __device__ __forceinline__ int seg_lim(int sb) const {
+        const int64_t all = nf, lim0 = nl, lim1 = nl1;
+        return (int)(paired ? (sb ? lim1 : lim0) : all);
+    }
+
+private:
+    template <class T>
+    __device__ __forceinline__ void at(T*& p, size_t off) { p = ws_at<T>(ws, off); }
+    template <class T>   // a buffer of the FD workspace alone
+    __device__ __forceinline__ void fd(T*& p, size_t off) {
+        p = td ? nullptr : ws_at<T>(ws, off);
+    }
+};
+
+// ----------------------------------------------------------------------------------------
 // K0: (m, n) groups: gm[g], gn[g]; members gmem[gstart[g] .. gstart[g+1]); G = hdr->groups.
 // Groups ascend in (m, n), members in harmonic index h (the order every later kernel and the
 // oracle's grouping use; a function of (m, n) alone, so everything downstream is deterministic). One 256-thread workgroup with a small LDS footprint: it
@@ -299,14 +356,17 @@ __device__ __forceinline__ void group_minmax(int& v_lo, int& v_hi, int* red, int
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { red[wave * 4 + slot] = v_lo; red[16 + wave * 4 + slot] = v_hi; }
 }
-__device__ __forceinline__ void group_body(const int32_t* __restrict__ marr,
-                                               const int32_t* __restrict__ narr, int K,
-                                               int32_t* __restrict__ gm, int32_t* __restrict__ gn,
-                                               int32_t* __restrict__ gstart,
-                                               int32_t* __restrict__ gmem,
-                                               Header* __restrict__ hdr,
-                                               double2* __restrict__ sctab_g,
-                                               unsigned long long* __restrict__ gkeys) {
+// (The sort's arrays arrive as __restrict__ parameters, filled from the view by k_group_b:
+// read from the view itself, whose members cannot be __restrict__, the one workgroup ran 2%
+// longer, 23.4 instead of 22.9 us.)
+__device__ __forceinline__ void group_body(const PrepView& V, const int32_t* __restrict__ marr,
+                                           const int32_t* __restrict__ narr,
+                                           int32_t* __restrict__ gm, int32_t* __restrict__ gn,
+                                           int32_t* __restrict__ gstart,
+                                           int32_t* __restrict__ gmem,
+                                           unsigned long long* __restrict__ gkeys) {
+    const int K = V.K;
+    Header* hdr = V.header;
     constexpr int NTH = 256, NW = NTH / 64;
     __shared__ int bcnt[GB_CAP], boff[GB_CAP];
     __shared__ int red[32];
@@ -318,12 +378,13 @@ __device__ __forceinline__ void group_body(const int32_t* __restrict__ marr,
     if (tid == 0) header_init(hdr);
     __syncthreads();
     // k_modesum's (sin, cos)(k pi/256) table, computed once per waveform here and copied into
-    // each tile's LDS by LDS-DMA (cheaper than 512 sincospi per tile at small harmonic counts)
-    if (sctab_g != nullptr)
+    // each tile's LDS by LDS-DMA (cheaper than 512 sincospi per tile at small harmonic counts);
+    // the TD sum has no use for it and its workspace no room
+    if (!V.td)
         for (int i = tid; i < 512; i += NTH) {
             double sv, cv;
             sincospi((double)i / 256.0, &sv, &cv);
-            sctab_g[i] = make_double2(sv, cv);
+            V.sctab[i] = make_double2(sv, cv);
         }
     auto mval = [&](int i) { return min(max(marr[i], -256), 255); };
     auto nval = [&](int i) { return min(max(narr[i], -1024), 1023); };
@@ -450,18 +511,9 @@ __device__ __forceinline__ void group_body(const int32_t* __restrict__ marr,
         hdr->groups = G;
     }
 }
-__global__ __launch_bounds__(256) void k_group(const int32_t* __restrict__ marr,
-                                               const int32_t* __restrict__ narr, int K,
-                                               int32_t* gm, int32_t* gn, int32_t* gstart,
-                                               int32_t* gmem, Header* hdr, double2* sctab_g,
-                                               unsigned long long* gkeys) {
-    group_body(marr, narr, K, gm, gn, gstart, gmem, hdr, sctab_g, gkeys);
-}
 __global__ __launch_bounds__(256) void k_group_b(const PrepBatch B) {
-    PREP_WALKER(B);
-    group_body(D.m, D.n, D.K, ws_at<int32_t>(W, L.gm), ws_at<int32_t>(W, L.gn),
-               ws_at<int32_t>(W, L.gstart), ws_at<int32_t>(W, L.gmem), ws_at<Header>(W, L.header),
-               ws_at<double2>(W, L.sctab), ws_at<unsigned long long>(W, L.gkeys));
+    const PrepView V(B, B.td != 0);
+    group_body(V, V.m, V.n, V.gm, V.gn, V.gstart, V.gmem, V.gkeys);
 }
 
 // K0b: group amplitudes at the knots, one thread per (knot i, group g):
@@ -472,11 +524,11 @@ __global__ __launch_bounds__(256) void k_group_b(const PrepBatch B) {
 // k_prep_pcr_b's amplitude waves call it for their own component (no gamp pass, one launch
 // fewer in the chain; the same operations in the same order, so the same values).
 template <class MEM>
-__device__ __forceinline__ double4 group_amp_sum(const double* __restrict__ amp,
-                                                 const double* __restrict__ ylm_p,
-                                                 const double* __restrict__ ylm_m, double sc_re,
-                                                 double sc_im, bool partner, int p0, int p1,
-                                                 MEM mem, int K, int i) {
+__device__ __forceinline__ double4 group_amp_sum(const PrepView& V, bool partner, int p0, int p1,
+                                                 MEM mem, int i) {
+    const double *amp = V.amp, *ylm_p = V.ylm_p, *ylm_m = V.ylm_m;
+    const double sc_re = V.sc_re, sc_im = V.sc_im;
+    const int K = V.K;
     double bpr = 0.0, bpi = 0.0, bmr = 0.0, bmi = 0.0;
     for (int p = p0; p < p1; ++p) {
         const int h = mem(p);
@@ -494,15 +546,9 @@ __device__ __forceinline__ double4 group_amp_sum(const double* __restrict__ amp,
     }
     return make_double4(bpr, bpi, bmr, bmi);
 }
-__device__ __forceinline__ double4 group_amp_at(const double* __restrict__ amp,
-                                                const double* __restrict__ ylm_p,
-                                                const double* __restrict__ ylm_m, double sc_re,
-                                                double sc_im, const int32_t* __restrict__ gm,
-                                                const int32_t* __restrict__ gstart,
-                                                const int32_t* __restrict__ gmem, int K, int i,
-                                                int g) {
-    return group_amp_sum(amp, ylm_p, ylm_m, sc_re, sc_im, gm[g] != 0, gstart[g], gstart[g + 1],
-                         [&](int p) { return gmem[p]; }, K, i);
+__device__ __forceinline__ double4 group_amp_at(const PrepView& V, int i, int g) {
+    return group_amp_sum(V, V.gm[g] != 0, V.gstart[g], V.gstart[g + 1],
+                         [&](int p) { return V.gmem[p]; }, i);
 }
 // the grids of k_items and k_group_amp at K >= ITEMS_SPLIT_K: K / ITEMS_PER_THREAD_K threads per
 // interval or knot, a thread taking every (K / ITEMS_PER_THREAD_K)-th of the G <= K (m, n) groups
@@ -513,66 +559,42 @@ __device__ __forceinline__ double4 group_amp_at(const double* __restrict__ amp,
 #define ITEMS_PER_THREAD_K 8
 #endif
 constexpr int ITEMS_SPLIT_K = 1024;
-__device__ __forceinline__ void group_amp_body(const double* __restrict__ amp,
-                                                   const double* __restrict__ ylm_p,
-                                                   const double* __restrict__ ylm_m, double sc_re,
-                                                   double sc_im, const int32_t* __restrict__ gm,
-                                                   const int32_t* __restrict__ gstart,
-                                                   const int32_t* __restrict__ gmem, int nt, int K,
-                                                   const Header* __restrict__ hdr,
-                                                   double* __restrict__ gamp) {
+__global__ __launch_bounds__(256) void k_group_amp_b(const PrepBatch B) {
+    const PrepView V(B, B.td != 0);
+    if (V.pcr & 2) return;   // k_prep_pcr_b evaluates this waveform's group amplitudes itself
     // (the grid covers K / ITEMS_PER_THREAD_K groups at large K: a thread may take several)
     const int i = blockIdx.y;
-    const int G = hdr->groups;
-    if (i >= nt) return;
+    const int G = V.header->groups;
+    if (i >= V.nt) return;
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < G; g += gridDim.x * blockDim.x) {
-        const double4 v = group_amp_at(amp, ylm_p, ylm_m, sc_re, sc_im, gm, gstart, gmem, K, i,
-                                       g);
-        double* o = gamp + (size_t)i * 4 * K + 4 * g;
+        const double4 v = group_amp_at(V, i, g);
+        double* o = V.gamp + (size_t)i * 4 * V.K + 4 * g;
         o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
     }
-}
-__global__ __launch_bounds__(256) void k_group_amp(const double* __restrict__ amp,
-                                                   const double* __restrict__ ylm_p,
-                                                   const double* __restrict__ ylm_m, double sc_re,
-                                                   double sc_im, const int32_t* __restrict__ gm,
-                                                   const int32_t* __restrict__ gstart,
-                                                   const int32_t* __restrict__ gmem, int nt, int K,
-                                                   const Header* __restrict__ hdr,
-                                                   double* __restrict__ gamp) {
-    group_amp_body(amp, ylm_p, ylm_m, sc_re, sc_im, gm, gstart, gmem, nt, K, hdr, gamp);
-}
-__global__ __launch_bounds__(256) void k_group_amp_b(const PrepBatch B) {
-    PREP_WALKER(B);
-    if (D.pcr & 2) return;   // k_prep_pcr_b evaluates this waveform's group amplitudes itself
-    group_amp_body(D.amp, D.ylm_p, D.ylm_m, D.sc_re, D.sc_im, ws_at<int32_t>(W, L.gm),
-                   ws_at<int32_t>(W, L.gstart), ws_at<int32_t>(W, L.gmem), D.nt, D.K,
-                   ws_at<Header>(W, L.header), ws_at<double>(W, L.gamp));
 }
 
 // ----------------------------------------------------------------------------------------
 // K1: trajectory splines (one wave; lanes 0..3 the knot data, then lanes 4..5 the slopes)
 // coefT layout: [interval][coef c][q], q: 0 Phi_phi, 1 Phi_r, 2 f_phi, 3 f_r, 4 f_phi', 5 f_r'
 // ----------------------------------------------------------------------------------------
-__device__ void traj_splines(const double* __restrict__ t, const double* __restrict__ phi_phi,
-                               const double* __restrict__ phi_r, const double* __restrict__ f_phi,
-                               const double* __restrict__ f_r, int nt, double* __restrict__ coefT,
-                               double* __restrict__ kslope, double* __restrict__ scratch) {
+__device__ void traj_splines(const PrepView& V) {
+    const int nt = V.nt;
+    double *coefT = V.coefT, *kslope = V.kslope;
     // the serial Thomas chains read their knots from LDS instead of global memory
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* xs = lds;                 // t
     double* ys = lds + nt;            // 6 interpolants: Phi_phi, Phi_r, f_phi, f_r, f_phi', f_r'
     for (int i = threadIdx.x; i < nt; i += blockDim.x) {
-        xs[i] = t[i];
-        ys[i] = phi_phi[i];
-        ys[nt + i] = phi_r[i];
-        ys[2 * nt + i] = f_phi[i];
-        ys[3 * nt + i] = f_r[i];
+        xs[i] = V.t[i];
+        ys[i] = V.phi_phi[i];
+        ys[nt + i] = V.phi_r[i];
+        ys[2 * nt + i] = V.f_phi[i];
+        ys[3 * nt + i] = V.f_r[i];
     }
     __syncthreads();
     const int q = threadIdx.x;
-    double* cp = scratch + (size_t)q * nt;
-    double* dp = scratch + (size_t)(8 + q) * nt;
+    double* cp = V.tscratch + (size_t)q * nt;
+    double* dp = V.tscratch + (size_t)(8 + q) * nt;
     auto X = [&](int i) { return xs[i]; };
     auto CP = [&](int i) -> double& { return cp[i]; };
     auto DP = [&](int i) -> double& { return dp[i]; };
@@ -763,29 +785,26 @@ __device__ __forceinline__ double knotF_rn(const double* f_phi, const double* f_
     return a + b;
 }
 
-__device__ void inverse_splines(const double* __restrict__ t, const double* __restrict__ f_phi,
-                                  const double* __restrict__ f_r, const int32_t* __restrict__ marr,
-                                  const int32_t* __restrict__ narr, int nt, int K, int G,
-                                  int32_t* __restrict__ runs, Item* __restrict__ items,
-                                  double* __restrict__ cpbuf, double* __restrict__ dpbuf,
-                                  int32_t* __restrict__ err, int block) {
+__device__ void inverse_splines(const PrepView& V, int block) {
+    const int nt = V.nt, K = V.K, G = V.header->groups;
     if (block * (int)blockDim.x >= G) return;   // grid sized for K >= G
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* ts = lds;              // t, f_phi, f_r staged in LDS for the serial chains
     double* fps = lds + nt;
     double* frs = lds + 2 * nt;
     for (int i = threadIdx.x; i < nt; i += blockDim.x) {
-        ts[i] = t[i];
-        fps[i] = f_phi[i];
-        frs[i] = f_r[i];
+        ts[i] = V.t[i];
+        fps[i] = V.f_phi[i];
+        frs[i] = V.f_r[i];
     }
     __syncthreads();
     const int h = block * blockDim.x + threadIdx.x;   // (m, n) group
     if (h >= G) return;
-    const int m = marr[h], n = narr[h];
+    const int m = V.gm[h], n = V.gn[h];
     const int ni = nt - 1;
-    Item* it = items + (size_t)h * ni;
-    int32_t* rr = runs + (size_t)h * 4 * MAXRUNS;
+    Item* it = V.items + (size_t)h * ni;
+    int32_t* rr = V.runs + (size_t)h * 4 * MAXRUNS;
+    double *cpbuf = V.invcp, *dpbuf = V.invdp;
     for (int r = 0; r < MAXRUNS; ++r) { rr[4 * r] = 0; rr[4 * r + 1] = 0; rr[4 * r + 2] = 0; }
     int nrun = 0;
     int j = 0;
@@ -805,7 +824,7 @@ __device__ void inverse_splines(const double* __restrict__ t, const double* __re
                     rr[4 * nrun] = ja; rr[4 * nrun + 1] = j; rr[4 * nrun + 2] = cur_sign;
                     ++nrun;
                 } else {
-                    atomicOr(err, 1);
+                    atomicOr(&V.header->runs_overflow, 1);
                 }
             }
             cur_sign = sg;
@@ -837,69 +856,27 @@ __device__ void inverse_splines(const double* __restrict__ t, const double* __re
 // chains on few workgroups, so running them side by side costs max() instead of sum().
 // Block 0: trajectory splines; blocks [1, 1 + nb_amp): amplitude splines (64 interpolants per
 // block); the rest: inverse splines (64 harmonics per block).
-__device__ __forceinline__ void prep_body(
-    const double* __restrict__ t, const double* __restrict__ phi_phi,
-    const double* __restrict__ phi_r, const double* __restrict__ f_phi,
-    const double* __restrict__ f_r, const double* __restrict__ gamp,
-    const int32_t* __restrict__ gm,
-    const int32_t* __restrict__ gn, int nt, int K,
-    int nb_amp, double* __restrict__ coefT, double* __restrict__ kslope,
-    double* __restrict__ tscratch, double* coefA, int32_t* __restrict__ runs,
-    Item* __restrict__ items, double* __restrict__ invcp, double* __restrict__ invdp,
-    Header* __restrict__ hdr) {
-    const int b = blockIdx.x;
-    if (b == 0) {
-        traj_splines(t, phi_phi, phi_r, f_phi, f_r, nt, coefT, kslope, tscratch);
-    } else if (b < 1 + nb_amp) {
-        const int G = hdr->groups;
-        auto yf = [&](int i, int q) { return gamp[(size_t)i * 4 * K + q]; };
-        spline_shared(t, nt, yf, 4 * G, 4 * K, coefA, (int64_t)4 * 4 * K, b - 1);
-    } else {
-        inverse_splines(t, f_phi, f_r, gm, gn, nt, K, hdr->groups, runs, items, invcp, invdp,
-                        &hdr->runs_overflow, b - 1 - nb_amp);
-    }
-}
-__global__ __launch_bounds__(64) void k_prep(
-    const double* __restrict__ t, const double* __restrict__ phi_phi,
-    const double* __restrict__ phi_r, const double* __restrict__ f_phi,
-    const double* __restrict__ f_r, const double* __restrict__ gamp,
-    const int32_t* __restrict__ gm,
-    const int32_t* __restrict__ gn, int nt, int K,
-    int nb_amp, double* __restrict__ coefT, double* __restrict__ kslope,
-    double* __restrict__ tscratch, double* coefA, int32_t* __restrict__ runs,
-    Item* __restrict__ items, double* __restrict__ invcp, double* __restrict__ invdp,
-    Header* __restrict__ hdr) {
-    prep_body(t, phi_phi, phi_r, f_phi, f_r, gamp, gm, gn, nt, K, nb_amp, coefT, kslope, tscratch,
-              coefA, runs, items, invcp, invdp, hdr);
-}
-// the grid is sized for the batch's largest K: blocks past this waveform's roles leave at once
+// The grid is sized for the batch's largest K: blocks past this waveform's roles leave at once.
+// (The TD sum's preparation launches 1 + nb_amp blocks: it has no use for inverse splines.)
 __global__ __launch_bounds__(64) void k_prep_b(const PrepBatch B) {
-    PREP_WALKER(B);
-    const int nb_amp = (4 * D.K + 63) / 64, nb_inv = (D.K + 63) / 64;
-    if ((int)blockIdx.x >= 1 + nb_amp + nb_inv) return;
-    if (D.pcr & 1) {   // k_prep_pcr_b has the trajectory and inverse roles (and maybe this one)
-        const int b = blockIdx.x;
-        if (b == 0 || b >= 1 + nb_amp || (D.pcr & 2)) return;
+    const PrepView V(B, B.td != 0);
+    const int b = blockIdx.x, K = V.K;
+    const int nb_amp = (4 * K + 63) / 64, nb_inv = (K + 63) / 64;
+    if (b >= 1 + nb_amp + nb_inv) return;
+    // k_prep_pcr_b has the trajectory and inverse roles (and maybe this one)
+    if ((V.pcr & 1) && (b == 0 || b >= 1 + nb_amp || (V.pcr & 2))) return;
+    if (b == 0) {
+        traj_splines(V);
+    } else if (b < 1 + nb_amp) {
+        const int G = V.header->groups;
+        const double* gamp = V.gamp;
+        auto yf = [&](int i, int q) { return gamp[(size_t)i * 4 * K + q]; };
+        spline_shared(V.t, V.nt, yf, 4 * G, 4 * K, V.coefA, (int64_t)4 * 4 * K, b - 1);
+    } else {
+        inverse_splines(V, b - 1 - nb_amp);
     }
-    prep_body(D.t, D.phi_phi, D.phi_r, D.f_phi, D.f_r, ws_at<double>(W, L.gamp),
-              ws_at<int32_t>(W, L.gm), ws_at<int32_t>(W, L.gn), D.nt, D.K, nb_amp,
-              ws_at<double>(W, L.coefT), ws_at<double>(W, L.kslope), ws_at<double>(W, L.tscratch),
-              ws_at<double>(W, L.coefA), ws_at<int32_t>(W, L.runs), ws_at<Item>(W, L.items),
-              ws_at<double>(W, L.invcp), ws_at<double>(W, L.invdp), ws_at<Header>(W, L.header));
 }
 
-// K1-K3 with one wave per interpolant (parallel cyclic reduction): blocks [0, 4) the trajectory splines (Phi_phi,
-// Phi_r, f_phi, f_r; the f_phi and f_r blocks go on to f_phi', f_r' from their own knot
-// slopes), [4, 4 + K) the inverse splines of group h = b - 4 < G, [4 + K, 4 + 5K) the group
-// amplitude splines (interpolant q = b - 4 - K < 4G; only when Item::pcr bit 1 is set, else the
-// grid stops at 4 + K). Blocks past this waveform's G leave at once.
-// The same coefficients as k_prep's (scipy's construction, to rounding); for 4 <= N_t <=
-// PCR_NMAX (the host takes k_prep_b otherwise). Dynamic LDS: 9 N_t doubles.
-struct GroupAmpSrc {   // group_amp_at's operands
-    const double *amp, *ylm_p, *ylm_m;
-    double sc_re, sc_im;
-    const int32_t *gstart, *gmem;
-};
 // The block's (m, n) group when k_prep_pcr_b groups the harmonics itself (PrepBatch::pcr_groups,
 // k_group_b not launched): G, the group's (m, n) and its members in ascending h (LDS)
 struct LocalGroups {
@@ -907,14 +884,99 @@ struct LocalGroups {
     int G, m, n, count;
     const int* mem;
 };
-__device__ __forceinline__ void prep_pcr_body(
-    const double* __restrict__ t, const double* __restrict__ phi_phi,
-    const double* __restrict__ phi_r, const double* __restrict__ f_phi,
-    const double* __restrict__ f_r, const GroupAmpSrc ga, const LocalGroups lg,
-    const int32_t* __restrict__ gm, const int32_t* __restrict__ gn, int nt, int K,
-    double* __restrict__ coefT, double* __restrict__ kslope, double* __restrict__ coefA,
-    int32_t* __restrict__ runs, Item* __restrict__ items, double* __restrict__ invcp,
-    double* __restrict__ invdp, Header* __restrict__ hdr) {
+// PrepBatch::pcr_groups (every waveform of the batch on the PCR roles with K <= 64): each block
+// groups the K harmonics itself, one per lane: a harmonic's group is the rank of its (m, n) among
+// the distinct pairs, its place in gmem the count of harmonics of smaller (m, n) plus the members
+// of its own before it. The same groups, order and member lists as k_group_b's counting sort (the
+// same clamping and bad_mn rule). Block 0 also writes them (gm, gn, gstart, gmem, G), initialises
+// the header and fills the sin/cos table: k_group_b's work, without its launch.
+constexpr int PCR_GROUPS_MAX_K = 64;
+__device__ __forceinline__ LocalGroups pcr_local_groups(const PrepView& V, int* s_mem) {
+    const int lane = threadIdx.x, K = V.K, b = blockIdx.x;
+    int m = 0, n = 0, key = INT32_MAX;
+    bool bad = false;
+    if (lane < K) {
+        const int mr = V.m[lane], nr = V.n[lane];
+        bad = mr < -256 || mr > 255 || nr < -1024 || nr > 1023;
+        m = min(max(mr, -256), 255);
+        n = min(max(nr, -1024), 1023);
+        key = ((m + 256) << 11) | (n + 1024);
+    }
+    int less = 0, eqb = 0;   // harmonics of smaller (m, n); of the same (m, n) before this one
+    for (int j = 0; j < K; ++j) {
+        const int kj = __shfl(key, j, 64);
+        less += kj < key;
+        eqb += (kj == key) & (j < lane);
+    }
+    const bool first = lane < K && eqb == 0;
+    int rank = 0;   // distinct (m, n) below this one: the group index
+    for (int j = 0; j < K; ++j) {
+        const int kj = __shfl(key, j, 64);
+        const int fj = __shfl(first ? 1 : 0, j, 64);
+        rank += fj & (kj < key);
+    }
+    LocalGroups lg{};
+    lg.on = true;
+    lg.G = __popcll(__ballot(first));
+    lg.mem = s_mem;
+    if (b == 0) {
+        Header* hdr = V.header;
+        if (first) {
+            V.gm[rank] = m;
+            V.gn[rank] = n;
+            V.gstart[rank] = less;
+        }
+        if (lane < K) V.gmem[less + eqb] = lane;
+        const bool anybad = __ballot(bad) != 0ull;
+        if (lane == 0) {
+            header_init(hdr);
+            V.gstart[lg.G] = K;
+            hdr->groups = lg.G;
+            if (anybad) hdr->bad_mn = 1;
+        }
+        for (int i = lane; i < 512; i += 64) {
+            double sv, cv;
+            sincospi((double)i / 256.0, &sv, &cv);
+            V.sctab[i] = make_double2(sv, cv);
+        }
+    }
+    const int g = b < 4 ? -1 : b < 4 + K ? b - 4 : (b - 4 - K) >> 2;
+    if (g >= 0 && g < lg.G) {
+        const unsigned long long sel = __ballot(first && rank == g);
+        const int src = __ffsll((long long)sel) - 1;
+        lg.m = __shfl(m, src, 64);
+        lg.n = __shfl(n, src, 64);
+        const int kg = __shfl(key, src, 64);
+        const bool mine = lane < K && key == kg;
+        if (mine) s_mem[eqb] = lane;
+        lg.count = __popcll(__ballot(mine));
+    }
+    __syncthreads();
+    return lg;
+}
+
+// K1-K3 with one wave per interpolant (parallel cyclic reduction): blocks [0, 4) the trajectory splines (Phi_phi,
+// Phi_r, f_phi, f_r; the f_phi and f_r blocks go on to f_phi', f_r' from their own knot
+// slopes), [4, 4 + K) the inverse splines of group h = b - 4 < G, [4 + K, 4 + 5K) the group
+// amplitude splines (interpolant q = b - 4 - K < 4G; only when PrepDesc::pcr bit 1 is set, else
+// the grid stops at 4 + K). Blocks past this waveform's G leave at once.
+// The same coefficients as k_prep_b's (scipy's construction, to rounding); for 4 <= N_t <=
+// PCR_NMAX (the host takes k_prep_b otherwise). Dynamic LDS: 9 N_t doubles.
+__global__ __launch_bounds__(64) void k_prep_pcr_b(const PrepBatch B) {
+    const PrepView V(B);
+    const int nt = V.nt, K = V.K;
+    if (!(V.pcr & 1) || (int)blockIdx.x >= 4 + ((V.pcr & 2) ? 5 : 1) * K) return;
+    __shared__ int s_mem[PCR_GROUPS_MAX_K];
+    LocalGroups lg{};
+    if (B.pcr_groups && (blockIdx.x == 0 || blockIdx.x >= 4))   // (blocks 1-3: trajectory only)
+        lg = pcr_local_groups(V, s_mem);
+    const double *t = V.t, *phi_phi = V.phi_phi, *phi_r = V.phi_r, *f_phi = V.f_phi, *f_r = V.f_r;
+    const int32_t *gm = V.gm, *gn = V.gn;
+    double *coefT = V.coefT, *kslope = V.kslope, *coefA = V.coefA;
+    double *invcp = V.invcp, *invdp = V.invdp;
+    int32_t* runs = V.runs;
+    Item* items = V.items;
+    Header* hdr = V.header;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
@@ -962,10 +1024,9 @@ __device__ __forceinline__ void prep_pcr_body(
         // component q & 3 of group q >> 2 at knot i (group_amp_at; no gamp pass)
         auto Y = [&](int i) {
             const double4 v =
-                lg.on ? group_amp_sum(ga.amp, ga.ylm_p, ga.ylm_m, ga.sc_re, ga.sc_im, lg.m != 0,
-                                      0, lg.count, [&](int p) { return lg.mem[p]; }, K, i)
-                      : group_amp_at(ga.amp, ga.ylm_p, ga.ylm_m, ga.sc_re, ga.sc_im, gm,
-                                     ga.gstart, ga.gmem, K, i, q >> 2);
+                lg.on ? group_amp_sum(V, lg.m != 0, 0, lg.count,
+                                      [&](int p) { return lg.mem[p]; }, i)
+                      : group_amp_at(V, i, q >> 2);
             const int c = q & 3;
             return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w;
         };
@@ -1058,93 +1119,6 @@ __device__ __forceinline__ void prep_pcr_body(
         }
     }
 }
-// PrepBatch::pcr_groups (every waveform of the batch on the PCR roles with K <= 64): each block
-// groups the K harmonics itself, one per lane: a harmonic's group is the rank of its (m, n) among
-// the distinct pairs, its place in gmem the count of harmonics of smaller (m, n) plus the members
-// of its own before it. The same groups, order and member lists as k_group's counting sort (the
-// same clamping and bad_mn rule). Block 0 also writes them (gm, gn, gstart, gmem, G), initialises
-// the header and fills the sin/cos table: k_group_b's work, without its launch.
-constexpr int PCR_GROUPS_MAX_K = 64;
-__device__ __forceinline__ LocalGroups pcr_local_groups(const PrepDesc& D, char* W,
-                                                        const Layout& L, int* s_mem) {
-    const int lane = threadIdx.x, K = D.K, b = blockIdx.x;
-    int m = 0, n = 0, key = INT32_MAX;
-    bool bad = false;
-    if (lane < K) {
-        const int mr = D.m[lane], nr = D.n[lane];
-        bad = mr < -256 || mr > 255 || nr < -1024 || nr > 1023;
-        m = min(max(mr, -256), 255);
-        n = min(max(nr, -1024), 1023);
-        key = ((m + 256) << 11) | (n + 1024);
-    }
-    int less = 0, eqb = 0;   // harmonics of smaller (m, n); of the same (m, n) before this one
-    for (int j = 0; j < K; ++j) {
-        const int kj = __shfl(key, j, 64);
-        less += kj < key;
-        eqb += (kj == key) & (j < lane);
-    }
-    const bool first = lane < K && eqb == 0;
-    int rank = 0;   // distinct (m, n) below this one: the group index
-    for (int j = 0; j < K; ++j) {
-        const int kj = __shfl(key, j, 64);
-        const int fj = __shfl(first ? 1 : 0, j, 64);
-        rank += fj & (kj < key);
-    }
-    LocalGroups lg{};
-    lg.on = true;
-    lg.G = __popcll(__ballot(first));
-    lg.mem = s_mem;
-    if (b == 0) {
-        Header* hdr = ws_at<Header>(W, L.header);
-        if (first) {
-            ws_at<int32_t>(W, L.gm)[rank] = m;
-            ws_at<int32_t>(W, L.gn)[rank] = n;
-            ws_at<int32_t>(W, L.gstart)[rank] = less;
-        }
-        if (lane < K) ws_at<int32_t>(W, L.gmem)[less + eqb] = lane;
-        const bool anybad = __ballot(bad) != 0ull;
-        if (lane == 0) {
-            header_init(hdr);
-            ws_at<int32_t>(W, L.gstart)[lg.G] = K;
-            hdr->groups = lg.G;
-            if (anybad) hdr->bad_mn = 1;
-        }
-        double2* sctab_g = ws_at<double2>(W, L.sctab);
-        for (int i = lane; i < 512; i += 64) {
-            double sv, cv;
-            sincospi((double)i / 256.0, &sv, &cv);
-            sctab_g[i] = make_double2(sv, cv);
-        }
-    }
-    const int g = b < 4 ? -1 : b < 4 + K ? b - 4 : (b - 4 - K) >> 2;
-    if (g >= 0 && g < lg.G) {
-        const unsigned long long sel = __ballot(first && rank == g);
-        const int src = __ffsll((long long)sel) - 1;
-        lg.m = __shfl(m, src, 64);
-        lg.n = __shfl(n, src, 64);
-        const int kg = __shfl(key, src, 64);
-        const bool mine = lane < K && key == kg;
-        if (mine) s_mem[eqb] = lane;
-        lg.count = __popcll(__ballot(mine));
-    }
-    __syncthreads();
-    return lg;
-}
-__global__ __launch_bounds__(64) void k_prep_pcr_b(const PrepBatch B) {
-    PREP_WALKER(B);
-    if (!(D.pcr & 1) || (int)blockIdx.x >= 4 + ((D.pcr & 2) ? 5 : 1) * D.K) return;
-    const GroupAmpSrc ga{D.amp, D.ylm_p, D.ylm_m, D.sc_re, D.sc_im,
-                         ws_at<int32_t>(W, L.gstart), ws_at<int32_t>(W, L.gmem)};
-    __shared__ int s_mem[PCR_GROUPS_MAX_K];
-    LocalGroups lg{};
-    if (B.pcr_groups && (blockIdx.x == 0 || blockIdx.x >= 4))   // (blocks 1-3: trajectory only)
-        lg = pcr_local_groups(D, W, L, s_mem);
-    prep_pcr_body(D.t, D.phi_phi, D.phi_r, D.f_phi, D.f_r, ga, lg, ws_at<int32_t>(W, L.gm),
-                  ws_at<int32_t>(W, L.gn), D.nt, D.K,
-                  ws_at<double>(W, L.coefT), ws_at<double>(W, L.kslope), ws_at<double>(W, L.coefA),
-                  ws_at<int32_t>(W, L.runs), ws_at<Item>(W, L.items), ws_at<double>(W, L.invcp),
-                  ws_at<double>(W, L.invdp), ws_at<Header>(W, L.header));
-}
 
 __global__ __launch_bounds__(64) void k_spline_shared(const double* __restrict__ x, int n,
                                                       const double* __restrict__ y, int ninterp,
@@ -1195,77 +1169,6 @@ __device__ int64_t grid_bound(const double* __restrict__ f, int64_t nf, double v
         if (pred(mid)) hi = mid; else lo = mid + 1;
     }
     return lo;
-}
-
-__device__ bool build_item(
-    const double* __restrict__ t, const double* __restrict__ f_phi, const double* __restrict__ f_r,
-    const int32_t* __restrict__ gm, const int32_t* __restrict__ gn, int ni, int K,
-    const double* __restrict__ coefA, const double* __restrict__ coefT,
-    const int32_t* __restrict__ runs, const double* __restrict__ freq, int64_t nf, int paired,
-    int64_t nl, int64_t nl1, Item* __restrict__ items, int4* __restrict__ ranges, int h, int j,
-    unsigned long long& evals, bool env);
-
-// K4: one thread per (group g, knot interval j). Counts both the SPA evaluations the kernel
-// makes (per group) and the reference formulation's contributions C (per (l, m, n) harmonic:
-// the group's evaluations times its member count).
-__device__ __forceinline__ void items_body(const double* __restrict__ t, const double* __restrict__ f_phi,
-                        const double* __restrict__ f_r, const int32_t* __restrict__ gm,
-                        const int32_t* __restrict__ gn, const int32_t* __restrict__ gstart,
-                        int nt, int K, const double* __restrict__ coefA,
-                        const double* __restrict__ coefT, const int32_t* __restrict__ runs,
-                        const double* __restrict__ freq, int64_t nf, int paired, int64_t nl,
-                        int64_t nl1, Item* __restrict__ items, int4* __restrict__ ranges,
-                        Header* __restrict__ hdr, bool runs_mark, bool env) {
-    const int ni = nt - 1;
-    const int G = hdr->groups;
-    // the grid is sized for K >= G groups (K / ITEMS_PER_THREAD_K threads per interval at large
-    // K): whole blocks past the records leave at once; a thread takes the records gid, gid +
-    // the grid's threads, ... (config 2: 627 groups over 377 threads an interval, one or two)
-    const int64_t total = (int64_t)ni * G;
-    if ((int64_t)blockIdx.x * blockDim.x >= total) return;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    __shared__ unsigned long long red[3][4];
-    unsigned long long ev = 0, contrib = 0, eev = 0;
-    for (int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
-         gid += stride) {
-        const int g = (int)(gid % G), j = (int)(gid / G);
-        // the PCR inverse splines' run-overflow marker (rr[3]) into the header's sticky flag
-        if (runs_mark && j == 0 && runs[(size_t)g * 4 * MAXRUNS + 3] != 0)
-            atomicOr(&hdr->runs_overflow, 1);
-        unsigned long long e1 = 0;
-        const bool envr = build_item(t, f_phi, f_r, gm, gn, ni, K, coefA, coefT, runs, freq, nf,
-                                     paired, nl, nl1, items, ranges, g, j, e1, env);
-        ev += e1;
-        contrib += e1 * (unsigned long long)(gstart[g + 1] - gstart[g]);
-        eev += envr ? e1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        ev += __shfl_xor(ev, o);
-        contrib += __shfl_xor(contrib, o);
-        eev += __shfl_xor(eev, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = contrib;
-        red[1][threadIdx.x >> 6] = ev;
-        red[2][threadIdx.x >> 6] = eev;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long c = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        const unsigned long long e = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        const unsigned long long x = red[2][0] + red[2][1] + red[2][2] + red[2][3];
-        if (c) atomicAdd((unsigned long long*)&hdr->contributions, c);
-        if (e) atomicAdd((unsigned long long*)&hdr->evaluations, e);
-        if (x) atomicAdd((unsigned long long*)&hdr->env_evaluations, x);
-    }
-}
-__global__ __launch_bounds__(256) void k_items(const PrepBatch B) {
-    PREP_WALKER(B);
-    items_body(D.t, D.f_phi, D.f_r, ws_at<int32_t>(W, L.gm), ws_at<int32_t>(W, L.gn),
-               ws_at<int32_t>(W, L.gstart), D.nt, D.K, ws_at<double>(W, L.coefA),
-               ws_at<double>(W, L.coefT), ws_at<int32_t>(W, L.runs), D.freq, B.nf, B.paired, B.nl,
-               B.nl1, ws_at<Item>(W, L.items), ws_at<int4>(W, L.ranges),
-               ws_at<Header>(W, L.header), (D.pcr & 1) != 0, D.env != 0);
 }
 
 // One interval record of group h; `evals` = its (branch x bin) evaluation count.
@@ -1330,6 +1233,9 @@ __device__ bool record_safe(const Item& it, FAT fat, int64_t lo0, int64_t hi0, i
     return fmn > 1e-12 * scale && isfinite(scale);
 }
 
+// (build_item and items_body keep their __restrict__ pointer lists: read through the view,
+// whose members cannot be __restrict__, k_items took 332 us instead of 202 us on the headline's
+// batch, with 117 VGPRs instead of 125)
 __device__ bool build_item(
     const double* __restrict__ t, const double* __restrict__ f_phi, const double* __restrict__ f_r,
     const int32_t* __restrict__ gm, const int32_t* __restrict__ gn, int ni, int K,
@@ -1502,6 +1408,67 @@ __device__ bool build_item(
     return false;
 }
 
+// K4: one thread per (group g, knot interval j). Counts both the SPA evaluations the kernel
+// makes (per group) and the reference formulation's contributions C (per (l, m, n) harmonic:
+// the group's evaluations times its member count).
+__device__ __forceinline__ void items_body(const double* __restrict__ t, const double* __restrict__ f_phi,
+                        const double* __restrict__ f_r, const int32_t* __restrict__ gm,
+                        const int32_t* __restrict__ gn, const int32_t* __restrict__ gstart,
+                        int nt, int K, const double* __restrict__ coefA,
+                        const double* __restrict__ coefT, const int32_t* __restrict__ runs,
+                        const double* __restrict__ freq, int64_t nf, int paired, int64_t nl,
+                        int64_t nl1, Item* __restrict__ items, int4* __restrict__ ranges,
+                        Header* __restrict__ hdr, bool runs_mark, bool env) {
+    const int ni = nt - 1;
+    const int G = hdr->groups;
+    // the grid is sized for K >= G groups (K / ITEMS_PER_THREAD_K threads per interval at large
+    // K): whole blocks past the records leave at once; a thread takes the records gid, gid +
+    // the grid's threads, ... (config 2: 627 groups over 377 threads an interval, one or two)
+    const int64_t total = (int64_t)ni * G;
+    if ((int64_t)blockIdx.x * blockDim.x >= total) return;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    __shared__ unsigned long long red[3][4];
+    unsigned long long ev = 0, contrib = 0, eev = 0;
+    for (int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total;
+         gid += stride) {
+        const int g = (int)(gid % G), j = (int)(gid / G);
+        // the PCR inverse splines' run-overflow marker (rr[3]) into the header's sticky flag
+        if (runs_mark && j == 0 && runs[(size_t)g * 4 * MAXRUNS + 3] != 0)
+            atomicOr(&hdr->runs_overflow, 1);
+        unsigned long long e1 = 0;
+        const bool envr = build_item(t, f_phi, f_r, gm, gn, ni, K, coefA, coefT, runs, freq, nf,
+                                     paired, nl, nl1, items, ranges, g, j, e1, env);
+        ev += e1;
+        contrib += e1 * (unsigned long long)(gstart[g + 1] - gstart[g]);
+        eev += envr ? e1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        ev += __shfl_xor(ev, o);
+        contrib += __shfl_xor(contrib, o);
+        eev += __shfl_xor(eev, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = contrib;
+        red[1][threadIdx.x >> 6] = ev;
+        red[2][threadIdx.x >> 6] = eev;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long c = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        const unsigned long long e = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        const unsigned long long x = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+        if (c) atomicAdd((unsigned long long*)&hdr->contributions, c);
+        if (e) atomicAdd((unsigned long long*)&hdr->evaluations, e);
+        if (x) atomicAdd((unsigned long long*)&hdr->env_evaluations, x);
+    }
+}
+__global__ __launch_bounds__(256) void k_items(const PrepBatch B) {
+    const PrepView V(B);
+    items_body(V.t, V.f_phi, V.f_r, V.gm, V.gn, V.gstart, V.nt, V.K, V.coefA, V.coefT, V.runs,
+               V.freq, V.nf, V.paired, V.nl, V.nl1, V.items, V.ranges, V.header,
+               (V.pcr & 1) != 0, V.env != 0);
+}
+
 // ----------------------------------------------------------------------------------------
 // K5: segment table. A segment is (group, monotonic run, sub-branch s) with a non-empty lane
 // range; its interval records are consecutive (h * ni + j, j in [ja, jb)) and, walked in lane
@@ -1512,19 +1479,20 @@ __device__ bool build_item(
 // seglh = (lo, hi) lane range; seginfo = (first record, count, dir, s).
 // ----------------------------------------------------------------------------------------
 // The segment of slot i = (group h, run r, sub-branch sb): its lane range lh and (first record,
-// count, dir, s) info, or info.y == 0 when the slot holds none. G = the call's group count.
-__device__ __forceinline__ void slot_segment(int i, const int32_t* __restrict__ runs,
-                                             const int4* __restrict__ ranges, int nt, int G,
-                                             int lim0, int lim1, int2& lh, int4& info) {
+// count, dir, s) info, or info.y == 0 when the slot holds none. G = the call's group count;
+// ranges: V.ranges, or k_segments_one's copy of it in LDS.
+__device__ __forceinline__ void slot_segment(const PrepView& V, int i,
+                                             const int4* __restrict__ ranges, int G, int2& lh,
+                                             int4& info) {
     const int h = i / (2 * MAXRUNS), r = (i >> 1) % MAXRUNS, sb = i & 1;
-    const int ni = nt - 1;
+    const int ni = V.nt - 1;
     lh = make_int2(0, 0);
     info = make_int4(0, 0, 0, 0);
-    const int32_t* rr = runs + (size_t)h * 4 * MAXRUNS + 4 * r;
+    const int32_t* rr = V.runs + (size_t)h * 4 * MAXRUNS + 4 * r;
     if (h < G && rr[2] != 0) {
         const int ja = rr[0], jb = rr[1], n = jb - ja;
         const int dir = (sb == 0) ? -rr[2] : rr[2];   // s = 0 walks g downward in lane order
-        const int lim = sb ? lim1 : lim0;
+        const int lim = V.seg_lim(sb);
         const int4* rg = ranges + (size_t)h * ni;
         // Records whose branch lies outside the lane range are empty and clamped to its
         // ends (lane 0 or lim); they sit at the two ends of the segment in lane order and
@@ -1555,25 +1523,21 @@ __device__ __forceinline__ void slot_segment(int i, const int32_t* __restrict__ 
         }
     }
 }
-__device__ __forceinline__ void segment_slots_body(const int32_t* __restrict__ runs,
-                                                       const int4* __restrict__ ranges, int nt,
-                                                       int K, int lim0, int lim1,
-                                                       const Header* __restrict__ hdr,
-                                                       int2* __restrict__ slot_lh,
-                                                       int4* __restrict__ slot_info,
-                                                       int32_t* __restrict__ blockcnt,
-                                                       int32_t* __restrict__ blocktiles) {
+// slot blocks of one waveform: (2 MAXRUNS K + 255) / 256; the grid has the batch's largest count
+__device__ __forceinline__ int slot_blocks(int K) { return (2 * MAXRUNS * K + 255) / 256; }
+__global__ __launch_bounds__(256) void k_segment_slots(const PrepBatch B) {
+    const PrepView V(B);
+    if ((int)blockIdx.x >= slot_blocks(V.K)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ int wc[4], wt[4];
     int ntl = 0;   // tiles the slot's segment covers
     bool valid = false;
-    if (i < K * MAXRUNS * 2) {
-        const int G = hdr->groups;
+    if (i < V.K * MAXRUNS * 2) {
         int2 lh;
         int4 info;
-        slot_segment(i, runs, ranges, nt, G, lim0, lim1, lh, info);
-        slot_lh[i] = lh;
-        slot_info[i] = info;
+        slot_segment(V, i, V.ranges, V.header->groups, lh, info);
+        V.slotlh[i] = lh;
+        V.slotinfo[i] = info;
         valid = info.y > 0;
         if (valid) ntl = (lh.y - 1) / TILE_LANES - lh.x / TILE_LANES + 1;
     }
@@ -1586,33 +1550,17 @@ __device__ __forceinline__ void segment_slots_body(const int32_t* __restrict__ r
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        blockcnt[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
-        blocktiles[blockIdx.x] = wt[0] + wt[1] + wt[2] + wt[3];
+        V.slotcnt[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+        V.slottiles[blockIdx.x] = wt[0] + wt[1] + wt[2] + wt[3];
     }
-}
-// slot blocks of one waveform: (2 MAXRUNS K + 255) / 256; the grid has the batch's largest count
-__device__ __forceinline__ int slot_blocks(int K) { return (2 * MAXRUNS * K + 255) / 256; }
-__global__ __launch_bounds__(256) void k_segment_slots(const PrepBatch B) {
-    PREP_WALKER(B);
-    if ((int)blockIdx.x >= slot_blocks(D.K)) return;
-    segment_slots_body(ws_at<int32_t>(W, L.runs), ws_at<int4>(W, L.ranges), D.nt, D.K,
-                       (int)(B.paired ? B.nl : B.nf), (int)(B.paired ? B.nl1 : B.nf),
-                       ws_at<Header>(W, L.header), ws_at<int2>(W, L.slotlh),
-                       ws_at<int4>(W, L.slotinfo), ws_at<int32_t>(W, L.slotcnt),
-                       ws_at<int32_t>(W, L.slottiles));
 }
 
 // one workgroup per slot block: its output offset is the sum of the earlier blocks' counts
-__device__ __forceinline__ void segment_compact_body(const int2* __restrict__ slot_lh,
-                                                         const int4* __restrict__ slot_info,
-                                                         const int32_t* __restrict__ blockcnt,
-                                                         const int32_t* __restrict__ blocktiles,
-                                                         int nslot, int64_t stbcap,
-                                                         int2* __restrict__ seglh,
-                                                         int4* __restrict__ seginfo,
-                                                         int32_t* __restrict__ segbase,
-                                                         int32_t* __restrict__ nseg, int nblk,
-                                                         Header* __restrict__ hdr) {
+__global__ __launch_bounds__(256) void k_segment_compact(const PrepBatch B) {
+    const PrepView V(B);
+    const int nblk = slot_blocks(V.K), nslot = 2 * MAXRUNS * V.K;
+    if ((int)blockIdx.x >= nblk) return;
+    Header* hdr = V.header;
     __shared__ int wc[4];
     __shared__ int64_t wt[4];
     __shared__ int2 wr[4];
@@ -1620,7 +1568,7 @@ __device__ __forceinline__ void segment_compact_body(const int2* __restrict__ sl
     const int blk = blockIdx.x;
     int before = 0;
     int64_t tbefore = 0;
-    for (int b = tid; b < blk; b += 256) { before += blockcnt[b]; tbefore += blocktiles[b]; }
+    for (int b = tid; b < blk; b += 256) { before += V.slotcnt[b]; tbefore += V.slottiles[b]; }
     for (int o = 32; o > 0; o >>= 1) {
         before += __shfl_xor(before, o);
         tbefore += __shfl_xor(tbefore, o);
@@ -1633,7 +1581,7 @@ __device__ __forceinline__ void segment_compact_body(const int2* __restrict__ sl
     const int i = blk * 256 + tid;
     int4 info = make_int4(0, 0, 0, 0);
     int2 lh = make_int2(0, 0);
-    if (i < nslot) { info = slot_info[i]; lh = slot_lh[i]; }
+    if (i < nslot) { info = V.slotinfo[i]; lh = V.slotlh[i]; }
     const bool valid = info.y > 0;
     const int ntl = valid ? (lh.y - 1) / TILE_LANES - lh.x / TILE_LANES + 1 : 0;
     // exclusive scan of the tile counts over the block's slots (slot order). Not block_excl_scan:
@@ -1652,12 +1600,12 @@ __device__ __forceinline__ void segment_compact_body(const int2* __restrict__ sl
     for (int w = 0; w < wave; ++w) { pos += wc[w]; toff += wt[w]; }
     pos += __popcll(bal & ((1ull << lane) - 1ull));
     if (valid) {
-        seglh[pos] = lh;
-        seginfo[pos] = info;
-        segbase[pos] = (toff + ntl <= stbcap) ? (int32_t)(toff - lh.x / TILE_LANES)
-                                                         : SEG_NO_STB;
+        V.seglh[pos] = lh;
+        V.seginfo[pos] = info;
+        V.segbase[pos] = (toff + ntl <= V.stbcap) ? (int32_t)(toff - lh.x / TILE_LANES)
+                                                  : SEG_NO_STB;
     }
-    if (blk == nblk - 1 && tid == 0) *nseg = base + wc[0] + wc[1] + wc[2] + wc[3];
+    if (blk == nblk - 1 && tid == 0) *V.nseg = base + wc[0] + wc[1] + wc[2] + wc[3];
     // the union of the block's segment lane ranges into the header: k_modesum's tiles outside
     // it skip the list build (one block-wide min / max, two global atomics per block)
     int lo = valid ? lh.x : INT32_MAX, hi = valid ? lh.y : INT32_MIN;
@@ -1674,16 +1622,6 @@ __device__ __forceinline__ void segment_compact_body(const int2* __restrict__ sl
             atomicMax(&hdr->lane_hi, hi);
         }
     }
-}
-__global__ __launch_bounds__(256) void k_segment_compact(const PrepBatch B) {
-    PREP_WALKER(B);
-    const int nblk = slot_blocks(D.K);
-    if ((int)blockIdx.x >= nblk) return;
-    segment_compact_body(ws_at<int2>(W, L.slotlh), ws_at<int4>(W, L.slotinfo),
-                         ws_at<int32_t>(W, L.slotcnt), ws_at<int32_t>(W, L.slottiles),
-                         2 * MAXRUNS * D.K, L.stbcap, ws_at<int2>(W, L.seglh),
-                         ws_at<int4>(W, L.seginfo), ws_at<int32_t>(W, L.segbase),
-                         ws_at<int32_t>(W, L.nseg), nblk, ws_at<Header>(W, L.header));
 }
 
 // One workgroup per segment (grid-stride): for every record p of the segment in lane order
@@ -1714,28 +1652,17 @@ __device__ __forceinline__ void seg_tiles_record(const int4* __restrict__ ranges
     b = p < n ? div_floor_nn(cur.x) - 1 : t1;
     for (int t = max(a, t0); t <= min(b, t1); ++t) stb1[sbase + t] = p;
 }
-__device__ __forceinline__ void seg_tiles_body(const int4* __restrict__ ranges,
-                                                   const int2* __restrict__ seglh,
-                                                   const int4* __restrict__ seginfo,
-                                                   const int32_t* __restrict__ segbase,
-                                                   const int32_t* __restrict__ nsegp,
-                                                   int32_t* __restrict__ stb0,
-                                                   int32_t* __restrict__ stb1) {
-    const int nseg = *nsegp;
-    for (int sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
-        const int32_t sbase = segbase[sg];
-        if (sbase == SEG_NO_STB) continue;
-        const int2 lh = seglh[sg];
-        const int4 info = seginfo[sg];
-        for (int p = threadIdx.x; p <= info.y; p += blockDim.x)
-            seg_tiles_record(ranges, lh, info, sbase, p, stb0, stb1);
-    }
-}
 __global__ __launch_bounds__(256) void k_seg_tiles(const PrepBatch B) {
-    PREP_WALKER(B);
-    seg_tiles_body(ws_at<int4>(W, L.ranges), ws_at<int2>(W, L.seglh), ws_at<int4>(W, L.seginfo),
-                   ws_at<int32_t>(W, L.segbase), ws_at<int32_t>(W, L.nseg),
-                   ws_at<int32_t>(W, L.stb0), ws_at<int32_t>(W, L.stb1));
+    const PrepView V(B);
+    const int nseg = *V.nseg;
+    for (int sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
+        const int32_t sbase = V.segbase[sg];
+        if (sbase == SEG_NO_STB) continue;
+        const int2 lh = V.seglh[sg];
+        const int4 info = V.seginfo[sg];
+        for (int p = threadIdx.x; p <= info.y; p += blockDim.x)
+            seg_tiles_record(V.ranges, lh, info, sbase, p, V.stb0, V.stb1);
+    }
 }
 
 // K5 in one workgroup per waveform when its 2 MAXRUNS K slots fit one (K <= 64: the walker
@@ -1746,7 +1673,7 @@ __global__ __launch_bounds__(256) void k_seg_tiles(const PrepBatch B) {
 // one launch instead of three.
 constexpr int64_t SEG1_LDS_CAP = 40 * 1024;   // bytes of staged ranges (+ 33 KB static LDS)
 __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
-    PREP_WALKER(B);
+    const PrepView V(B);
     constexpr int NW = SEG1_NT / 64;
     __shared__ int wsum[NW];
     __shared__ int2 wr[NW];
@@ -1754,15 +1681,15 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     __shared__ int4 s_info[SEG1_NT];
     __shared__ int32_t s_base[SEG1_NT];
     __shared__ int32_t s_roff[SEG1_NT];
-    Header* hdr = ws_at<Header>(W, L.header);
+    Header* hdr = V.header;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nslot = 2 * MAXRUNS * D.K;   // <= SEG1_NT (host: every waveform has K <= SEG1_MAX_K)
+    const int nslot = 2 * MAXRUNS * V.K;   // <= SEG1_NT (host: every waveform has K <= SEG1_MAX_K)
     // the interval records' lane ranges staged in LDS when they fit (one coalesced pass): the
     // slots' bisections and the tile pairs then read LDS instead of chains of global loads
     extern __shared__ int4 s_rg[];
-    const int ni = D.nt - 1;
-    const int4* ranges = ws_at<int4>(W, L.ranges);
-    if ((int64_t)D.K * ni * (int64_t)sizeof(int4) <= (int64_t)B.seg_lds) {
+    const int ni = V.nt - 1;
+    const int4* ranges = V.ranges;
+    if ((int64_t)V.K * ni * (int64_t)sizeof(int4) <= (int64_t)B.seg_lds) {
         const int nrec = hdr->groups * ni;
         for (int i = tid; i < nrec; i += SEG1_NT) s_rg[i] = ranges[i];
         __syncthreads();
@@ -1771,8 +1698,7 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     int2 lh = make_int2(0, 0);
     int4 info = make_int4(0, 0, 0, 0);
     if (tid < nslot)
-        slot_segment(tid, ws_at<int32_t>(W, L.runs), ranges, D.nt, hdr->groups,
-                     (int)(B.paired ? B.nl : B.nf), (int)(B.paired ? B.nl1 : B.nf), lh, info);
+        slot_segment(V, tid, ranges, hdr->groups, lh, info);
     const bool valid = info.y > 0;
     const int ntl = valid ? (lh.y - 1) / TILE_LANES - lh.x / TILE_LANES + 1 : 0;
     // (a barrier after each block scan frees wsum for the next)
@@ -1783,11 +1709,11 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     __syncthreads();
     int32_t sbase = SEG_NO_STB;
     if (valid) {
-        sbase = ((int64_t)toff + ntl <= L.stbcap) ? (int32_t)(toff - lh.x / TILE_LANES)
+        sbase = ((int64_t)toff + ntl <= V.stbcap) ? (int32_t)(toff - lh.x / TILE_LANES)
                                                   : SEG_NO_STB;
-        ws_at<int2>(W, L.seglh)[pos] = lh;
-        ws_at<int4>(W, L.seginfo)[pos] = info;
-        ws_at<int32_t>(W, L.segbase)[pos] = sbase;
+        V.seglh[pos] = lh;
+        V.seginfo[pos] = info;
+        V.segbase[pos] = sbase;
         s_lh[pos] = lh;
         s_info[pos] = info;
         s_base[pos] = sbase;
@@ -1811,10 +1737,8 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
             hdr->lane_lo = lo;
             hdr->lane_hi = hi;
         }
-        *ws_at<int32_t>(W, L.nseg) = nseg;
+        *V.nseg = nseg;
     }
-    int32_t* stb0 = ws_at<int32_t>(W, L.stb0);
-    int32_t* stb1 = ws_at<int32_t>(W, L.stb1);
     // the sparse sum's split plan (paired grids, i.e. the fused likelihood): every union tile's
     // cost in wave-records, from the same (segment, record) pairs. Possible when the union fits
     // SPLIT_UNION_CAP tiles and every segment has its tile pairs (else nitems stays -1)
@@ -1836,7 +1760,7 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
             if (s_roff[mid] <= f) a = mid; else b = mid - 1;
         }
         const int p = f - s_roff[a];
-        seg_tiles_record(ranges, s_lh[a], s_info[a], s_base[a], p, stb0, stb1);
+        seg_tiles_record(ranges, s_lh[a], s_info[a], s_base[a], p, V.stb0, V.stb1);
         if (plan && p < s_info[a].y) {
             // record p's cost per tile it reaches: the 64 BPL-lane wave chunks it touches there
             // (modesum_tile evaluates a record on every wave whose bins it reaches)
@@ -1890,8 +1814,8 @@ __global__ __launch_bounds__(SEG1_NT) void k_segments_one(const PrepBatch B) {
     __syncthreads();
     if (n_split == 0 || n_items > SPLIT_ITEM_CAP || n_split > SPLIT_TILE_CAP)
         return;   // nothing to split, or past the plan's capacity: the plain tile loop
-    int4* items = ws_at<int4>(W, L.sitem);
-    int32_t* cnt = ws_at<int32_t>(W, L.scnt);
+    int4* items = V.sitem;
+    int32_t* cnt = V.scnt;
     int ii = io, sp = po;
     for (int i = 0; i < PER; ++i) {
         const int u = tid * PER + i, S = nS[i];
@@ -1932,120 +1856,106 @@ static bool env_records() {
     return v;
 }
 
-// Preparation (K0-K6) of `count` waveforms in one chain of launches; blockIdx.z = waveform.
-// efd_modesum_prepare and efd_modesum's first phase are a batch of one.
-int efdhip::prepare_batch(const char* fn, const efd_modesum_args* const* a,
-                          void* const* workspace, const size_t* workspace_bytes, int32_t count,
-                          void* stream) {
-    const std::string F(fn);
-    if (!a || !workspace || !workspace_bytes) return fail(EFD_ERR_ARG, F + ": NULL argument");
-    if (count < 1 || count > EFD_BATCH_MAX)
-        return fail(EFD_ERR_ARG, F + ": count out of range [1, EFD_BATCH_MAX]");
-    PrepBatch B{};
-    B.n = count;
+// Waveform i of a batch, checked: its arguments, its workspace's size against its own layout L,
+// and its descriptor d, with the switches (lists, pcr, env) that follow from its own (N_t, K).
+// F names the caller in the error strings.
+static int fill_desc(const std::string& F, const efd_modesum_args* const* a,
+                     void* const* workspace, const size_t* workspace_bytes, int i, PrepDesc& d,
+                     Layout& L) {
+    const efd_modesum_args* ai = a[i];
+    const int rc = efdhip::check_modesum_args(ai, workspace[i], 1);
+    if (rc != EFD_OK) return rc;
+    if (ai->nf != a[0]->nf || (ai->grid_symmetric != 0) != (a[0]->grid_symmetric != 0))
+        return fail(EFD_ERR_ARG, F + ": nf and grid_symmetric must agree across the batch");
+    L = make_layout(ai->nt, ai->K, ai->nf, ai->grid_symmetric ? 1 : 0);
+    if (workspace_bytes[i] < L.total)
+        return fail(EFD_ERR_WORKSPACE, F + ": workspace too small (see "
+                                           "efd_modesum_workspace_bytes)");
+    for (int j = 0; j < i; ++j)
+        if (workspace[j] == workspace[i])
+            return fail(EFD_ERR_ARG, F + ": one workspace per waveform");
+    d.t = ai->t; d.phi_phi = ai->phi_phi; d.phi_r = ai->phi_r; d.f_phi = ai->f_phi;
+    d.f_r = ai->f_r; d.amp = ai->amp; d.ylm_p = ai->ylm_p; d.ylm_m = ai->ylm_m;
+    d.freq = ai->freq; d.m = ai->m; d.n = ai->n;
+    d.ws = (char*)workspace[i];
+    d.sc_re = ai->scale_re; d.sc_im = ai->scale_im;
+    d.nt = ai->nt; d.K = ai->K;
+    d.lists = efdhip::list_mode(ai->K, L.ntiles);
+    d.env = (ai->caustic == EFD_CAUSTIC_UNIFORM && env_records()) ? 1 : 0;
+#ifdef EFD_EXP_NO_PCR   // experiment: every waveform on the Thomas kernels (the twin's solve order)
+    const bool pcr = false;
+#else
+    const bool pcr = ai->nt >= 4 && ai->nt <= PCR_NMAX;
+#endif
+    d.pcr = pcr ? (ai->K < PCR_MAX_K ? 3 : 1) : 0;
+    return EFD_OK;
+}
+
+// The launch shape of a batch: the maxima its grids and dynamic LDS are sized for, and which
+// kernels any of its waveforms needs
+struct PrepShape {
     int ntmax = 0, Kmax = 0, ntmax_pcr = 0, pcr_blocks = 0;
-    bool any_pcr = false, any_thomas = false;
-    int64_t items_max = 0, ntiles = 0;
-    bool any_lists = false, any_order = false;
-    for (int i = 0; i < count; ++i) {
-        const efd_modesum_args* ai = a[i];
-        const int rc = efdhip::check_modesum_args(ai, workspace[i], 1);
-        if (rc != EFD_OK) return rc;
-        if (ai->nf != a[0]->nf || (ai->grid_symmetric != 0) != (a[0]->grid_symmetric != 0))
-            return fail(EFD_ERR_ARG, F + ": nf and grid_symmetric must agree across the batch");
-        const int paired = ai->grid_symmetric ? 1 : 0;
-        const Layout L = make_layout(ai->nt, ai->K, ai->nf, paired);
-        if (workspace_bytes[i] < L.total)
-            return fail(EFD_ERR_WORKSPACE, F + ": workspace too small (see "
-                                               "efd_modesum_workspace_bytes)");
-        for (int j = 0; j < i; ++j)
-            if (workspace[j] == workspace[i])
-                return fail(EFD_ERR_ARG, F + ": one workspace per waveform");
-        PrepDesc& d = B.d[i];
-        d.t = ai->t; d.phi_phi = ai->phi_phi; d.phi_r = ai->phi_r; d.f_phi = ai->f_phi;
-        d.f_r = ai->f_r; d.amp = ai->amp; d.ylm_p = ai->ylm_p; d.ylm_m = ai->ylm_m;
-        d.freq = ai->freq; d.m = ai->m; d.n = ai->n;
-        d.ws = (char*)workspace[i];
-        d.sc_re = ai->scale_re; d.sc_im = ai->scale_im;
-        d.nt = ai->nt; d.K = ai->K;
-        d.lists = efdhip::list_mode(ai->K, L.ntiles);
-        d.env = (ai->caustic == EFD_CAUSTIC_UNIFORM && env_records()) ? 1 : 0;
+    int64_t items_max = 0, seg_lds = 0;
+    bool any_pcr = false, any_thomas = false, any_lists = false, any_order = false;
+    void add(const PrepDesc& d) {
         any_lists |= d.lists != 0;
         any_order |= d.lists == 3;
-#ifdef EFD_EXP_NO_PCR   // experiment: every waveform on the Thomas kernels (the twin's solve order)
-        const bool pcr = false;
-#else
-        const bool pcr = ai->nt >= 4 && ai->nt <= PCR_NMAX;
-#endif
-        d.pcr = pcr ? (ai->K < PCR_MAX_K ? 3 : 1) : 0;
-        if (pcr) {
+        if (d.pcr) {
             any_pcr = true;
-            ntmax_pcr = std::max(ntmax_pcr, ai->nt);
-            pcr_blocks = std::max(pcr_blocks, 4 + (d.pcr == 3 ? 5 : 1) * ai->K);
+            ntmax_pcr = std::max(ntmax_pcr, d.nt);
+            pcr_blocks = std::max(pcr_blocks, 4 + (d.pcr == 3 ? 5 : 1) * d.K);
         }
         if (d.pcr != 3) any_thomas = true;
-        ntmax = std::max(ntmax, ai->nt);
-        Kmax = std::max(Kmax, ai->K);
+        ntmax = std::max(ntmax, d.nt);
+        Kmax = std::max(Kmax, d.K);
         // (G <= K groups; at large K each thread may take several records: config 2's 3,020
         // harmonics form 627 groups, so a K-sized grid was 79% workgroups that exit at once)
-        const int64_t per = ai->K >= ITEMS_SPLIT_K ? ITEMS_PER_THREAD_K : 1;
-        items_max = std::max(items_max, ((int64_t)(ai->nt - 1) * ai->K + per - 1) / per);
-        if (i == 0) {
-            B.paired = paired;
-            B.nf = ai->nf;
-            B.nl = L.nlanes;
-            B.nl1 = paired ? ((ai->nf % 2) ? L.nlanes - 1 : L.nlanes) : ai->nf;
-            ntiles = L.ntiles;
-        }
+        const int64_t per = d.K >= ITEMS_SPLIT_K ? ITEMS_PER_THREAD_K : 1;
+        items_max = std::max(items_max, ((int64_t)(d.nt - 1) * d.K + per - 1) / per);
+        // k_segments_one: the largest ranges table that fits SEG1_LDS_CAP (K N_t int4s at most)
+        const int64_t b = (int64_t)d.K * (d.nt - 1) * 16;
+        if (b <= SEG1_LDS_CAP) seg_lds = std::max(seg_lds, b);
     }
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned nz = (unsigned)count;
+};
+
+// K0-K6 for the batch B of shape S on a grid of ntiles tiles
+static int launch_chain(PrepBatch& B, const PrepShape& S, int64_t ntiles, hipStream_t st) {
+    const unsigned nz = (unsigned)B.n;
+    const int Kmax = S.Kmax;
     // K0: (m, n) groups (in k_prep_pcr_b's blocks when the batch allows) and, for the Thomas
     // kernel's amplitude role, their amplitudes at the knots (the PCR amplitude waves evaluate
     // their own)
-    B.pcr_groups = (!any_thomas && Kmax <= PCR_GROUPS_MAX_K) ? 1 : 0;
-    {
-        if (!B.pcr_groups) {
-            hipLaunchKernelGGL(k_group_b, dim3(1, 1, nz), dim3(256), 0, st, B);
-            HIP_TRY(hipGetLastError());
-        }
-        if (any_thomas) {
-            const int gper = Kmax >= ITEMS_SPLIT_K ? ITEMS_PER_THREAD_K : 1;
-            hipLaunchKernelGGL(k_group_amp_b, dim3((Kmax / gper + 255) / 256, ntmax, nz),
-                               dim3(256), 0, st, B);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    // K1-K3: trajectory splines, group amplitude splines, inverse splines (one fused launch;
-    // grids sized for G = K, blocks past the device-side G return at once)
-    {
-        if (any_pcr) {   // one wave per interpolant, parallel cyclic reduction (prep_pcr_body)
-            hipLaunchKernelGGL(k_prep_pcr_b, dim3(pcr_blocks, 1, nz), dim3(64),
-                               sizeof(double) * 9 * ntmax_pcr, st, B);
-            HIP_TRY(hipGetLastError());
-        }
-        if (any_thomas) {
-            const int nb = 1 + (4 * Kmax + 63) / 64 + (Kmax + 63) / 64;
-            hipLaunchKernelGGL(k_prep_b, dim3(nb, 1, nz), dim3(64), sizeof(double) * 7 * ntmax,
-                               st, B);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    // K4: interval records
-    {
-        const int64_t blocks = (items_max + 255) / 256;
-        hipLaunchKernelGGL(k_items, dim3((unsigned)blocks, 1, nz), dim3(256), 0, st, B);
+    B.pcr_groups = (!S.any_thomas && Kmax <= PCR_GROUPS_MAX_K) ? 1 : 0;
+    if (!B.pcr_groups) {
+        hipLaunchKernelGGL(k_group_b, dim3(1, 1, nz), dim3(256), 0, st, B);
         HIP_TRY(hipGetLastError());
     }
+    if (S.any_thomas) {
+        const int gper = Kmax >= ITEMS_SPLIT_K ? ITEMS_PER_THREAD_K : 1;
+        hipLaunchKernelGGL(k_group_amp_b, dim3((Kmax / gper + 255) / 256, S.ntmax, nz),
+                           dim3(256), 0, st, B);
+        HIP_TRY(hipGetLastError());
+    }
+    // K1-K3: trajectory splines, group amplitude splines, inverse splines (grids sized for
+    // G = K, blocks past the device-side G return at once)
+    if (S.any_pcr) {   // one wave per interpolant, parallel cyclic reduction
+        hipLaunchKernelGGL(k_prep_pcr_b, dim3(S.pcr_blocks, 1, nz), dim3(64),
+                           sizeof(double) * 9 * S.ntmax_pcr, st, B);
+        HIP_TRY(hipGetLastError());
+    }
+    if (S.any_thomas) {
+        const int nb = 1 + (4 * Kmax + 63) / 64 + (Kmax + 63) / 64;
+        hipLaunchKernelGGL(k_prep_b, dim3(nb, 1, nz), dim3(64), sizeof(double) * 7 * S.ntmax,
+                           st, B);
+        HIP_TRY(hipGetLastError());
+    }
+    // K4: interval records
+    hipLaunchKernelGGL(k_items, dim3((unsigned)((S.items_max + 255) / 256), 1, nz), dim3(256), 0,
+                       st, B);
+    HIP_TRY(hipGetLastError());
     // K5: segment table
     if (Kmax <= SEG1_MAX_K) {
-        // the largest ranges table of the batch that fits SEG1_LDS_CAP (K N_t int4s at most)
-        int64_t need = 0;
-        for (int i = 0; i < count; ++i) {
-            const int64_t b = (int64_t)a[i]->K * (a[i]->nt - 1) * 16;
-            if (b <= SEG1_LDS_CAP) need = std::max(need, b);
-        }
-        B.seg_lds = (int32_t)need;
+        B.seg_lds = (int32_t)S.seg_lds;
         B.split_min = split_min_cost();
         hipLaunchKernelGGL(k_segments_one, dim3(1, 1, nz), dim3(SEG1_NT), (size_t)B.seg_lds, st,
                            B);
@@ -2064,36 +1974,61 @@ int efdhip::prepare_batch(const char* fn, const efd_modesum_args* const* a,
     // K6: the tiles' record lists (k_tile_keys, with the sum in emrifd.hip): moves the
     // latency-bound build out of the mode sum into the preparation phase, which overlaps the
     // previous waveform's sum in a two-stream pipeline
-    return efdhip::launch_tile_lists(&B, ntiles, any_lists, any_order, st);
+    return efdhip::launch_tile_lists(&B, ntiles, S.any_lists, S.any_order, st);
 }
 
-// The TD sum's preparation: k_group, k_group_amp and k_prep on one waveform's own arguments
+// Preparation (K0-K6) of `count` waveforms in one chain of launches; blockIdx.z = waveform.
+// efd_modesum_prepare and efd_modesum's first phase are a batch of one.
+int efdhip::prepare_batch(const char* fn, const efd_modesum_args* const* a,
+                          void* const* workspace, const size_t* workspace_bytes, int32_t count,
+                          void* stream) {
+    const std::string F(fn);
+    if (!a || !workspace || !workspace_bytes) return fail(EFD_ERR_ARG, F + ": NULL argument");
+    if (count < 1 || count > EFD_BATCH_MAX)
+        return fail(EFD_ERR_ARG, F + ": count out of range [1, EFD_BATCH_MAX]");
+    PrepBatch B{};
+    B.n = count;
+    PrepShape S;
+    int64_t ntiles = 0;
+    for (int i = 0; i < count; ++i) {
+        Layout L;
+        const int rc = fill_desc(F, a, workspace, workspace_bytes, i, B.d[i], L);
+        if (rc != EFD_OK) return rc;
+        S.add(B.d[i]);
+        if (i == 0) {   // the grid, which the batch shares
+            B.paired = a[0]->grid_symmetric ? 1 : 0;
+            B.nf = a[0]->nf;
+            B.nl = L.nlanes;
+            B.nl1 = B.paired ? ((B.nf % 2) ? L.nlanes - 1 : L.nlanes) : B.nf;
+            ntiles = L.ntiles;
+        }
+    }
+    return launch_chain(B, S, ntiles, (hipStream_t)stream);
+}
+
+// The TD sum's preparation: a batch of one on the TD workspace (B.td) through k_group_b,
+// k_group_amp_b and k_prep_b with every role on Thomas (pcr = 0), on the grids of one waveform
 int efdhip::td_prepare(const efd_td_args* a, void* workspace, hipStream_t st) {
-    const TdLayout L = make_td_layout(a->nt, a->K);
-    char* ws = (char*)workspace;
-    Header* hdr = (Header*)(ws + L.header);
-    int32_t* gm = (int32_t*)(ws + L.gm);
-    int32_t* gn = (int32_t*)(ws + L.gn);
-    int32_t* gstart = (int32_t*)(ws + L.gstart);
-    int32_t* gmem = (int32_t*)(ws + L.gmem);
-    double* gamp = (double*)(ws + L.gamp);
+    PrepBatch B{};
+    B.n = 1;
+    B.td = 1;
+    PrepDesc& d = B.d[0];
+    d.t = a->t; d.phi_phi = a->phi_phi; d.phi_r = a->phi_r; d.f_phi = a->f_phi; d.f_r = a->f_r;
+    d.amp = a->amp; d.ylm_p = a->ylm_p; d.ylm_m = a->ylm_m; d.m = a->m; d.n = a->n;
+    d.ws = (char*)workspace;
+    d.sc_re = a->scale_re; d.sc_im = a->scale_im;
+    d.nt = a->nt; d.K = a->K;
     const int nt = a->nt, K = a->K;
 
-    HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(Header), st));
-    hipLaunchKernelGGL(k_group, dim3(1), dim3(256), 0, st, a->m, a->n, K, gm, gn, gstart, gmem,
-                       hdr, (double2*)nullptr, (unsigned long long*)(ws + L.gkeys));
+    HIP_TRY(hipMemsetAsync(d.ws + make_td_layout(nt, K).header, 0, sizeof(Header), st));
+    hipLaunchKernelGGL(k_group_b, dim3(1), dim3(256), 0, st, B);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_group_amp, dim3((K + 255) / 256, nt), dim3(256), 0, st, a->amp, a->ylm_p,
-                       a->ylm_m, a->scale_re, a->scale_im, gm, gstart, gmem, nt, K, hdr, gamp);
+    hipLaunchKernelGGL(k_group_amp_b, dim3((K + 255) / 256, nt), dim3(256), 0, st, B);
     HIP_TRY(hipGetLastError());
-    // k_prep's first two roles only (trajectory splines, group amplitude splines): the grid
+    // k_prep_b's first two roles only (trajectory splines, group amplitude splines): the grid
     // stops before the inverse-spline blocks, which the TD sum does not need
     const int nb_amp = (4 * K + 63) / 64;
-    hipLaunchKernelGGL(k_prep, dim3(1 + nb_amp), dim3(64), sizeof(double) * 7 * nt, st, a->t,
-                       a->phi_phi, a->phi_r, a->f_phi, a->f_r, gamp, gm, gn, nt, K, nb_amp,
-                       (double*)(ws + L.coefT), (double*)(ws + L.kslope),
-                       (double*)(ws + L.tscratch), (double*)(ws + L.coefA), (int32_t*)nullptr,
-                       (Item*)nullptr, (double*)nullptr, (double*)nullptr, hdr);
+    hipLaunchKernelGGL(k_prep_b, dim3(1 + nb_amp), dim3(64), sizeof(double) * 7 * nt, st, B);
     HIP_TRY(hipGetLastError());
     return EFD_OK;
 }

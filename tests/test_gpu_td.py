@@ -64,6 +64,38 @@ def test_td_single_and_sparse_harmonics():
         assert _relerr(h, _ref(d, ns)) < RTOL, modes
 
 
+def _check_td(d, ns):
+    h = TDEngine().run(_inp(d), d["dt"], ns, scale=d["prefactor"]).cpu().numpy()
+    R = _ref(d, ns)
+    assert np.all(np.isfinite(R)) and np.abs(R).max() > 0
+    err = _relerr(h, R)
+    print(f"K={len(d['m'])} nt={len(d['t'])} ns={ns}: relerr {err:.3e}")
+    assert err < RTOL
+    nv = td_oracle.valid_samples(d["t"][-1], d["dt"], ns)
+    assert nv > 0 and np.all(h[nv:] == 0)
+    return nv
+
+
+@pytest.mark.parametrize("nk", [2, 3, 4])
+def test_td_short_trajectories(multimode, nk):
+    # the closed-form splines (2 and 3 knots) and the shortest Thomas solve (4) of the TD sum's
+    # preparation, which shares the batched chain's kernels
+    d = dict(multimode)
+    for k in ("t", "phi_phi", "phi_r", "f_phi", "f_r"):
+        d[k] = d[k][:nk].copy()
+    d["amp"] = d["amp"][:, :nk].copy()
+    ns = int(d["t"][-1] / d["dt"]) + 50   # about 50 samples past the last knot
+    assert ns - _check_td(d, ns) >= 48
+
+
+def test_td_many_harmonics():
+    # K >= 1024: the harmonic count at which the batched chain changes its grids (the TD sum's
+    # preparation keeps its own), many (m, n) groups over several blocks of the spline kernel
+    d = source_inputs(M=3e5, mu=10.0, e0=0.35, T=0.02, dt=20.0, eps=1e-5)
+    assert len(d["m"]) > 3000
+    _check_td(d, 8000)
+
+
 def test_td_outputs_scale_accumulate(multimode):
     d = multimode
     ns = len(d["freq"]) + 777   # not a multiple of the block

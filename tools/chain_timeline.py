@@ -19,7 +19,10 @@ def main(path):
     ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]))
                 for r in rows)
     # a chain runs from one k_group_b (or k_prep_pcr_b when it groups the harmonics itself) to
-    # the last kernel before the next
+    # the last kernel before the next. The TD sum's preparation launches k_group_b,
+    # k_group_amp_b and k_prep_b as well (there is no other form of them): in a trace that
+    # holds TD sums their chains end in k_td_modesum, and the name filter below keeps the
+    # chains shaped like the first one
     chains, cur = [], None
     for s, e, n in ev:
         if n in ("k_ll_tile_const", "vectorized_elementwise_kernel", "__amd_rocclr_copyBuffer"):
