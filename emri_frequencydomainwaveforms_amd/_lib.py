@@ -164,6 +164,12 @@ class ModesumArgs(ctypes.Structure):
     ]
 
 
+# the workspace's `Header` (csrc/emrifd_layout.h): its size, and the byte offset of the split
+# plan's two int32 (nitems, nsplit) in it
+HEADER_BYTES = 64
+HEADER_SPLIT_PLAN = 48
+
+
 class TdArgs(ctypes.Structure):
     """Mirror of `efd_td_args` (include/emrifd.h)."""
 

@@ -29,8 +29,9 @@ and _run takes the branch choose_branch names from the template model's flags:
                 sums run a group at a time in one launch with the reduction in the sum's
                 epilogue (efd_modesum_sum_loglike, efd_modesum_sum_dh_hh): no template is
                 written, and the batch costs one host synchronisation (_run_fused: _fused_route
-                picks _HostFeed or _DeviceFeed, _fused_preparer holds the BatchPreparer,
-                _fused_drive runs the groups, joins their streams and copies out). Otherwise, or
+                picks the feed, waveform._HostFeed or _DeviceFeed, which the batched generator
+                shares; _fused_preparer holds the BatchPreparer; _fused_drive runs the groups
+                through summation.run_groups, joins their streams and copies out). Otherwise, or
                 with fused_likelihood = False, h+ and hx are written by efd_polarizations into
                 one reusable [2][N_pos] buffer per pipeline slot and reduced from it
                 (efd_loglike, efd_dh_hh_rows).
@@ -56,7 +57,9 @@ from .noise import check_seed, new_seed
 from .profiled import (DISTANCE_NODES, ProfiledLikelihood, marginalize_distance,  # noqa: F401
                        profile_amplitude, profile_none)
 from .reductions import Reducer
-from .summation import BatchPreparer, WaveformPipeline, loglike_tile_constants, require_gpu
+from .summation import (BatchPreparer, WaveformPipeline, loglike_tile_constants, require_gpu,
+                        run_groups)
+from .waveform import GenerateEMRIWaveform, _DeviceFeed, _HostFeed
 
 
 def choose_branch(tm, vectorized, has_args):
@@ -453,19 +456,25 @@ class Likelihood:
         Returns the result on the host, [n, *kind.tail] (one synchronisation per batch), or
         None, before queueing anything, when no route applies: the caller then takes the
         per-walker path."""
-        Feed = self._fused_route(tm, args, kwargs)
-        if Feed is None:
+        route = self._fused_route(tm, args, kwargs)
+        if route is None:
             return None
         n = len(params)
         if n == 0:
             return np.empty((0, *kind.tail), dtype=np.float64)
-        ngroups = -(-n // (_lib.EFD_BATCH_MAX if Feed is _DeviceFeed else self.FUSED_GROUP))
+        ngroups = -(-n // (_lib.EFD_BATCH_MAX if route == "device" else self.FUSED_GROUP))
         G = -(-n // ngroups)                       # balanced groups of at most that many
         F = self._fused_preparer(tm, G)
-        B = F["prep"]
-        feed = Feed(self, F, tm, params, args, kwargs)
+        B = F.prep
+        if route == "device":
+            feed = _DeviceFeed(B, tm.waveform_generator, params, kwargs, self.device,
+                               self.device_trajectory, F.traj, k0=getattr(tm, "_suffix_k0", None))
+        else:
+            feed = _HostFeed(B, params, getattr(tm, "submit_batch", None),
+                             getattr(tm, "submit", None), args, kwargs,
+                             prefetch=lambda p, *a, **k: _prefetch(tm, p, a, k))
         self._order_group_streams(F, ngroups)
-        if (kind.native_group and Feed is _HostFeed and self.FUSED_NATIVE_GROUP
+        if (kind.native_group and route == "host" and self.FUSED_NATIVE_GROUP
                 and hasattr(B.lib, "efd_fused_group")):
             def step(g0, g):
                 # the tile constants are made on the group's stream (once per grid), before
@@ -481,42 +490,43 @@ class Likelihood:
         return self._fused_drive(F, feed, step, n, G, out, kind.width).reshape((n, *kind.tail))
 
     def _fused_route(self, tm, args, kwargs):
-        """What feeds the fused groups: _DeviceFeed with device_upstream (it needs a
-        GenerateEMRIWaveform, keyword waveform arguments and no explicit mode list, and
-        otherwise leaves the walkers to the host route), _HostFeed with fused_likelihood, or
-        None when neither applies or the template's grid is not symmetric. Queues nothing."""
-        from .waveform import GenerateEMRIWaveform
+        """What feeds the fused groups: "device" (waveform._DeviceFeed) with device_upstream
+        (it needs a GenerateEMRIWaveform, keyword waveform arguments and no explicit mode list,
+        and otherwise leaves the walkers to the host route), "host" (waveform._HostFeed) with
+        fused_likelihood, or None when neither applies or the template's grid is not symmetric.
+        Queues nothing."""
         device = (self.device_upstream and not args
                   and isinstance(getattr(tm, "waveform_generator", None), GenerateEMRIWaveform)
                   and kwargs.get("mode_selection") is None)
         if not (device or self.fused_likelihood) or not self._fused_grid_ok(tm, kwargs):
             return None
-        return _DeviceFeed if device else _HostFeed
+        return "device" if device else "host"
 
     def _fused_preparer(self, tm, G):
-        """self._fused: the groups' BatchPreparer ("prep", made again when the caustic
-        treatment changes or a group outgrows it) and what is cached beside it: the group
-        streams' handles ("gst"; efd_stream_order takes them: one event record and one stream
-        wait each, in C), arrays of them per ordering, the pinned result ("pin") and the device
-        trajectories' state ("traj")."""
+        """self._fused: the groups' BatchPreparer (prep, made again when the caustic treatment
+        changes or a group outgrows it) and what is cached beside it: the group streams'
+        handles (gst; efd_stream_order takes them: one event record and one stream wait each,
+        in C), arrays of them per ordering (order), the pinned result (pin) and the device
+        trajectories' state (traj)."""
         caustic = _caustic(tm)
         F = self._fused
-        if F is None or F["prep"].caustic != caustic or F["prep"].group < G:
+        if F is None or F.prep.caustic != caustic or F.prep.group < G:
             B = BatchPreparer(max(G, self.FUSED_GROUP), self.FUSED_DEPTH, caustic=caustic,
                               device=self.device)
-            F = self._fused = dict(prep=B, gst=[B.stream(gi).cuda_stream
-                                                for gi in range(len(B.groups))])
+            F = self._fused = SimpleNamespace(
+                prep=B, gst=[B.stream(gi).cuda_stream for gi in range(len(B.groups))],
+                order={}, pin=None, traj={})
         return F
 
     def _order_group_streams(self, F, ngroups):
         """The group streams this batch's flushes take (the preparer's rotation from its next
         group) wait for the work queued so far on the current stream: one stream wait each."""
-        B, gst = F["prep"], F["gst"]
-        key = ("ord", gst.index(B.next_flush()[0].cuda_stream), min(ngroups, len(gst)))
-        arr = F.get(key)
+        B, gst = F.prep, F.gst
+        key = (gst.index(B.next_flush()[0].cuda_stream), min(ngroups, len(gst)))
+        arr = F.order.get(key)
         if arr is None:
-            arr = F[key] = (ctypes.c_void_p * key[2])(
-                *[gst[(key[1] + k) % len(gst)] for k in range(key[2])])
+            arr = F.order[key] = (ctypes.c_void_p * key[1])(
+                *[gst[(key[0] + k) % len(gst)] for k in range(key[1])])
         _lib.check(B.lib.efd_stream_order(
             self.torch.cuda.current_stream(self.device).cuda_stream, arr, len(arr)),
             "efd_stream_order", B.lib)
@@ -526,15 +536,14 @@ class Likelihood:
         join of the used group streams into the last one, which copies `out` (per doubles a
         walker) to the pinned buffer, and the wait for it. Returns the host copy; a failed
         walker comes back NaN from the kernel, and only then are the groups' flags read."""
-        B, gst, lib = F["prep"], F["gst"], F["prep"].lib
-        pin = F.get("pin")
+        B, gst, lib = F.prep, F.gst, F.prep.lib
+        pin = F.pin
         if pin is None or pin.numel() < per * n:
-            pin = F["pin"] = self.torch.empty(max(per * n, 64), dtype=self.torch.float64,
-                                              pin_memory=True)
+            pin = F.pin = self.torch.empty(max(per * n, 64), dtype=self.torch.float64,
+                                           pin_memory=True)
         used = []
         try:
-            for g0 in range(0, n, G):
-                used.append(step(g0, slice(g0, g0 + G)))
+            run_groups(B, feed, n, G, step, used)
             # the other groups' streams join the last one, which copies out
             last = used[-1]
             for gj in sorted(set(used) - {last}):
@@ -543,9 +552,6 @@ class Likelihood:
             _lib.check(lib.efd_download(pin.data_ptr(), out.data_ptr(), 8 * per * n, gst[last]),
                        "efd_download", lib)
         finally:
-            for f in feed.futs:
-                f.cancel()
-            B.drop_pending()
             # `out` belongs to the current stream: nothing may still write it when it is
             # returned, or freed after an exception
             if sys.exc_info()[0] is not None:
@@ -658,73 +664,6 @@ class Likelihood:
         if self.separate_d_h:   # (<d|h>, <h|h>) per subset: each concatenated on its own
             return tuple(np.concatenate([o[k] for o in out_ll], axis=0) for k in range(2))
         return np.concatenate(out_ll, axis=0)
-
-
-class _HostFeed:
-    """Fused groups (at most FUSED_GROUP walkers) fed from the host upstream, which starts on
-    the prefetch pool at once: the template chain collects a group's packed host inputs in the
-    preparer (submit_batch), whose flush stages, uploads and prepares them."""
-    futs = ()
-
-    def __init__(self, like, F, tm, params, args, kwargs):
-        self.B, self.tm, self.params, self.args, self.kwargs = F["prep"], tm, params, args, kwargs
-        self.batch = getattr(tm, "submit_batch", None)
-        _prefetch(tm, params, args, kwargs)
-
-    def collect(self, g):
-        """Walkers g into the preparer; the stream, grid and k0 of the flush that takes them."""
-        if self.batch is not None:
-            self.batch(self.B, self.params[g], *self.args, **self.kwargs)
-        else:
-            for p in self.params[g]:
-                self.tm.submit(self.B, None, *p, *self.args, order=False, prepare_only=True,
-                               **self.kwargs)
-        return self.B.next_flush()
-
-    def flush(self, g):
-        """(group index, walkers, the group's stream, grid, k0) of walkers g, prepared."""
-        sst, freq, k0 = self.collect(g)
-        gi, jobs = self.B.flush()
-        return gi, len(jobs), sst, freq, k0
-
-
-class _DeviceFeed:
-    """Fused groups (at most EFD_BATCH_MAX walkers) fed from the device upstream: the walkers'
-    trajectories start on the prefetch pool at once (device_trajectory: all of them in one
-    launch on the current stream, which the group streams are then ordered after); per group
-    the generator's device_inputs_batch (packed trajectory upload, efd_modes_select_batch, the
-    read of the group's K) runs on the group's stream and BatchPreparer.flush_device prepares
-    the group from what it left on the device, so a group's device chain runs beside the next
-    group's trajectories and selection."""
-
-    def __init__(self, like, F, tm, params, args, kwargs):
-        self.B, self.few, self.kwargs = F["prep"], tm.waveform_generator, kwargs
-        self.device = like.device
-        cw = _create_waveform(tm)
-        self.freq, _ = cw._grid(kwargs.get("T", 1.0), kwargs.get("dt", 10.0), kwargs.get("f_arr"))
-        self.k0 = cw.positive_start()
-        if getattr(tm, "_suffix_k0", self.k0) != self.k0:
-            raise ValueError("positive_frequency_mask does not match the generator's grid")
-        self.B.restart()
-        self.calls, self.scales = self.few.device_calls(params, kwargs.get("T", 1.0),
-                                                        kwargs.get("eps", 1e-5))
-        self.futs, self.trajs = [], None
-        if like.device_trajectory:
-            self.trajs = self.few.device_trajectories(self.calls, like.device,
-                                                      F.setdefault("traj", {}))
-        else:
-            self.futs = self.few.waveform_generator.trajectories_async(self.calls)
-
-    def flush(self, g):
-        """As _HostFeed.flush."""
-        sst = self.B.next_flush()[0]
-        inps = self.few.waveform_generator.device_inputs_batch(
-            self.calls[g], include_minus_m=bool(self.kwargs.get("include_minus_m", True)),
-            device=self.device, stream=sst, state=self.B.next_select(),
-            futures=self.futs[g] if self.trajs is None else None,
-            trajs=self.trajs[g] if self.trajs is not None else None)
-        gi, jobs = self.B.flush_device(inps, self.freq, self.scales[g], self.k0)
-        return gi, len(jobs), sst, self.freq, self.k0
 
 
 # The output kinds of Likelihood._run. tail, width: a walker's slot in `out` ([n, *tail], width

@@ -11,6 +11,7 @@ figures/spectrum_downsampled.png): N = int(T * YRSID_SI / dt) + 1, made odd when
 frequency = fftshift(fftfreq(N, dt)); or the caller's `f_arr` (emri_pe.py:344-364).
 """
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -36,10 +37,7 @@ def require_gpu():
 
 def fd_grid(T, dt, odd_len=True):
     """FEW's default two-sided grid for an observation of T years sampled at dt seconds."""
-    N = int(T * YRSID_SI / dt) + 1
-    if odd_len and N % 2 == 0:
-        N += 1
-    return np.fft.fftshift(np.fft.fftfreq(N, dt))
+    return np.fft.fftshift(np.fft.fftfreq(td_length(T, dt, odd_len), dt))
 
 
 def is_symmetric(freq):
@@ -115,8 +113,8 @@ class DeviceInputs:
         one device buffer, whose typed slices are the fields (the ten separate pageable copies
         this replaces cost ~0.17 ms per waveform). Kernels launched on that stream see the data
         in order; the staging buffer is reused only after its previous copy has completed.
-        `staging`: a dict owned by the caller (one per pipeline slot) instead of the per-device
-        default, so waveforms on different streams do not wait on each other's copies.
+        `staging`: a PinnedStage owned by the caller (one per row or stream) instead of the
+        per-device default, so waveforms on different streams do not wait on each other's copies.
         """
         torch = require_gpu()
         dev = device or torch.device("cuda", torch.cuda.current_device())
@@ -128,38 +126,74 @@ class DeviceInputs:
         return cls(**_staged_upload(arrays, dev, stream, staging), nt=int(nt), K=int(K))
 
 
+class PinnedStage:
+    """A pinned host buffer that asynchronous host->device copies read, reused from copy to
+    copy. The copies (efd_upload, efd_fused_group's) are invisible to torch's host allocator, so
+    the reuse-after-DMA rule lives here and nowhere else: `reserve` waits for the last copy out
+    of the buffer before the host may overwrite it or drop it for a larger one, and `sent`
+    records that copy. buf (uint8 tensor), np (its numpy view), ptr and nbytes are None, None,
+    0, 0 until the first reservation of at least a byte."""
+
+    def __init__(self, stream=None):
+        self.buf = self.np = self.done = None
+        self.ptr = self.nbytes = 0
+        if stream is not None:
+            # a first record, on the still empty stream, creates the event's handle for callers
+            # that re-record it natively (efd_fused_group)
+            self.sent(stream)
+
+    def reserve(self, nbytes=0):
+        """At least nbytes of pinned buffer the host may write now (its numpy view): waits for
+        the last copy recorded by `sent`, and only then replaces a buffer that is too small, by
+        one of max(2 * nbytes, 1 MiB)."""
+        if self.done is not None:
+            self.done.synchronize()
+        if self.nbytes < nbytes:
+            self.buf = _torch().empty(max(2 * nbytes, 1 << 20), dtype=_torch().uint8,
+                                      pin_memory=True)
+            self.np = self.buf.numpy()
+            self.ptr, self.nbytes = self.buf.data_ptr(), self.buf.numel()
+        return self.np
+
+    def sent(self, stream):
+        """Record, on the torch stream, the copy out of the buffer just queued there."""
+        if self.done is None:
+            self.done = _torch().cuda.Event()
+        self.done.record(stream)
+
+
 _STAGING = {}
 
 
 def _staged_upload(arrays, dev, stream=None, staging=None):
-    """Copy _host_arrays' arrays into one device buffer through a cached pinned buffer (see
-    from_host); returns the fields' views."""
+    """Copy _host_arrays' arrays into one device buffer through a pinned stage (see from_host;
+    default: one per device); returns the fields' views."""
     torch = _torch()
     offs, total = _packed_offsets(arrays)
     if staging is None:
-        staging = _STAGING.setdefault((dev.type, dev.index), {})
-    st = staging
-    if st.get("buf") is None or st["buf"].numel() < total:
-        if st.get("done") is not None:
-            st["done"].synchronize()        # the old buffer's last copy has read it
-        st["buf"] = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        st["done"] = None
-    if st.get("done") is not None:
-        st["done"].synchronize()        # the previous copy out of the staging buffer finished
-    _pack(st["buf"].numpy(), arrays, offs)
+        staging = _STAGING.setdefault((dev.type, dev.index), PinnedStage())
+    _pack(staging.reserve(total), arrays, offs)
     strm = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.stream(strm):
         d = torch.empty(total, dtype=torch.uint8, device=dev)
-        d.copy_(st["buf"][:total], non_blocking=True)
-    done = torch.cuda.Event()
-    done.record(strm)
-    st["done"] = done
+        d.copy_(staging.buf[:total], non_blocking=True)
+    staging.sent(strm)
     return _packed_views(d, arrays, offs)
 
 
-# efd_modesum_workspace_bytes per (N_t, K, N_f): walkers repeat shapes, and the lookup is cheaper
-# than the ctypes call
 _WS_BYTES = {}
+
+
+def _ws_bytes(lib, nt, K, nf):
+    """efd_modesum_workspace_bytes(N_t, K, N_f), kept in _WS_BYTES: walkers repeat shapes, and
+    the lookup (which the hot callers make themselves first) is cheaper than the ctypes call."""
+    nbytes = int(lib.efd_modesum_workspace_bytes(nt, K, nf))
+    if nbytes == 0:
+        raise _lib.EFDError("efd_modesum_workspace_bytes rejected the shape")
+    if len(_WS_BYTES) > 65536:
+        _WS_BYTES.clear()
+    _WS_BYTES[(nt, K, nf)] = nbytes
+    return nbytes
 
 
 class ModeSumEngine:
@@ -171,24 +205,14 @@ class ModeSumEngine:
         self.caustic = caustic
         self.lib = _lib.load()
         self._ws = None
-        self._ws_key = None
         self._ws_cap, self._ws_dev, self._ws_ptr = 0, None, 0
         self._last_args = None
-        self.last_contributions = None
 
     def _workspace(self, nt, K, nf, device, stream=None):
         """The workspace for (nt, K, nf), grown when too small. With `stream` (a torch stream)
         a new allocation is made on it, so the caching allocator ties the block to the stream
         that uses it (WaveformPipeline slots)."""
-        key = (nt, K, nf)
-        nbytes = _WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = int(self.lib.efd_modesum_workspace_bytes(nt, K, nf))
-            if nbytes == 0:
-                raise _lib.EFDError("efd_modesum_workspace_bytes rejected the shape")
-            if len(_WS_BYTES) > 65536:
-                _WS_BYTES.clear()
-            _WS_BYTES[key] = nbytes
+        nbytes = _WS_BYTES.get((nt, K, nf)) or _ws_bytes(self.lib, nt, K, nf)
         if self._ws is not None and self._ws_cap >= nbytes and self._ws_dev == device:
             return self._ws   # the walker-batch fast path: no torch calls
         torch = _torch()
@@ -203,9 +227,9 @@ class ModeSumEngine:
                 # reads them: a grown workspace inherits its predecessor's header (stream
                 # order), a first one starts clean (nothing from the memory's previous owner)
                 if old is not None:
-                    ws[:64].copy_(old[:64])
+                    ws[:_lib.HEADER_BYTES].copy_(old[:_lib.HEADER_BYTES])
                 else:
-                    ws[:64].zero_()
+                    ws[:_lib.HEADER_BYTES].zero_()
             self._ws = ws
         self._ws_cap, self._ws_dev = self._ws.numel(), self._ws.device
         self._ws_ptr = self._ws.data_ptr()
@@ -219,7 +243,8 @@ class ModeSumEngine:
             return (-1, 0)
         torch = _torch()
         torch.cuda.synchronize(self._ws.device)
-        v = self._ws[48:56].cpu().numpy().view(np.int32)
+        o = _lib.HEADER_SPLIT_PLAN
+        v = self._ws[o:o + 8].cpu().numpy().view(np.int32)
         return int(v[0]), int(v[1])
 
     def launch(self, inp, freq, out, grid_symmetric, scale=1.0 + 0.0j, accumulate=False,
@@ -265,36 +290,27 @@ class ModeSumEngine:
         st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         return self.lib.efd_modesum_status(self._ws.data_ptr(), st) == _lib.EFD_OK
 
+    def _header_counters(self, fn, ctypes_of, stream):
+        """The workspace header's counters the C call `fn` reads after synchronising `stream`
+        (None: the current one), one per ctypes type in ctypes_of, as Python ints."""
+        st = stream if stream is not None else _torch().cuda.current_stream().cuda_stream
+        vals = [t(0) for t in ctypes_of]
+        _lib.check(getattr(self.lib, fn)(self._ws.data_ptr(), *map(ctypes.byref, vals), st),
+                   fn, self.lib)
+        return [int(v.value) for v in vals]
+
     def contributions(self, stream=None):
-        import ctypes
-        torch = _torch()
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        c = ctypes.c_int64(0)
-        _lib.check(self.lib.efd_modesum_contributions(self._ws.data_ptr(), ctypes.byref(c), st),
-                   "efd_modesum_contributions", self.lib)
-        return int(c.value)
+        return self._header_counters("efd_modesum_contributions", [ctypes.c_int64], stream)[0]
 
     def stats(self, stream=None):
         """(contributions C, SPA evaluations, (m, n) groups) of the last launch."""
-        import ctypes
-        torch = _torch()
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        c, e, g = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        _lib.check(self.lib.efd_modesum_stats(self._ws.data_ptr(), ctypes.byref(c),
-                                              ctypes.byref(e), ctypes.byref(g), st),
-                   "efd_modesum_stats", self.lib)
-        return int(c.value), int(e.value), int(g.value)
+        return tuple(self._header_counters(
+            "efd_modesum_stats", [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32], stream))
 
     def env_evaluations(self, stream=None):
         """SPA evaluations of the last launch made on envelope records (k_items' per-record
         amplitude / K_1/3-phase polynomials)."""
-        import ctypes
-        torch = _torch()
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        e = ctypes.c_int64(0)
-        _lib.check(self.lib.efd_modesum_env_evaluations(self._ws.data_ptr(), ctypes.byref(e), st),
-                   "efd_modesum_env_evaluations", self.lib)
-        return int(e.value)
+        return self._header_counters("efd_modesum_env_evaluations", [ctypes.c_int64], stream)[0]
 
     def run(self, inp, freq, out=None, grid_symmetric=None, scale=1.0 + 0.0j, accumulate=False,
             check=True):
@@ -311,12 +327,32 @@ class ModeSumEngine:
         return out
 
 
+def _job_args(eng, kw, outputs=None, prof=None):
+    """(argument struct, workspace) of one (engine, launch_kwargs) job of a batched sum. A
+    BatchPreparer job carries its prepare call's struct (kw["_args"]): the fused sums, which
+    write no template, take it as it is (outputs None); sum_batch passes the call's outputs (a
+    dict with out / hp / hc / accumulate, the job's own kwargs) and gets a copy with those and
+    the prof events set. A job without the struct, or sum_batch's with its `inp` (a
+    WaveformPipeline slot's), is built from its kwargs by the engine."""
+    a0 = kw.get("_args")
+    if a0 is None or (outputs is not None and "inp" in kw):
+        return eng._args(prof_events=prof or (None, None),
+                         **{k: v for k, v in kw.items() if k != "_args"})
+    if outputs is None:
+        return a0, eng._ws
+    ptr = lambda x: x.data_ptr() if x is not None else None  # noqa: E731
+    a = _lib.ModesumArgs.from_buffer_copy(a0)
+    a.out, a.hp, a.hc = ptr(outputs.get("out")), ptr(outputs.get("hp")), ptr(outputs.get("hc"))
+    a.accumulate = 1 if outputs.get("accumulate") else 0
+    a.prof_begin, a.prof_end = prof or (None, None)
+    return a, eng._ws
+
+
 def _marshal(what, jobs, one, stream):
     """The batch calls' shared marshalling: (lib, args**, workspaces*, bytes*, count, stream
     handle, workspaces) of 1..EFD_BATCH_MAX (engine, launch_kwargs) jobs, each job's
     (argument struct, workspace) made by one(i, engine, kwargs); stream None: the current one
     on the grid's device."""
-    import ctypes
     jobs = list(jobs)
     n = len(jobs)
     if not 1 <= n <= _lib.EFD_BATCH_MAX:
@@ -341,22 +377,9 @@ def sum_batch(jobs, stream=None, prof_events=(None, None)):
     waveforms' tiles share one longest-first dispatch (one ramp, one tail, no launch gaps).
     prof_events bracket the launch. At most EFD_BATCH_MAX waveforms.
     """
-    ptr = lambda x: x.data_ptr() if x is not None else None  # noqa: E731
-
-    def one(i, eng, kw):
-        kw = dict(kw)
-        a0 = kw.pop("_args", None)
-        prof = prof_events if i == 0 else (None, None)
-        if a0 is None or "inp" in kw:
-            return eng._args(prof_events=prof, **kw)
-        # a BatchPreparer job: its prepare struct, with this call's outputs
-        a = _lib.ModesumArgs.from_buffer_copy(a0)
-        a.out, a.hp, a.hc = ptr(kw.get("out")), ptr(kw.get("hp")), ptr(kw.get("hc"))
-        a.accumulate = 1 if kw.get("accumulate") else 0
-        a.prof_begin, a.prof_end = prof
-        return a, eng._ws
-
-    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch", jobs, one, stream)
+    lib, pa, pw, pb, n, st, wss = _marshal(
+        "sum_batch", jobs,
+        lambda i, eng, kw: _job_args(eng, kw, kw, prof_events if i == 0 else None), stream)
     _lib.check(lib.efd_modesum_sum_batch(pa, pw, pb, n, st), "efd_modesum_sum_batch", lib)
     return wss
 
@@ -429,12 +452,8 @@ def sum_batch_loglike(jobs, d, w, out, stream=None, tile_const=None):
         _check_ll_io(torch, d, w, out, int(kw0["freq"].numel()) - int(kw0.get("k0", 0)),
                      len(jobs))
 
-    def one(i, eng, kw):
-        kw = dict(kw)
-        a = kw.pop("_args", None)   # the prepare call's own struct, as it is
-        return (a, eng._ws) if a is not None else eng._args(**kw)
-
-    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_loglike", jobs, one, stream)
+    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_loglike", jobs,
+                                           lambda i, eng, kw: _job_args(eng, kw), stream)
     tc = _tile_const_ptr(tile_const, jobs[0][1]["freq"].numel(), lib)
     _lib.check(lib.efd_modesum_sum_loglike_ex(pa, pw, pb, n, torch.view_as_real(d).data_ptr(),
                                               w.data_ptr(), tc, out.data_ptr(), st),
@@ -464,12 +483,8 @@ def sum_batch_dh_hh(jobs, d, w, out, stream=None, dense=False, part=None):
                      int(kw0["freq"].numel()) - int(kw0.get("k0", 0)), 1)
         _check_dh_out(torch, out, len(jobs))
 
-    def one(i, eng, kw):
-        kw = dict(kw)
-        a = kw.pop("_args", None)   # the prepare call's own struct, as it is
-        return (a, eng._ws) if a is not None else eng._args(**kw)
-
-    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_dh_hh", jobs, one, stream)
+    lib, pa, pw, pb, n, st, wss = _marshal("sum_batch_dh_hh", jobs,
+                                           lambda i, eng, kw: _job_args(eng, kw), stream)
     need = 3 * n * int(lib.efd_loglike_tile_count(int(jobs[0][1]["freq"].numel())))
     if part is None:
         part = torch.empty(need, dtype=torch.float64, device=d.device)
@@ -480,6 +495,20 @@ def sum_batch_dh_hh(jobs, d, w, out, stream=None, dense=False, part=None):
                                          out.data_ptr(), st),
                "efd_modesum_sum_dh_hh", lib)
     return wss
+
+
+class _Slot:
+    """One WaveformPipeline slot: its engine (workspace), stream and pinned stage; the device
+    buffer the inputs are copied to with the (key, offsets, total) layout and the DeviceInputs
+    views made for it; the sum job a prepare_only submit left; whether it was used; and S, the
+    spectrum buffer submit_channels keeps here for grids that are not symmetric."""
+
+    def __init__(self, caustic, device):
+        self.engine = ModeSumEngine(caustic=caustic)
+        self.stream = _torch().cuda.Stream(device)
+        self.stage = PinnedStage()
+        self.dbuf = self.layout = self.inp = self.job = self.S = None
+        self.used = False
 
 
 class WaveformPipeline:
@@ -502,9 +531,7 @@ class WaveformPipeline:
         if num_slots < 1:
             raise ValueError("num_slots must be >= 1")
         self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.slots = [dict(engine=ModeSumEngine(caustic=caustic),
-                           stream=torch.cuda.Stream(self.device), used=False)
-                      for _ in range(num_slots)]
+        self.slots = [_Slot(caustic, self.device) for _ in range(num_slots)]
         self._next = 0
         self.caustic = caustic
 
@@ -517,7 +544,7 @@ class WaveformPipeline:
         return self._next
 
     def stream(self, slot):
-        return self.slots[slot]["stream"]
+        return self.slots[slot].stream
 
     def submit(self, host, freq, grid_symmetric, scale=1.0 + 0.0j, out=None, hp=None, hc=None,
                k0=0, accumulate=False, order=True, prepare_only=False):
@@ -536,30 +563,25 @@ class WaveformPipeline:
         i = self._next
         self._next = (i + 1) % len(self.slots)
         sl = self.slots[i]
-        st = sl["stream"]
+        st = sl.stream
         if order:
             # the caller produced freq / outputs on its own stream: order this slot after it
             st.wait_stream(torch.cuda.current_stream(self.device))
         inp = self._upload(sl, host)
-        eng = sl["engine"]
+        eng = sl.engine
         eng._workspace(inp.nt, inp.K, int(freq.numel()), freq.device, stream=st)
-        if prepare_only:
-            eng.launch(inp, freq, out, grid_symmetric, scale, accumulate, stream=st.cuda_stream,
-                       hp=hp, hc=hc, k0=k0, phase="prepare")
-            # the prepare call's argument struct is the sum's too (same fields, no events)
-            sl["job"] = (eng, dict(inp=inp, freq=freq, out=out, grid_symmetric=grid_symmetric,
-                                   scale=scale, accumulate=accumulate, hp=hp, hc=hc, k0=k0,
-                                   _args=eng._last_args))
-        else:
-            eng.launch(inp, freq, out, grid_symmetric, scale, accumulate, stream=st.cuda_stream,
-                       hp=hp, hc=hc, k0=k0)
-            sl["job"] = None
-        sl["used"] = True
+        eng.launch(inp, freq, out, grid_symmetric, scale, accumulate, stream=st.cuda_stream,
+                   hp=hp, hc=hc, k0=k0, phase="prepare" if prepare_only else "all")
+        # the prepare call's argument struct is the sum's too (same fields, no events)
+        sl.job = (eng, dict(inp=inp, freq=freq, out=out, grid_symmetric=grid_symmetric,
+                            scale=scale, accumulate=accumulate, hp=hp, hc=hc, k0=k0,
+                            _args=eng._last_args)) if prepare_only else None
+        sl.used = True
         return i
 
     def job(self, slot):
         """The sum job a prepare_only submit left on `slot` (engine, launch kwargs)."""
-        return self.slots[slot].get("job")
+        return self.slots[slot].job
 
     def order_after_current(self):
         """Make every slot wait for the work queued so far on the current stream (once per
@@ -567,7 +589,7 @@ class WaveformPipeline:
         torch = _torch()
         cur = torch.cuda.current_stream(self.device)
         for sl in self.slots:
-            sl["stream"].wait_stream(cur)
+            sl.stream.wait_stream(cur)
 
     def _upload(self, sl, host):
         """The waveform's inputs into the slot's device buffer: packed into the slot's pinned
@@ -575,51 +597,39 @@ class WaveformPipeline:
         and are reused in stream order; the field views are rebuilt only when (nt, K) change."""
         torch = _torch()
         arrays, key = _host_arrays(host)
-        lay = sl.get("layout")
+        lay = sl.layout
         if lay is None or lay[0] != key:
             lay = (key,) + _packed_offsets(arrays)
         _, offs, total = lay
-        if sl.get("pin") is None or sl["pin"].numel() < total:
-            if sl.get("pin_done") is not None:
-                # the old buffer's last copy (efd_upload, invisible to torch's host allocator)
-                # must have read it before the block can be handed out again
-                sl["pin_done"].synchronize()
-            sl["pin"] = torch.empty(max(2 * total, 1 << 20), dtype=torch.uint8, pin_memory=True)
-            sl["pin_np"] = sl["pin"].numpy()
-            sl["pin_done"] = None
-        if sl.get("pin_done") is not None:
-            sl["pin_done"].synchronize()   # the slot's previous copy out of the pinned buffer
-        _pack(sl["pin_np"], arrays, offs)
-        if sl.get("dbuf") is None or sl["dbuf"].numel() < total:
-            with torch.cuda.stream(sl["stream"]):
-                sl["dbuf"] = torch.empty(max(2 * total, 1 << 20), dtype=torch.uint8,
-                                         device=self.device)
-            sl["layout"] = None
-        lib = sl["engine"].lib
-        _lib.check(lib.efd_upload(sl["dbuf"].data_ptr(), sl["pin"].data_ptr(), total,
-                                  sl["stream"].cuda_stream), "efd_upload", lib)
-        if sl.get("pin_done") is None:
-            sl["pin_done"] = torch.cuda.Event()
-        sl["pin_done"].record(sl["stream"])
-        if sl.get("layout") is None or sl["layout"][0] != key or sl.get("inp") is None:
-            sl["inp"] = DeviceInputs(**_packed_views(sl["dbuf"], arrays, offs),
-                                     nt=int(key[0]), K=int(key[1]))
-            sl["layout"] = lay
-        return sl["inp"]
+        _pack(sl.stage.reserve(total), arrays, offs)
+        if sl.dbuf is None or sl.dbuf.numel() < total:
+            with torch.cuda.stream(sl.stream):
+                sl.dbuf = torch.empty(max(2 * total, 1 << 20), dtype=torch.uint8,
+                                      device=self.device)
+            sl.layout = None
+        lib = sl.engine.lib
+        _lib.check(lib.efd_upload(sl.dbuf.data_ptr(), sl.stage.ptr, total,
+                                  sl.stream.cuda_stream), "efd_upload", lib)
+        sl.stage.sent(sl.stream)
+        if sl.layout is None or sl.layout[0] != key or sl.inp is None:
+            sl.inp = DeviceInputs(**_packed_views(sl.dbuf, arrays, offs),
+                                  nt=int(key[0]), K=int(key[1]))
+            sl.layout = lay
+        return sl.inp
 
     def join(self):
         """Make the current stream wait for every slot (device-side; no host sync)."""
         torch = _torch()
         cur = torch.cuda.current_stream(self.device)
         for sl in self.slots:
-            if sl["used"]:
-                cur.wait_stream(sl["stream"])
+            if sl.used:
+                cur.wait_stream(sl.stream)
 
     def wait(self):
         """Synchronise every slot and raise if any reported a device-side error."""
         for sl in self.slots:
-            if sl["used"] and not sl["engine"].status(sl["stream"].cuda_stream):
-                raise _lib.EFDError(f"efd_modesum: {_lib.last_error(sl['engine'].lib)}")
+            if sl.used and not sl.engine.status(sl.stream.cuda_stream):
+                raise _lib.EFDError(f"efd_modesum: {_lib.last_error(sl.engine.lib)}")
         self.join()
 
 
@@ -628,16 +638,13 @@ class _Group:
     stream its work runs on, its staging buffers and the argument arrays the native calls take."""
 
     def __init__(self, size, caustic, device):
-        import ctypes
         torch = _torch()
         self.engines = [ModeSumEngine(caustic=caustic) for _ in range(size)]
         self.stream = torch.cuda.Stream(device)
-        # the pinned staging buffer and its device copy (BatchPreparer._stage grows them)
-        self.pin = self.dbuf = None
-        # recorded after every copy out of `pin`; this first record, on the still empty stream,
-        # creates the handle efd_fused_group re-records
-        self.pin_done = torch.cuda.Event()
-        self.pin_done.record(self.stream)
+        # the pinned stage (its event exists from the start: efd_fused_group re-records it) and
+        # the device buffer it is copied to (BatchPreparer._stage grows both)
+        self.stage = PinnedStage(self.stream)
+        self.dbuf = None
         self.busy = None      # release()'s event: the group's last sum has read its workspaces
         # the device upstream's selection state (device_inputs_batch's `state`: its pinned and
         # output buffers; the group's previous sum reads them on this stream)
@@ -719,6 +726,14 @@ class BatchPreparer:
                               bool(accumulate)))
         return len(self._pending) - 1
 
+    def collect(self, host, freq, scale, k0):
+        """submit(host, freq, True, scale, k0=k0, prepare_only=True) for callers that hold
+        normalised arguments already (a complex scale, an int k0): a symmetric grid, accumulate
+        off, no argument handling. A walker batch's loop binds it once."""
+        if len(self._pending) >= self.group:
+            raise ValueError(f"at most {self.group} walkers per flush")
+        self._pending.append((host, freq, True, scale, k0, False))
+
     def order_after_current(self):
         torch = _torch()
         cur = torch.cuda.current_stream(self.device)
@@ -769,7 +784,7 @@ class BatchPreparer:
         """The pending walkers for the next group: (group index, group, walkers, template
         struct). The walkers are checked first (one grid; symmetry, k0 and accumulate agree);
         then the groups rotate and the group's stream waits for the sum that last read its
-        workspaces, the host for the last copy out of its pinned buffer."""
+        workspaces, the host for the last copy out of its pinned stage (reserve)."""
         pend, self._pending = self._pending, []
         if not pend:
             raise ValueError(f"{what}: nothing submitted")
@@ -781,7 +796,7 @@ class BatchPreparer:
             if s != sym or k != k0 or a != acc:
                 raise ValueError("flush: grid symmetry, k0 and accumulate must agree in a group")
         gi, G = self._rotate()
-        G.pin_done.synchronize()
+        G.stage.reserve()
         key = (freq.data_ptr(), nf, sym, acc, k0)
         if G.tmpl is None or G.tmpl[0] != key:
             G.tmpl = (key, _lib.ModesumArgs(
@@ -819,28 +834,26 @@ class BatchPreparer:
     def _stage(self, G, call, failed):
         """The staging call call(pin, pin bytes, dbuf, dbuf bytes, &total) on G's buffers
         (efd_stage_batch, or efd_fused_group, which goes on to the launches); a buffer too
-        small for `total` is grown to max(2 * total, 1 MiB) (the device one on G's stream) and
-        the call made once more. Returns total; failed(rc) is the error's text."""
-        import ctypes
+        small for `total` is grown (the pinned stage's reserve; the device one to
+        max(2 * total, 1 MiB) on G's stream) and the call made once more. _take has waited for
+        the last copy out of the stage. Returns total; failed(rc) is the error's text."""
         torch = _torch()
         total = ctypes.c_size_t(0)
+        pin = G.stage
         for attempt in range(2):
-            pin, dbuf = G.pin, G.dbuf
-            rc = call(pin.data_ptr() if pin is not None else 0,
-                      pin.numel() if pin is not None else 0,
-                      dbuf.data_ptr() if dbuf is not None else 0,
+            dbuf = G.dbuf
+            rc = call(pin.ptr, pin.nbytes, dbuf.data_ptr() if dbuf is not None else 0,
                       dbuf.numel() if dbuf is not None else 0, ctypes.byref(total))
             need = total.value
             if rc == _lib.EFD_OK and dbuf is not None and dbuf.numel() >= need:
                 return need
             if rc not in (_lib.EFD_OK, _lib.EFD_ERR_WORKSPACE) or attempt == 1:
                 raise _lib.EFDError(failed(rc))
-            cap = max(2 * need, 1 << 20)
-            if pin is None or pin.numel() < need:
-                G.pin = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            pin.reserve(need)
             if dbuf is None or dbuf.numel() < need:
                 with torch.cuda.stream(G.stream):
-                    G.dbuf = torch.empty(cap, dtype=torch.uint8, device=self.device)
+                    G.dbuf = torch.empty(max(2 * need, 1 << 20), dtype=torch.uint8,
+                                         device=self.device)
 
     def _size_each(self, G, shape, freq, k0, sym):
         """flush()'s workspaces: every engine sized for its own walker's (N_t, K) (the
@@ -867,12 +880,7 @@ class BatchPreparer:
         stand as they are and no per-walker step is needed."""
         nf, dev, n = int(freq.numel()), freq.device, len(shape)
         kb = (int(shape[:, 0].max()), int(shape[:, 1].max()), nf)
-        nbmax = _WS_BYTES.get(kb)
-        if nbmax is None:
-            nbmax = int(self.lib.efd_modesum_workspace_bytes(*kb))
-            if nbmax == 0:
-                raise _lib.EFDError("efd_modesum_workspace_bytes rejected the shape")
-            _WS_BYTES[kb] = nbmax
+        nbmax = _WS_BYTES.get(kb) or _ws_bytes(self.lib, *kb)
         floor = G.ws_floor
         if floor is None or floor[0] != dev or floor[1] < nbmax or floor[2] < n:
             engines = G.engines
@@ -889,7 +897,6 @@ class BatchPreparer:
         """Upload and prepare the collected walkers; returns (group index, jobs). A job's
         argument struct lives in the group's reused array: use the jobs before the group's next
         flush (sum_batch / sum_batch_loglike copy what they need)."""
-        import ctypes
         gi, G, pend, tmpl = self._take("flush")
         _, freq, sym, _, k0, _ = pend[0]
         n, lib, st = len(pend), self.lib, G.stream
@@ -900,9 +907,9 @@ class BatchPreparer:
                 ctypes.byref(tmpl), G.args, total),
             lambda rc: f"efd_stage_batch failed ({rc})")
         del keep
-        _lib.check(lib.efd_upload(G.dbuf.data_ptr(), G.pin.data_ptr(), total, st.cuda_stream),
+        _lib.check(lib.efd_upload(G.dbuf.data_ptr(), G.stage.ptr, total, st.cuda_stream),
                    "efd_upload", lib)
-        G.pin_done.record(st)
+        G.stage.sent(st)
         return gi, self._prepare(G, self._size_each(G, shape, freq, k0, sym))
 
     def flush_device(self, inputs, freq, scales, k0):
@@ -943,7 +950,6 @@ class BatchPreparer:
         then sum_loglike(gi, ..., G's stream), bitwise the same logL, in one ctypes
         transition instead of five. d, w: checked once per pair of buffers. The logL go to
         out[out_off : out_off + n]."""
-        import ctypes
         torch = _torch()
         gi, G, pend, tmpl = self._take("flush_loglike")
         _, freq, sym, _, k0, _ = pend[0]
@@ -959,7 +965,7 @@ class BatchPreparer:
         self._size_group(G, shape, freq)
         tcp = tile_const.data_ptr() if tile_const is not None else None
         op = out.data_ptr() + 8 * out_off
-        ev, sth = G.pin_done.cuda_event, G.stream.cuda_stream
+        ev, sth = G.stage.done.cuda_event, G.stream.cuda_stream
         self._stage(
             G, lambda pin, pin_bytes, dbuf, dbuf_bytes, total: lib.efd_fused_group(
                 pin, pin_bytes, dbuf, dbuf_bytes, n, src.ctypes.data, shape.ctypes.data,
@@ -992,15 +998,12 @@ class BatchPreparer:
         nb = int(G.args[0].nf) - int(G.args[0].k0)
         _check_ll_io(torch, d, w, out, nb, n)
         dp, wp, op = torch.view_as_real(d).data_ptr(), w.data_ptr(), out.data_ptr()
+        # (checked by the caller that made them for this grid: no per-call recount)
+        tcp = tile_const.data_ptr() if tile_const is not None else None
         for c0, cnt, pa_c, pw_c, pb_c in G.chunks[n]:
-            if tile_const is None:
-                _lib.check(self.lib.efd_modesum_sum_loglike(pa_c, pw_c, pb_c, cnt, dp, wp,
-                                                            op + 8 * c0, stream),
-                           "efd_modesum_sum_loglike", self.lib)
-            else:   # (checked by the caller that made them for this grid: no per-call recount)
-                _lib.check(self.lib.efd_modesum_sum_loglike_ex(
-                    pa_c, pw_c, pb_c, cnt, dp, wp, tile_const.data_ptr(), op + 8 * c0, stream),
-                    "efd_modesum_sum_loglike_ex", self.lib)
+            _lib.check(self.lib.efd_modesum_sum_loglike_ex(
+                pa_c, pw_c, pb_c, cnt, dp, wp, tcp, op + 8 * c0, stream),
+                "efd_modesum_sum_loglike_ex", self.lib)
 
     def sum_dh_hh(self, gi, d, w, out, stream, dense=False):
         """efd_modesum_sum_dh_hh over group gi's last flush, in launches of EFD_BATCH_MAX
@@ -1033,7 +1036,6 @@ class BatchPreparer:
 
     def wait(self):
         """Synchronise every group and raise if any workspace reported a device-side error."""
-        import ctypes
         for G in self.groups:
             wss = [eng._ws.data_ptr() for eng in G.engines if eng._ws is not None]
             if not G.used or not wss:
@@ -1044,6 +1046,21 @@ class BatchPreparer:
                 if self.lib.efd_modesum_status_batch(pw, len(part), None,
                                                      G.stream.cuda_stream) != _lib.EFD_OK:
                     raise _lib.EFDError(_lib.last_error(self.lib))
+
+
+def run_groups(prep, feed, n, G, step, used):
+    """The batched callers' group loop: step(g0, slice(g0, g0 + G)) for every group of G of n
+    walkers, each step's return value (the preparer group it took) appended to the caller's
+    list `used` once the step is through. However the loop ends, the feed's futures are
+    cancelled and the preparer forgets what was collected for a group that never flushed; the
+    caller joins or synchronises the group streams (its own policy) around this call."""
+    try:
+        for g0 in range(0, n, G):
+            used.append(step(g0, slice(g0, g0 + G)))
+    finally:
+        for f in feed.futs:
+            f.cancel()
+        prep.drop_pending()
 
 
 def td_length(T, dt, odd_len=True):
@@ -1251,9 +1268,9 @@ class FDInterpolatedModeSum:
         sl = pipeline.slots[slot]
         st = pipeline.stream(slot)
         with torch.cuda.stream(st):
-            S = sl.get("S")
+            S = sl.S
             if S is None or S.numel() != nf:
-                sl["S"] = S = torch.empty(nf, dtype=torch.complex128, device=freq.device)
+                sl.S = S = torch.empty(nf, dtype=torch.complex128, device=freq.device)
         pipeline.submit(host, freq, False, scale, out=torch.view_as_real(S), order=order)
         lib = self.engine.lib
         _lib.check(lib.efd_polarizations(torch.view_as_real(S).data_ptr(), nf, k0,

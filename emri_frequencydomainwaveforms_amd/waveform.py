@@ -28,7 +28,9 @@ kernel's complex scale, so it costs nothing.
 """
 
 import os
+import sys
 import threading
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -36,7 +38,9 @@ from . import _lib
 from .amplitude import ModeSelector, RomanAmplitude
 from .constants import Gpc, MRSUN_SI, MTSUN_SI
 from .frequencies import get_fundamental_frequencies
-from .summation import FDInterpolatedModeSum, TDInterpolatedModeSum, require_gpu
+from .summation import (BatchPreparer, DeviceInputs, FDInterpolatedModeSum, PinnedStage,
+                        TDEngine, TDInterpolatedModeSum, require_gpu, run_groups, sum_batch,
+                        td_length)
 from .trajectory import EMRIInspiral
 from .ylm import GetYlms
 
@@ -262,7 +266,6 @@ class FastSchwarzschildEccentricFlux:
         `stream` is ordered after): the seven arrays are those views instead; no trajectory
         runs on the host and nothing is packed or uploaded here."""
         torch = require_gpu()
-        from .summation import DeviceInputs
         calls = [tuple(c) for c in calls]
         n = len(calls)
         if not 1 <= n <= _lib.EFD_BATCH_MAX:
@@ -578,6 +581,77 @@ def _pool():
     return _POOL
 
 
+class _HostFeed:
+    """Walker groups of a BatchPreparer fed from the host upstream, which `prefetch(params,
+    *args, **kwargs)` starts on the pool before the first group: submit_batch(prep, rows, *args,
+    **kwargs) collects a group's packed host inputs in the preparer (GenerateEMRIWaveform's, or a
+    template model's; without one, submit(prep, None, *row, ...) per walker), whose flush stages,
+    uploads and prepares them. The batched generator and the fused likelihood share it."""
+    futs = ()
+
+    def __init__(self, prep, params, submit_batch, submit=None, args=(), kwargs=None,
+                 prefetch=None):
+        self.B, self.params, self.args, self.kwargs = prep, params, args, kwargs or {}
+        self.batch, self.submit = submit_batch, submit
+        if prefetch is not None:
+            prefetch(params, *args, **self.kwargs)
+
+    def collect(self, g):
+        """Walkers g into the preparer; the stream, grid and k0 of the flush that takes them."""
+        if self.batch is not None:
+            self.batch(self.B, self.params[g], *self.args, **self.kwargs)
+        else:
+            for p in self.params[g]:
+                self.submit(self.B, None, *p, *self.args, order=False, prepare_only=True,
+                            **self.kwargs)
+        return self.B.next_flush()
+
+    def flush(self, g):
+        """(group index, walkers, the group's stream, grid, k0) of walkers g, prepared."""
+        sst, freq, k0 = self.collect(g)
+        gi, jobs = self.B.flush()
+        return gi, len(jobs), sst, freq, k0
+
+
+class _DeviceFeed:
+    """Walker groups (at most EFD_BATCH_MAX walkers) of a BatchPreparer fed from the device
+    upstream of `few`, a GenerateEMRIWaveform: the walkers' trajectories start on the prefetch
+    pool at once (trajectory_on_device: all of them in one launch on the current stream, which
+    the group streams are then ordered after; `state` keeps that launch's buffers); per group
+    the generator's device_inputs_batch (packed trajectory upload, efd_modes_select_batch, the
+    read of the group's K) runs on the group's stream and BatchPreparer.flush_device prepares
+    the group from what it left on the device, so a group's device chain runs beside the next
+    group's trajectories and selection. Every batch starts at the preparer's first group
+    (restart). k0: the caller's f >= 0 start, checked against the grid's."""
+
+    def __init__(self, prep, few, params, kwargs, device, trajectory_on_device, state, k0=None):
+        self.B, self.gen, self.device = prep, few.waveform_generator, device
+        self.minus_m = bool(kwargs.get("include_minus_m", True))
+        T = kwargs.get("T", 1.0)
+        cw = self.gen.create_waveform
+        self.freq, _ = cw._grid(T, kwargs.get("dt", 10.0), kwargs.get("f_arr"))
+        self.k0 = cw.positive_start()
+        if k0 is not None and k0 != self.k0:
+            raise ValueError("positive_frequency_mask does not match the generator's grid")
+        prep.restart()
+        self.calls, self.scales = few.device_calls(params, T, kwargs.get("eps", 1e-5))
+        self.futs, self.trajs = [], None
+        if trajectory_on_device:
+            self.trajs = few.device_trajectories(self.calls, device, state)
+        else:
+            self.futs = self.gen.trajectories_async(self.calls)
+
+    def flush(self, g):
+        """As _HostFeed.flush."""
+        sst = self.B.next_flush()[0]
+        inps = self.gen.device_inputs_batch(
+            self.calls[g], include_minus_m=self.minus_m, device=self.device, stream=sst,
+            state=self.B.next_select(), futures=self.futs[g] if self.trajs is None else None,
+            trajs=self.trajs[g] if self.trajs is not None else None)
+        gi, jobs = self.B.flush_device(inps, self.freq, self.scales[g], self.k0)
+        return gi, len(jobs), sst, self.freq, self.k0
+
+
 class GenerateEMRIWaveform:
     """Generic EMRI generator with FEW's 14-parameter call (frame handling + list output)."""
 
@@ -655,22 +729,14 @@ class GenerateEMRIWaveform:
             raise ValueError("positive_frequency_mask does not match the generator's grid")
         if not sym:
             raise ValueError("submit_batch needs a symmetric grid (the fused likelihood's)")
-        kc = cw._k0
-        submit = preparer.submit
-        # the native upstream's walkers go straight onto the preparer's pending list (what
-        # submit(d, freq, True, scale, k0=kc, prepare_only=True) appends, without its argument
-        # handling per walker)
-        pend = getattr(preparer, "_pending", None)
-        room = getattr(preparer, "group", 0)
+        kc = int(cw._k0)
+        submit, collect = preparer.submit, preparer.collect
         for call, scale in zip(*self.device_calls(params, T, eps)):
             d = gen.prepare(*call, mode_selection, include_minus_m)
             if "_src" in d:
                 # the native upstream recorded its arrays' addresses: the preparer stages them
-                # straight from prepare()'s dict
-                if pend is not None and len(pend) < room:
-                    pend.append((d, freq, True, scale, int(kc), False))
-                else:
-                    submit(d, freq, True, scale, k0=kc, prepare_only=True)
+                # straight from prepare()'s dict (collect: submit without its argument handling)
+                collect(d, freq, scale, kc)
                 continue
             K = len(d["m"])
             y = d["ylms"]
@@ -755,14 +821,14 @@ class GenerateEMRIWaveform:
         """Wait for the last spectrum_batch's lane-range copies into lanes_host (each group's
         event; the sums behind them keep running)."""
         if self._gen_batch is not None:
-            for ev in self._gen_batch["lanes_ev_used"]:
+            for ev in self._gen_batch.lanes_ev_used:
                 ev.synchronize()
 
     def check_batch(self):
         """Synchronise the last batch's groups and raise if a workspace reported a device-side
         error (what spectrum_batch(check=False) skipped)."""
         if self._gen_batch is not None:
-            self._gen_batch["prep"].wait()
+            self._gen_batch.prep.wait()
 
     def positive_bins(self, T=1.0, dt=10.0, f_arr=None):
         """N_pos, the f >= 0 bins of the grid generate_batch writes (its out's last dimension)."""
@@ -801,100 +867,79 @@ class GenerateEMRIWaveform:
     def _run_batch(self, params, out, outputs, T, dt, eps, f_arr, kwargs, lanes=None,
                    check=True, lanes_host=None, upstream="host", trajectory="host"):
         torch = require_gpu()
-        from .summation import BatchPreparer, sum_batch
-        gen = self.waveform_generator
-        cw = gen.create_waveform
+        cw = self.waveform_generator.create_waveform
         params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
         B = len(params)
         if B == 0:
             return out
         G = min(self.BATCH_GROUP, _lib.EFD_BATCH_MAX)
         st = self._gen_batch
-        if (st is None or st["prep"].caustic != cw.caustic or st["device"] != out.device
-                or st["prep"].group != G):
-            st = self._gen_batch = dict(
+        if (st is None or st.prep.caustic != cw.caustic or st.device != out.device
+                or st.prep.group != G):
+            # the preparer's two rotating groups; an event per group for the preparation's end
+            # and for the lane-range copy (lanes_host), those copies' side stream, the last
+            # call's events (lanes_ready); the device trajectories' buffers
+            st = self._gen_batch = SimpleNamespace(
                 prep=BatchPreparer(group=G, depth=2, caustic=cw.caustic, device=out.device),
-                device=out.device,
-                ev=[torch.cuda.Event(), torch.cuda.Event()],
+                device=out.device, prep_ev=[torch.cuda.Event(), torch.cuda.Event()],
                 lanes_ev=[torch.cuda.Event(), torch.cuda.Event()],
-                prep_ev=[torch.cuda.Event(), torch.cuda.Event()],
-                lstream=torch.cuda.Stream(out.device))
-        prep = st["prep"]
+                lstream=torch.cuda.Stream(out.device), lanes_ev_used=[], traj={})
+        prep = st.prep
         # the upstream of all rows, started before the first group: the host route's on the
         # prefetch pool; the device route's trajectories on the pool too, or in one launch on
         # the current stream (the groups' selections then run on their streams)
-        device = upstream == "device"
-        futs, trajs = [], None
-        if not device:
-            self.prefetch(params, T=T, dt=dt, eps=eps, **kwargs)
+        kw = dict(kwargs, T=T, dt=dt, eps=eps, f_arr=f_arr)
+        if upstream == "device":
+            feed = _DeviceFeed(prep, self, params, kw, out.device, trajectory == "device",
+                               st.traj)
         else:
-            prep.restart()
-            freq, kc = cw._grid(T, dt, f_arr)[0], cw._k0
-            calls, scales = self.device_calls(params, T, eps)
-            if trajectory == "device":
-                trajs = self.device_trajectories(calls, out.device, st.setdefault("traj", {}))
-            else:
-                futs = gen.trajectories_async(calls)
+            feed = _HostFeed(prep, params, self.submit_batch, kwargs=kw, prefetch=self.prefetch)
         cur = torch.cuda.current_stream(out.device)
         prep.order_after_current()
-        # each group's sum on the group's own stream, right behind its preparation (no
-        # cross-stream wait between the two: ~34 us of idle device a group in the windowed
-        # trace, r05zg); group i + 1's preparation on the other stream still runs beside it,
-        # and the current stream joins every used group stream at the end
-        used = []
-        st["lanes_ev_used"] = []
-        try:
-            for g0 in range(0, B, G):
-                # joined at the end however the group's queueing ends
-                gs = prep.next_flush()[0]
-                if gs not in used:
-                    used.append(gs)
-                if device:
-                    g = slice(g0, g0 + G)
-                    inps = gen.device_inputs_batch(
-                        calls[g], include_minus_m=bool(kwargs.get("include_minus_m", True)),
-                        device=out.device, stream=gs, state=prep.next_select(),
-                        futures=futs[g] if trajs is None else None,
-                        trajs=trajs[g] if trajs is not None else None)
-                    gi, jobs = prep.flush_device(inps, freq, scales[g], kc)
-                else:
-                    self.submit_batch(prep, params[g0:g0 + G], T=T, dt=dt, eps=eps, f_arr=f_arr,
-                                      **kwargs)
-                    gi, jobs = prep.flush()
+        st.lanes_ev_used = []
+
+        def step(g0, g):
+            # the group's sum on the group's own stream, right behind its preparation (no
+            # cross-stream wait between the two: ~34 us of idle device a group in the windowed
+            # trace, r05zg); group i + 1's preparation on the other stream still runs beside
+            # it. The stream orders the group's next preparation after this sum: no release()
+            gi, m, gs, _, _ = feed.flush(g)
+            if lanes_host is not None:
+                pev = st.prep_ev[gi]
+                pev.record(gs)
+            sum_batch([(eng, dict(job, **outputs(g0 + i)))
+                       for i, (eng, job) in enumerate(prep.last_jobs)], stream=gs.cuda_stream)
+            if lanes is not None:   # the preparation's segment ranges
+                # with lanes_host: gathered and copied on a side stream behind the
+                # preparation, beside the sum, so the host has them while the sum runs; the
+                # group's stream waits for that stream too before its next preparation
+                ls = st.lstream if lanes_host is not None else gs
                 if lanes_host is not None:
-                    pev = st["prep_ev"][gi]
-                    pev.record(gs)
-                sum_batch([(eng, dict(kw, **outputs(g0 + i)))
-                           for i, (eng, kw) in enumerate(jobs)], stream=gs.cuda_stream)
-                if lanes is not None:   # the preparation's segment ranges
-                    # with lanes_host: gathered and copied on a side stream behind the
-                    # preparation, beside the sum, so the host has them while the sum runs;
-                    # the group's release waits for that stream too
-                    ls = st["lstream"] if lanes_host is not None else gs
-                    if lanes_host is not None:
-                        ls.wait_event(pev)
-                    _lib.check(prep.lib.efd_modesum_lane_ranges(
-                        prep.workspace_ptrs(gi), len(jobs), lanes[g0].data_ptr(),
-                        ls.cuda_stream), "efd_modesum_lane_ranges", prep.lib)
-                    if lanes_host is not None:
-                        _lib.check(prep.lib.efd_download(
-                            lanes_host[g0].data_ptr(), lanes[g0].data_ptr(), 8 * len(jobs),
-                            ls.cuda_stream), "efd_download", prep.lib)
-                        lev = st["lanes_ev"][gi]
-                        lev.record(ls)
-                        st["lanes_ev_used"].append(lev)
-                        gs.wait_event(lev)
-                ev = st["ev"][gi]
-                ev.record(gs)
-                prep.release(gi, ev)
+                    ls.wait_event(pev)
+                _lib.check(prep.lib.efd_modesum_lane_ranges(
+                    prep.workspace_ptrs(gi), m, lanes[g0].data_ptr(), ls.cuda_stream),
+                    "efd_modesum_lane_ranges", prep.lib)
+                if lanes_host is not None:
+                    _lib.check(prep.lib.efd_download(
+                        lanes_host[g0].data_ptr(), lanes[g0].data_ptr(), 8 * m,
+                        ls.cuda_stream), "efd_download", prep.lib)
+                    lev = st.lanes_ev[gi]
+                    lev.record(ls)
+                    st.lanes_ev_used.append(lev)
+                    gs.wait_event(lev)
+            return gi
+
+        used = []
+        try:
+            run_groups(prep, feed, B, G, step, used)
         finally:
-            for f in futs:
-                f.cancel()
-            prep.drop_pending()
-            for gs in used:
-                cur.wait_stream(gs)
-            if lanes_host is not None and used:
-                cur.wait_stream(st["lstream"])
+            # out is the caller's: the current stream joins the group streams that took work;
+            # after an exception all of them (its group may not have reached `used`)
+            failed = sys.exc_info()[0] is not None
+            for gi in (range(len(prep.groups)) if failed else dict.fromkeys(used)):
+                cur.wait_stream(prep.stream(gi))
+            if lanes_host is not None and (used or failed):
+                cur.wait_stream(st.lstream)
         if check:
             prep.wait()   # device-side errors of the groups' workspaces raise here
         return out
@@ -921,7 +966,6 @@ class GenerateEMRIWaveform:
         cw = self.waveform_generator.create_waveform
         if self.waveform_generator.output_type != "td" or not cw.pad_output:
             raise ValueError("time_series_batch needs the TD generator with pad_output=True")
-        from .summation import td_length
         return td_length(T, dt, cw.odd_len)
 
     def time_series_batch(self, params, out, window=None, T=1.0, dt=10.0, eps=1e-5,
@@ -937,7 +981,6 @@ class GenerateEMRIWaveform:
         synchronisation between walkers. Each walker has its own TD workspace; their device-side
         status is read once at the end (check=False: by the caller, check_td_batch())."""
         torch = require_gpu()
-        from .summation import DeviceInputs, TDEngine
         gen = self.waveform_generator
         ns = self.td_samples(T, dt)
         params = np.asarray(params, dtype=np.float64).reshape(-1, 14)
@@ -952,7 +995,7 @@ class GenerateEMRIWaveform:
             st = self._td_batch = dict(engines=[], staging=[], used=0)
         while len(st["engines"]) < B:
             st["engines"].append(TDEngine())
-            st["staging"].append({})
+            st["staging"].append(PinnedStage())
         st["used"] = 0
         if B == 0:
             return out

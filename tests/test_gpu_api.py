@@ -164,7 +164,7 @@ def test_fused_likelihood_many_walkers(setup):
     like.fused_likelihood = False
     np.testing.assert_allclose(llf, like.get_ll(walkers, **kw), rtol=1e-12, atol=0.0)
     # argument errors: wrong data shape (host-side ValueError), unprepared mix of grids (C ABI)
-    jobs = like._fused["prep"].last_jobs[:2]
+    jobs = like._fused.prep.last_jobs[:2]
     out = torch.empty(2, dtype=torch.float64, device="cuda")
     with pytest.raises(ValueError):
         sum_batch_loglike(jobs, like._d[:, 1:].contiguous(), like._w_templ, out)
@@ -177,7 +177,7 @@ def test_fused_likelihood_many_walkers(setup):
     # get_ll raises only once every group stream is idle, and the next call is unaffected
     # (both host paths: one native call per group, flush_loglike, and the Python steps, flush)
     like.fused_likelihood = True
-    Bp = like._fused["prep"]
+    Bp = like._fused.prep
     for native, name in ((True, "flush_loglike"), (False, "flush")):
         like.FUSED_NATIVE_GROUP = native
         orig, seen = getattr(Bp, name), []
@@ -220,7 +220,7 @@ def test_fused_likelihood_large_group(setup):
     like.FUSED_GROUP = 32
     like._fused = None
     got = like.get_ll(walkers, **kw)
-    assert like._fused["prep"].group == 32
+    assert like._fused.prep.group == 32
     np.testing.assert_array_equal(got, ref)
     assert got[0] == 0.0
 

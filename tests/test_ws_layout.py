@@ -35,6 +35,10 @@ def test_mirror_total_equals_workspace_bytes(nt, K, nf):
 
 def test_record_and_header_sizes():
     assert ws_layout.ITEM.itemsize == 288 and ws_layout.HEADER.itemsize == 64
+    # the package's own two header numbers (ModeSumEngine._workspace, split_plan)
+    assert _lib.HEADER_BYTES == ws_layout.HEADER.itemsize
+    assert _lib.HEADER_SPLIT_PLAN == ws_layout.HEADER.fields["nitems"][1]
+    assert ws_layout.HEADER.fields["nsplit"][1] == _lib.HEADER_SPLIT_PLAN + 4
     assert ws_layout.ITEM.names == ("gx", "ic", "tj", "ph", "fd", "dtj", "fdd", "jser", "fdneg",
                                     "b", "klo", "khi")
     assert ws_layout.SEG1_MAX_K == 64 and ws_layout.TILE_LANES == 768

@@ -12,7 +12,7 @@ for cfg in (dict(Tobs=2.0, dt=10.0, eps=1e-2, nwalkers=16, ntemps=1),
     b = s.half_steps()[0]
     s.like(b, **s.kwargs)
     torch.cuda.synchronize()
-    B = s.like._fused["prep"]
+    B = s.like._fused.prep
     G = B.groups[0]
     for eng in G.engines[:4]:
         h = eng._ws[:64].cpu().numpy().view(np.int32)
