@@ -5,9 +5,13 @@ source is compiled to an object under build/, all of them at once, and one link 
                          -ffp-contract=off each (the host twins, efd_*_cpu: the mode sum's, the
                          reductions' and the noise draws'; AVX-512 is on both this container's
                          Sapphire Rapids and the GPU box's EPYC 9575F)
-  csrc/emrifd_host.cpp -> g++ -O3 -fopenmp: the host upstream stand-ins (trajectory, p0 solve) in C++,
-  the walker batches' staging and the PSD table of the noise-weighted mode selection
-  (csrc/emrifd_psd.h: its NaN and sign guards need a unit built without -ffast-math)
+  csrc/emrifd_host.cpp -> g++ -O3 -fopenmp -ffp-contract=off: the host upstream stand-ins
+  (trajectory, p0 solve) in C++, the walker batches' staging and the PSD table of the
+  noise-weighted mode selection (its NaN and sign guards need a unit built without -ffast-math).
+  The integrator and the root solve are csrc/emrifd_rk45.h and the table's evaluation is
+  csrc/emrifd_psd.h: one text each for this unit and the device (emrifd_traj.hip;
+  emrifd_modes_device.inc), both built without contraction; emrifd_modes.cpp (-ffast-math) must
+  not include emrifd_rk45.h and does not define EFD_HD for emrifd_psd.h
   csrc/emrifd_modes.cpp -> g++ -O3 -ffast-math -fopenmp (libmvec; knots over threads for one-at-a-time
                           calls): amplitudes, mode selection
   csrc/emrifd.hip, emrifd_prepare.hip, emrifd_window.hip, emrifd_reduce.hip (HIP_UNITS: the mode
@@ -20,7 +24,7 @@ source is compiled to an object under build/, all of them at once, and one link 
                          the first two also csrc/emrifd_layout.h (no relocatable device code);
                          emrifd_prepare.hip includes csrc/emrifd_modes_device.inc (amplitudes and
                          mode selection on the device); emrifd_traj.hip includes
-                         csrc/traj_costab.inc (the host's cosine table)
+                         csrc/emrifd_rk45.h and csrc/traj_costab.inc (the host's cosine table)
   link                -> hipcc -shared over the ten objects, with libgomp and libmvec
 """
 

@@ -26,6 +26,11 @@
 
 #include <type_traits>
 
+// the PSD table's evaluation, the text the host compiles too
+#define EFD_HD __device__ inline
+#include "emrifd_psd.h"
+#undef EFD_HD
+
 namespace {
 
 constexpr int MODES_MAX = 4096;           // modes; 2 MODES_MAX branch powers at most
@@ -78,34 +83,6 @@ struct ModesWeights {
 struct ModesNoWeights {};
 
 __host__ __device__ inline int modes_stride(int nmodes) { return (nmodes + 3) & ~3; }
-
-// S(f) of a PPoly-layout table (include/emrifd.h; emrifd_host.cpp: psd_eval, the same bits:
-// every product and sum rounded on its own: contraction is off in these two functions). x: the
-// breakpoints, in LDS or global memory
-__device__ inline double psd_eval_dev(const double* x, const double* c, int n, double f) {
-#pragma clang fp contract(off)
-    int lo = 0, hi = n;   // -> #{j : x[j] <= f} (NaN: n)
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (f < x[mid]) hi = mid; else lo = mid + 1;
-    }
-    const int i = min(max(lo - 1, 0), n - 2);
-    const double s = f - x[i];
-    const int st = n - 1;
-    double r = c[i];
-    r = r * s + c[st + i];
-    r = r * s + c[2 * st + i];
-    return r * s + c[3 * st + i];
-}
-
-// 1 / S(|m f_phi + n f_r|) where S is finite and > 0, else 0
-__device__ inline double psd_weight_dev(const double* x, const double* c, int n, int m, int nn,
-                                        double f_phi, double f_r) {
-#pragma clang fp contract(off)
-    const double F = fabs((double)m * f_phi + (double)nn * f_r);
-    const double S = psd_eval_dev(x, c, n, F);
-    return (isfinite(S) && S > 0.0) ? 1.0 / S : 0.0;
-}
 
 // |A_lmn(p, e)| of the stand-in model (emrifd_modes.cpp: magnitudes)
 __device__ inline double standin_mag(int l, int m, int n, double jit, double p, double e) {
@@ -219,7 +196,7 @@ __global__ __launch_bounds__(MODES_NT) void k_modes_select(
             double wk = 1.0;   // one weight per (knot, mode) serves both branches
             if constexpr (WT)
                 if (weighted)
-                    wk = psd_weight_dev(psd_x, W.c, W.n, B.m[k], B.n[k], f_phi, f_r);
+                    wk = efdpsd::psd_weight(psd_x, W.c, W.n, B.m[k], B.n[k], f_phi, f_r);
             pw[2 * j] = a2 * abs2(d.ylm_p, k);
             if constexpr (WT) pw[2 * j] *= wk;
             part += pw[2 * j];
@@ -472,7 +449,7 @@ int modes_select(const char* fname, const efd_modes_table* tab, const efd_modes_
 __global__ __launch_bounds__(256) void k_psd_eval(const double* x, const double* c, int n,
                                                   const double* f, int64_t nf, double* out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < nf) out[j] = psd_eval_dev(x, c, n, f[j]);
+    if (j < nf) out[j] = efdpsd::psd_eval(x, c, n, f[j]);
 }
 
 }  // namespace

@@ -1,10 +1,10 @@
 // emrifd_traj.hip -- the inspiral trajectory and the p0 root solve on the device, one wavefront
 // per source (efd_traj_batch, efd_traj_p_at_t_batch; include/emrifd.h).
 //
-// STAND-IN PHYSICS, NOT FEW: this restates trajectory.py and csrc/emrifd_host.cpp, the same
-// equations and the same integrator (scipy RK45's Dormand-Prince 5(4), its step control, dense
-// output and terminal separatrix event; Brent's root for the event and for p0). The host forms,
-// efd_host_trajectory and efd_host_p_at_t, are the reference.
+// STAND-IN PHYSICS, NOT FEW. The equations, the integrator and the root solve are
+// csrc/emrifd_rk45.h, the text that emrifd_host.cpp's efd_host_trajectory and efd_host_p_at_t
+// compile too; this unit holds what is the device's own: the quadrature's sums over the wave, the
+// three powers, the knot store and the loop bounds (the side type Wave below), and the kernels.
 //
 // The right-hand side's cost is fundamental()'s 64-node trapezoid over the relativistic anomaly:
 // lane i of the wave64 evaluates node i with the host's cosine table (traj_costab.inc, bit for
@@ -22,49 +22,27 @@
 // bit from there on.
 //
 // Every loop is bounded: accepted plus rejected steps of one integration by 4 EFD_TRAJ_MAX_LEN,
-// the roots by 100 iterations, the bracket by 7 expansions. A source that hits a bound or fails
-// the input checks writes its status word and its wave returns.
+// the roots by 100 iterations, the bracket by 7 expansions: from hi = 40 it is p_at_t's hi > 500
+// test that ends it (40 * 1.5^7 > 500); the driver's own pass bound, P0_MAX_PASSES, is the wider
+// one that the host's hi overrides need and is never reached here. A source that hits a bound or
+// fails the input checks writes its status word and its wave returns.
 #include "emrifd_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr double MTSUN_SI = 4.925491025543576e-06;
-constexpr double YRSID_SI = 31558149.763545603;
-constexpr double TWO_PI = 6.283185307179586476925286766559005768;
-constexpr double DIST_TO_SEPARATRIX = 0.1;
-constexpr int NCHI = 64;
-constexpr int NY = 4;
+#define EFD_HD __device__ __forceinline__
+#define EFD_TABLE __device__ constexpr
+#include "emrifd_rk45.h"
+#undef EFD_TABLE
+#undef EFD_HD
+
 constexpr int STEP_CAP = 4 * EFD_TRAJ_MAX_LEN;   // accepted + rejected steps of one integration
-constexpr int ROOT_MAXITER = 100;
-constexpr int BRACKET_MAX = 7;                   // 40 * 1.5^7 > 500
 
 __constant__ double c_costab[NCHI] = {
 #include "traj_costab.inc"
 };
-
-// scipy RK45 tableau, error weights and dense-output matrix (emrifd_host.cpp's)
-__device__ constexpr double A[6][5] = {
-    {0, 0, 0, 0, 0},
-    {1.0 / 5, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
-__device__ constexpr double B[6] = {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784,
-                                    11.0 / 84};
-__device__ constexpr double E[7] = {-71.0 / 57600, 0.0, 71.0 / 16695, -71.0 / 1920,
-                                    17253.0 / 339200, -22.0 / 525, 1.0 / 40};
-__device__ constexpr double P[7][4] = {
-    {1.0, -8048581381.0 / 2820520608, 8663915743.0 / 2820520608, -12715105075.0 / 11282082432},
-    {0.0, 0.0, 0.0, 0.0},
-    {0.0, 131558114200.0 / 32700410799, -68118460800.0 / 10900136933, 87487479700.0 / 32700410799},
-    {0.0, -1754552775.0 / 470086768, 14199869525.0 / 1410260304, -10690763975.0 / 1880347072},
-    {0.0, 127303824393.0 / 49829197408, -318862633887.0 / 49829197408,
-     701980252875.0 / 199316789632},
-    {0.0, -282668133.0 / 205662961, 2019193451.0 / 616988883, -1453857185.0 / 822651844},
-    {0.0, 40617522.0 / 29380423, -110615467.0 / 29380423, 69997945.0 / 29380423}};
 
 // The two sums of the quadrature over the wave64 in the host's order, ((x0 + x1) + x2) + ...:
 // every lane stores its node to LDS; the lower half-wave then adds the 64 dt in lane order and
@@ -92,7 +70,7 @@ __device__ __forceinline__ void wave_sums_host_order(double dt, double dphi, dou
     sdphi = __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
 }
 
-// Double-double helpers for the three powers below (explicit fma; the unit is built without
+// Double-double helpers for Wave's three powers (explicit fma; the unit is built without
 // contraction).
 struct dd {
     double hi, lo;
@@ -115,267 +93,76 @@ __device__ __forceinline__ dd dd_mul(dd a, dd b) {
     p.lo += fma(a.hi, b.lo, a.lo * b.hi);
     return fast_two_sum(p.hi, p.lo);
 }
-// x^2.5 and x^3.5 correctly rounded (but for ties within 1e-30): x^2 sqrt(x), and that times x,
-// in double-double. The host's std::pow is correctly rounded in 99.92 % of its calls (measured
-// against these forms over 2e6 arguments), so the two agree bit for bit nearly always.
-__device__ __forceinline__ void pow_25_35(double x, double& x25, double& x35) {
-    const double s = sqrt(x);
-    const dd sq = {s, fma(-s, s, x) / (2.0 * s)};
-    const dd r25 = dd_mul(two_prod(x, x), sq);
-    x25 = r25.hi;
-    x35 = dd_mul_d(r25, x).hi;
-}
-// en^a, a = the double nearest -0.2 (-1/5 - 1.11e-17), correctly rounded likewise: one Newton
-// step on y^-5 = en from the library's value in double-double, and the exponent's rounding
-// as the factor 1 - 1.11e-17 ln(en).
-__device__ __forceinline__ double pow_m02(double en) {
-    const double y0 = pow(en, -1.0 / 5.0);
-    const dd y2 = two_prod(y0, y0);
-    const dd y4 = dd_mul(y2, y2);
-    const dd y5 = dd_mul_d(y4, y0);
-    const dd z = dd_mul_d(y5, en);
-    const double r = (1.0 - z.hi) - z.lo;
-    return y0 + y0 * (r / 5.0 - 1.1102230246251565e-17 * log(en));
-}
 
-// Omega_phi, Omega_r of a Schwarzschild eccentric equatorial orbit (emrifd_host.cpp
-// fundamental()): this lane's node of the trapezoid, c = cos(2 pi lane / 64)
-__device__ __forceinline__ void fundamental(double p, double e, double c, double& om_phi,
-                                            double& om_r) {
-    const double k = (p - 2.0) * (p - 2.0) - 4.0 * e * e;
-    const double ec = e * c;
-    const double den = p - 6.0 - 2.0 * ec;
-    const double dphi = sqrt(p / den);
-    const double q = 1.0 + ec;
-    const double dt = p * p / ((p - 2.0 - 2.0 * ec) * q * q) * sqrt(k / den);
-    double sdt, sdphi;
-    wave_sums_host_order(dt, dphi, sdt, sdphi);
-    const double t_r = sdt / NCHI * TWO_PI, phi_r = sdphi / NCHI * TWO_PI;
-    om_phi = phi_r / t_r;
-    om_r = TWO_PI / t_r;
-}
+// The device's side of emrifd_rk45.h: one wave64 integrates one source. Wave counts the knots
+// (the p0 solve needs each integration's end only); WaveStore also stores them.
+struct Wave {
+    static constexpr int STEP_FAILED = EFD_TRAJ_STEP_FAILED, NO_BRACKET = EFD_TRAJ_NO_BRACKET;
+    double c;   // this lane's node of the trapezoid, cos(2 pi lane / NCHI)
 
-// d/d tau of (p, e, Phi_phi, Phi_r), tau = t / M (trajectory.py _pn_rhs)
-__device__ __forceinline__ void rhs(const double* y, double q, double c, double* f) {
-    const double p = y[0], e = y[1], e2 = e * e;
-    const double x = 1.0 - e2;
-    const double a = p / x;
-    double x25, x35;
-    pow_25_35(x, x25, x35);
-    const double da = -(64.0 / 5.0) * q / (a * a * a * x35) *
-                      (1.0 + 73.0 / 24.0 * e2 + 37.0 / 96.0 * e2 * e2);
-    const double de = -(304.0 / 15.0) * q * e / (a * a * a * a * x25) *
-                      (1.0 + 121.0 / 304.0 * e2);
-    f[0] = (1.0 - e2) * da - 2.0 * a * e * de;
-    f[1] = de;
-    fundamental(p, e, c, f[2], f[3]);
-}
-
-__device__ __forceinline__ double sep_event(const double* y) {
-    return y[0] - (6.0 + 2.0 * y[1]) - DIST_TO_SEPARATRIX;
-}
-
-// std::min / std::max as the host writes them (their NaN behaviour included)
-__device__ __forceinline__ double min_h(double a, double b) { return (b < a) ? b : a; }
-__device__ __forceinline__ double max_h(double a, double b) { return (a < b) ? b : a; }
-
-// One step of Brent's method (scipy brentq's loop body, emrifd_host.cpp brentq): from the
-// bracket state with fcur = f(xcur) known, either converges (returns true; the root is xcur) or
-// moves xcur to the next abscissa, whose f the caller supplies before the next call.
-struct Brent {
-    double xpre, xcur, xblk, fpre, fcur, fblk, spre, scur;
+    // x^2.5 and x^3.5 correctly rounded (but for ties within 1e-30): x^2 sqrt(x), and that times
+    // x, in double-double. The host's std::pow is correctly rounded in 99.92 % of its calls
+    // (measured against these forms over 2e6 arguments), so the two agree bit for bit nearly
+    // always.
+    __device__ __forceinline__ static void pow_25_35(double x, double& x25, double& x35) {
+        const double s = sqrt(x);
+        const dd sq = {s, fma(-s, s, x) / (2.0 * s)};
+        const dd r25 = dd_mul(two_prod(x, x), sq);
+        x25 = r25.hi;
+        x35 = dd_mul_d(r25, x).hi;
+    }
+    // en^a, a = the double nearest -0.2 (-1/5 - 1.11e-17), correctly rounded likewise: one Newton
+    // step on y^-5 = en from the library's value in double-double, and the exponent's rounding
+    // as the factor 1 - 1.11e-17 ln(en).
+    __device__ __forceinline__ static double pow_m02(double en) {
+        const double y0 = pow(en, -1.0 / 5.0);
+        const dd y2 = two_prod(y0, y0);
+        const dd y4 = dd_mul(y2, y2);
+        const dd y5 = dd_mul_d(y4, y0);
+        const dd z = dd_mul_d(y5, en);
+        const double r = (1.0 - z.hi) - z.lo;
+        return y0 + y0 * (r / 5.0 - 1.1102230246251565e-17 * log(en));
+    }
+    __device__ __forceinline__ void quad_sums(double p, double e, double k, double& sdt,
+                                              double& sdphi) const {
+        double dt, dphi;
+        quad_node(p, e, k, c, dt, dphi);
+        wave_sums_host_order(dt, dphi, sdt, sdphi);
+    }
+    __device__ __forceinline__ static int step(int steps) {
+        return steps > STEP_CAP ? EFD_TRAJ_STEP_CAP : 0;
+    }
+    __device__ __forceinline__ static int knot(int, double, const double*, const double*) {
+        return 0;
+    }
 };
-__device__ __forceinline__ void brent_init(Brent& b, double xa, double fa, double xb, double fb) {
-    b.xpre = xa; b.fpre = fa; b.xcur = xb; b.fcur = fb;
-    b.xblk = 0.0; b.fblk = 0.0; b.spre = 0.0; b.scur = 0.0;
-}
-__device__ __forceinline__ bool brent_step(Brent& b, double xtol, double rtol) {
-    if (b.fpre != 0.0 && b.fcur != 0.0 && (signbit(b.fpre) != signbit(b.fcur))) {
-        b.xblk = b.xpre;
-        b.fblk = b.fpre;
-        b.spre = b.scur = b.xcur - b.xpre;
-    }
-    if (fabs(b.fblk) < fabs(b.fcur)) {
-        b.xpre = b.xcur; b.xcur = b.xblk; b.xblk = b.xpre;
-        b.fpre = b.fcur; b.fcur = b.fblk; b.fblk = b.fpre;
-    }
-    const double delta = (xtol + rtol * fabs(b.xcur)) / 2.0;
-    const double sbis = (b.xblk - b.xcur) / 2.0;
-    if (b.fcur == 0.0 || fabs(sbis) < delta) return true;
-    if (fabs(b.spre) > delta && fabs(b.fcur) < fabs(b.fpre)) {
-        double stry;
-        if (b.xpre == b.xblk) {
-            stry = -b.fcur * (b.xcur - b.xpre) / (b.fcur - b.fpre);   // interpolate
-        } else {                                                      // extrapolate
-            const double dpre = (b.fpre - b.fcur) / (b.xpre - b.xcur);
-            const double dblk = (b.fblk - b.fcur) / (b.xblk - b.xcur);
-            stry = -b.fcur * (b.fblk * dblk - b.fpre * dpre) / (dblk * dpre * (b.fblk - b.fpre));
-        }
-        if (2.0 * fabs(stry) < min_h(fabs(b.spre), 3.0 * fabs(sbis) - delta)) {
-            b.spre = b.scur;   // good short step
-            b.scur = stry;
-        } else {
-            b.spre = sbis;     // bisect
-            b.scur = sbis;
-        }
-    } else {
-        b.spre = sbis;
-        b.scur = sbis;
-    }
-    b.xpre = b.xcur;
-    b.fpre = b.fcur;
-    if (fabs(b.scur) > delta) b.xcur += b.scur;
-    else b.xcur += (sbis > 0 ? delta : -delta);
-    return false;
-}
 
-// the dense output of the step (t, y) -> t + h at tt: y + h Q (x, x^2, x^3, x^4), x = (tt - t)/h
-__device__ __forceinline__ void dense(const double (*Q)[4], const double* y, double t, double h,
-                                      double tt, double* out) {
-    const double x = (tt - t) / h;
-    const double pw[4] = {x, x * x, x * x * x, x * x * x * x};
-    for (int k = 0; k < NY; ++k) {
-        double acc = 0.0;
-        for (int c = 0; c < 4; ++c) acc += Q[k][c] * pw[c];
-        out[k] = h * acc + y[k];
-    }
-}
+// Knot i goes to the source's slab [7][max_len] as (tau tscale, y, Omega / fden), stored by lane
+// 0; a knot past max_len ends the integration with EFD_TRAJ_TOO_LONG instead (nothing past
+// max_len knots is written).
+struct WaveStore : Wave {
+    double* slab;
+    int max_len;
+    double tscale, fden;
 
-// lane 0 stores knot i of the source's slab [7][max_len]; the caller has checked i < max_len
-__device__ __forceinline__ void store_knot(double* slab, int max_len, int i, double t,
-                                           const double* y, double f_phi, double f_r) {
-    if ((threadIdx.x & (NCHI - 1)) == 0) {
-        slab[i] = t;
-        slab[(size_t)max_len + i] = y[0];
-        slab[2 * (size_t)max_len + i] = y[1];
-        slab[3 * (size_t)max_len + i] = y[2];
-        slab[4 * (size_t)max_len + i] = y[3];
-        slab[5 * (size_t)max_len + i] = f_phi;
-        slab[6 * (size_t)max_len + i] = f_r;
+    __device__ __forceinline__ int knot(int i, double tau, const double* y, const double* om) {
+        // (max_len >= 2, checked ahead of the launch: knot 0 always has room)
+        if (i > 0 && i >= max_len) return EFD_TRAJ_TOO_LONG;
+        double o[2];
+        if (om) { o[0] = om[0]; o[1] = om[1]; }
+        else fundamental(*this, y[0], y[1], o[0], o[1]);
+        if ((threadIdx.x & (NCHI - 1)) == 0) {
+            slab[i] = tau * tscale;
+            slab[(size_t)max_len + i] = y[0];
+            slab[2 * (size_t)max_len + i] = y[1];
+            slab[3 * (size_t)max_len + i] = y[2];
+            slab[4 * (size_t)max_len + i] = y[3];
+            slab[5 * (size_t)max_len + i] = o[0] / fden;
+            slab[6 * (size_t)max_len + i] = o[1] / fden;
+        }
+        return 0;
     }
-}
-
-// The sparse inspiral (emrifd_host.cpp integrate()): the accepted RK45 steps from (0, y0) to the
-// separatrix event or tau_max. STORE: knot i goes to slab as (tau tscale, y, Omega / fden) and a
-// knot past max_len ends the integration with EFD_TRAJ_TOO_LONG (nothing past max_len knots is
-// written). Returns the status; *nt the knot count and *tau_end the last knot's tau on success.
-template <bool STORE>
-__device__ int integrate(double p0, double e0, double pp0, double pr0, double q, double tau_max,
-                         double rtol, double atol, double c, double* slab, int max_len,
-                         double tscale, double fden, int* nt, double* tau_end) {
-    double t = 0.0, y[NY] = {p0, e0, pp0, pr0}, f[NY];
-    rhs(y, q, c, f);
-    double h_abs = min_h(1e-3 * tau_max, 1e4);   // first_step (trajectory.py)
-    int n = 0, steps = 0;
-    if (STORE) store_knot(slab, max_len, n, 0.0, y, f[2] / fden, f[3] / fden);
-    ++n;
-    double g = sep_event(y);
-    double K[7][NY];
-    while (t < tau_max) {
-        const double min_step = 10.0 * fabs(nextafter(t, INFINITY) - t);
-        if (h_abs < min_step) h_abs = min_step;
-        bool accepted = false, rejected = false;
-        double t_new = t, y_new[NY], f_new[NY], h = 0.0;
-        while (!accepted) {
-            if (h_abs < min_step) return EFD_TRAJ_STEP_FAILED;
-            if (++steps > STEP_CAP) return EFD_TRAJ_STEP_CAP;
-            h = h_abs;
-            t_new = t + h;
-            if (t_new - tau_max > 0) t_new = tau_max;
-            h = t_new - t;
-            h_abs = fabs(h);
-            for (int k = 0; k < NY; ++k) K[0][k] = f[k];
-#pragma unroll
-            for (int s = 1; s < 6; ++s) {
-                double ys_[NY];
-                for (int k = 0; k < NY; ++k) {
-                    double dy = 0.0;
-                    for (int r = 0; r < s; ++r) dy += K[r][k] * A[s][r];
-                    ys_[k] = y[k] + dy * h;
-                }
-                rhs(ys_, q, c, K[s]);
-            }
-            for (int k = 0; k < NY; ++k) {
-                double acc = 0.0;
-                for (int r = 0; r < 6; ++r) acc += K[r][k] * B[r];
-                y_new[k] = y[k] + h * acc;
-            }
-            rhs(y_new, q, c, f_new);
-            for (int k = 0; k < NY; ++k) K[6][k] = f_new[k];
-            double en = 0.0;
-            for (int k = 0; k < NY; ++k) {
-                double ek = 0.0;
-                for (int r = 0; r < 7; ++r) ek += K[r][k] * E[r];
-                ek *= h;
-                const double sc = atol + max_h(fabs(y[k]), fabs(y_new[k])) * rtol;
-                en += (ek / sc) * (ek / sc);
-            }
-            en = sqrt(en) / sqrt((double)NY);
-            if (en < 1.0) {
-                double factor = en == 0.0 ? 10.0 : min_h(10.0, 0.9 * pow_m02(en));
-                if (rejected) factor = min_h(1.0, factor);
-                h_abs *= factor;
-                accepted = true;
-            } else {
-                h_abs *= max_h(0.2, 0.9 * pow_m02(en));
-                rejected = true;
-            }
-        }
-        const double g_new = sep_event(y_new);
-        if (g >= 0.0 && g_new <= 0.0) {   // terminal event (direction -1): root of the dense output
-            double Q[NY][4];
-            for (int k = 0; k < NY; ++k)
-                for (int cc = 0; cc < 4; ++cc) {
-                    double acc = 0.0;
-                    for (int r = 0; r < 7; ++r) acc += K[r][k] * P[r][cc];
-                    Q[k][cc] = acc;
-                }
-            const double eps4 = 4.0 * 2.220446049250313e-16;
-            double yy[NY];
-            // brentq(f, t, t_new): f(t) = g's dense-output value, f(t_new) likewise
-            dense(Q, y, t, h, t, yy);
-            const double fa = sep_event(yy);
-            dense(Q, y, t, h, t_new, yy);
-            const double fb = sep_event(yy);
-            double te;
-            if (fa == 0.0) te = t;
-            else if (fb == 0.0) te = t_new;
-            else {
-                Brent b;
-                brent_init(b, t, fa, t_new, fb);
-                for (int i = 0; i < ROOT_MAXITER; ++i) {
-                    if (brent_step(b, eps4, eps4)) break;
-                    dense(Q, y, t, h, b.xcur, yy);
-                    b.fcur = sep_event(yy);
-                }
-                te = b.xcur;
-            }
-            double ye[NY];
-            dense(Q, y, t, h, te, ye);
-            if (STORE) {
-                if (n >= max_len) return EFD_TRAJ_TOO_LONG;
-                double op, orr;
-                fundamental(ye[0], ye[1], c, op, orr);
-                store_knot(slab, max_len, n, te * tscale, ye, op / fden, orr / fden);
-            }
-            ++n;
-            *nt = n;
-            *tau_end = te;
-            return EFD_TRAJ_OK;
-        }
-        g = g_new;
-        t = t_new;
-        for (int k = 0; k < NY; ++k) { y[k] = y_new[k]; f[k] = f_new[k]; }
-        if (STORE) {
-            if (n >= max_len) return EFD_TRAJ_TOO_LONG;
-            store_knot(slab, max_len, n, t * tscale, y, f[2] / fden, f[3] / fden);
-        }
-        ++n;
-    }
-    *nt = n;
-    *tau_end = t;
-    return EFD_TRAJ_OK;
-}
+};
 
 __device__ __forceinline__ bool finite_all(const efd_traj_source& s) {
     return isfinite(s.M) && isfinite(s.mu) && isfinite(s.p0) && isfinite(s.e0) &&
@@ -400,11 +187,11 @@ __global__ __launch_bounds__(NCHI) void k_traj_rk45(const efd_traj_source* __res
     } else {
         const double tscale = s.M * MTSUN_SI;
         const double fden = TWO_PI * s.M * MTSUN_SI;   // (the host's divisor)
+        WaveStore side{{c_costab[lane]}, knots + (size_t)w * 7 * (size_t)max_len, max_len,
+                       tscale, fden};
         double tau_end;
-        st = integrate<true>(s.p0, s.e0, s.Phi_phi0, s.Phi_r0, s.mu / s.M,
-                             s.T * YRSID_SI / tscale, s.rtol, s.atol, c_costab[lane],
-                             knots + (size_t)w * 7 * (size_t)max_len, max_len, tscale, fden, &n,
-                             &tau_end);
+        st = integrate(side, s.p0, s.e0, s.Phi_phi0, s.Phi_r0, s.mu / s.M,
+                       s.T * YRSID_SI / tscale, s.rtol, s.atol, &n, &tau_end);
     }
     if (lane == 0) {
         status[w] = st;
@@ -412,10 +199,7 @@ __global__ __launch_bounds__(NCHI) void k_traj_rk45(const efd_traj_source* __res
     }
 }
 
-// efd_host_p_at_t per source: the default bracket, the upper end times 1.5 until 500, Brent on
-// t_plunge(p0) - t_out. One integration per pass of the loop (a single call site); the bracket's
-// end values are reused as Brent's first two (the function is deterministic, so they are the
-// bits the host recomputes).
+// efd_host_p_at_t per source with the default bracket (emrifd_rk45.h: p_at_t)
 __global__ __launch_bounds__(NCHI) void k_traj_p_at_t(const efd_traj_source* __restrict__ src,
                                                       int count, double xtol, double rtol_root,
                                                       double* __restrict__ p0_out,
@@ -434,50 +218,9 @@ __global__ __launch_bounds__(NCHI) void k_traj_p_at_t(const efd_traj_source* __r
         const double t_out = s.T;
         const double tscale = s.M * MTSUN_SI;
         const double tau_max = (2.0 * t_out + 1.0) * YRSID_SI / tscale;
-        const double rt = max_h(rtol_root, 4 * 2.220446049250313e-16);
-        const double c = c_costab[lane];
-        const double lo = 6.0 + 2.0 * s.e0 + DIST_TO_SEPARATRIX + 1e-3;
-        double hi = 40.0, flo = 0.0, x = lo;
-        int phase = 0, expansions = 0, iters = 0;
-        Brent b;
-        bool done = false;
-        // 1 + (1 + BRACKET_MAX) + ROOT_MAXITER integrations at the most
-        for (int pass = 0; pass < 2 + BRACKET_MAX + ROOT_MAXITER && !done; ++pass) {
-            int n;
-            double tau_end;
-            st = integrate<false>(x, s.e0, 0.0, 0.0, s.mu / s.M, tau_max, s.rtol, s.atol, c,
-                                  nullptr, 0, tscale, 1.0, &n, &tau_end);
-            if (st != EFD_TRAJ_OK) break;
-            const double fx = tau_end * tscale / YRSID_SI - t_out;
-            if (phase == 0) {
-                if (fx > 0) { st = EFD_TRAJ_NO_BRACKET; break; }   // t_out shorter than the plunge
-                flo = fx;                                           // from the buffer
-                phase = 1;
-                x = hi;
-                continue;
-            }
-            if (phase == 1) {
-                if (fx < 0) {
-                    hi *= 1.5;
-                    if (hi > 500 || ++expansions > BRACKET_MAX) { st = EFD_TRAJ_NO_BRACKET; break; }
-                    x = hi;
-                    continue;
-                }
-                if (flo == 0.0) { root = lo; done = true; break; }
-                if (fx == 0.0) { root = hi; done = true; break; }
-                brent_init(b, lo, flo, hi, fx);
-                phase = 2;
-            } else {
-                b.fcur = fx;
-            }
-            if (iters++ >= ROOT_MAXITER || brent_step(b, xtol, rt)) {
-                root = b.xcur;
-                done = true;
-                break;
-            }
-            x = b.xcur;
-        }
-        if (st == EFD_TRAJ_OK && !done) st = EFD_TRAJ_STEP_CAP;   // (unreachable: the pass bound)
+        Wave side{c_costab[lane]};
+        st = p_at_t(side, s.e0, s.mu / s.M, tau_max, s.rtol, s.atol, tscale, t_out,
+                    p0_bracket_lo(s.e0), 40.0, xtol, max_h(rtol_root, EPS4), &root);
     }
     if (lane == 0) {
         status[w] = st;

@@ -1,6 +1,8 @@
 """The inspiral trajectories and the p0 solve on the device (efd_traj_batch,
-efd_traj_p_at_t_batch: one wavefront per source) against the native host forms they restate,
-efd_host_trajectory and efd_host_p_at_t. STAND-IN PHYSICS, NOT FEW.
+efd_traj_p_at_t_batch: one wavefront per source) against the native host forms,
+efd_host_trajectory and efd_host_p_at_t, which compile the same integrator and root solve
+(csrc/emrifd_rk45.h) with their own powers, quadrature loop and knot store. STAND-IN PHYSICS,
+NOT FEW.
 
 The device integrates the same equations with the same integrator and aims at the host's own
 steps: the quadrature is summed in the host's order and the three powers are correctly rounded,
@@ -199,6 +201,25 @@ def test_status_words_without_faults(ref):
     bad[0, 6], bad[1, 7], bad[2, 8] = 0.0, -1e-12, 0.0
     _, _, n3, s3 = _raw_launch(bad, 8, SENT)
     assert s3.tolist() == [_lib.EFD_TRAJ_BAD_SOURCE] * 3 and n3.tolist() == [-7] * 3
+
+
+def test_knot_count_boundary(ref):
+    """The device's knot sink at the boundary (the host's: tests/test_native_upstream.py):
+    max_len = nt succeeds with the knots of the roomy launch; max_len = nt - 1 is
+    EFD_TRAJ_TOO_LONG and nothing behind the slab is written. NO_PLUNGE, one source a launch."""
+    SENT = -777.25
+    row = np.array([[*ref["rows"][4], RTOL, ATOL]])
+    k, tail, nt, status = _raw_launch(row, L, SENT)
+    n = int(nt[0])
+    assert status[0] == _lib.EFD_TRAJ_OK and 2 < n < L and np.all(tail == SENT)
+    assert np.all(k[0, :, :n] != SENT) and np.all(k[0, :, n:] == SENT)
+    k1, tail1, nt1, status1 = _raw_launch(row, n, SENT)
+    assert status1[0] == _lib.EFD_TRAJ_OK and nt1[0] == n and np.all(tail1 == SENT)
+    np.testing.assert_array_equal(k1[0], k[0, :, :n])
+    k2, tail2, nt2, status2 = _raw_launch(row, n - 1, SENT)
+    assert status2[0] == _lib.EFD_TRAJ_TOO_LONG and nt2[0] == -7 and np.all(tail2 == SENT)
+    # what it did write are the first n - 1 knots
+    np.testing.assert_array_equal(k2[0], k[0, :, :n - 1])
 
 
 def test_p_at_t_batch_matches_host(ref):

@@ -14,6 +14,7 @@ stand-ins it restates (trajectory.py, amplitude.py). STAND-IN PHYSICS, NOT FEW.
   walker batch (thread pool) giving the same dicts as serial prepare() calls.
 """
 
+import ctypes
 import threading
 
 import numpy as np
@@ -60,6 +61,50 @@ def test_trajectory_and_p_at_t_match_scipy(trajs, src):
     op, _, orr = get_fundamental_frequencies(0.0, p, e, 0.0)
     np.testing.assert_allclose(fphi, op / (2 * np.pi * M * MTSUN_SI), rtol=1e-13)
     np.testing.assert_allclose(fr, orr / (2 * np.pi * M * MTSUN_SI), rtol=1e-13)
+
+
+def _host_trajectory(lib, row, max_len, sentinel=-777.25):
+    """efd_host_trajectory on sentinel-filled arrays [7][max_len]; nt starts at -7."""
+    a = np.full((7, max_len), sentinel)
+    n = ctypes.c_int32(-7)
+    rc = lib.efd_host_trajectory(*row, 1e-12, 1e-12, max_len, *(a[i].ctypes.data for i in range(7)),
+                                 ctypes.byref(n))
+    return rc, n.value, a
+
+
+def _host_p_at_t(lib, M, mu, e0, t_out, lo, hi):
+    out = ctypes.c_double(-7.0)
+    rc = lib.efd_host_p_at_t(M, mu, e0, t_out, 1e-12, 1e-12, 2e-12, 8.881784197001252e-16, lo, hi,
+                             ctypes.byref(out))
+    return rc, out.value
+
+
+def test_host_knot_count_boundary():
+    """The host's knot sink: a trajectory of exactly max_len knots succeeds with the bits of a
+    roomy call; one knot less room is EFD_ERR_WORKSPACE with the arrays and nt untouched (the
+    device refuses likewise, tests/test_gpu_traj_device.py). NO_PLUNGE: 11 knots, ending at T."""
+    lib = _lib.load()
+    row = (1e6, 10.0, 12.0, 0.2, 0.3, 1.1, 0.5)   # M, mu, p0, e0, Phi_phi0, Phi_r0, T
+    rc, n, ref = _host_trajectory(lib, row, 1000)
+    assert rc == _lib.EFD_OK and n == 11
+    assert np.all(ref[:, :n] != -777.25) and np.all(ref[:, n:] == -777.25)
+    rc, n1, a = _host_trajectory(lib, row, n)
+    assert rc == _lib.EFD_OK and n1 == n
+    np.testing.assert_array_equal(a, ref[:, :n])
+    rc, n2, a = _host_trajectory(lib, row, n - 1)
+    assert rc == _lib.EFD_ERR_WORKSPACE and n2 == -7 and np.all(a == -777.25)
+
+
+def test_host_p_at_t_default_bracket_and_short_t_out():
+    """efd_host_p_at_t: lo = hi = 0 are the default bracket, bit for bit; a t_out shorter than
+    the plunge from the separatrix buffer is EFD_ERR_ARG and leaves *p0 alone."""
+    lib = _lib.load()
+    for M, mu, e0, T in SOURCES:
+        rc0, p0 = _host_p_at_t(lib, M, mu, e0, 0.99 * T, 0.0, 0.0)
+        rc1, p1 = _host_p_at_t(lib, M, mu, e0, 0.99 * T, 6.0 + 2.0 * e0 + 0.1 + 1e-3, 40.0)
+        assert rc0 == rc1 == _lib.EFD_OK and p0 == p1 and 6.0 + 2.0 * e0 + 0.1 < p0 < 40.0
+    rc, p = _host_p_at_t(lib, 1e6, 10.0, 0.3, 1e-4, 0.0, 0.0)
+    assert rc == _lib.EFD_ERR_ARG and p == -7.0
 
 
 @pytest.mark.parametrize("theta", [1.0, 0.3, 2.5])
